@@ -7,9 +7,13 @@ on a synthetic, HBM-resident 28x28x1 batch of 128 images PER GPU, through libt4h
 With --gpus N the batch is sharded by sample (N x 128, weak scaling) and the gradient slab is
 all-reduced (SUM) over RCCL before the optimizer kernel.
 
-The same run also times the 1024x1024x1024 fp32 `matmul` kernel (BASELINE config #2) with HIP
-events and reports it against the fp32 MFMA peak in `roofline`; `roofline_step` carries the
-HBM roofline of the CNN step; `cpu_baseline` is the CPU oracle timed on this box's cores.
+A plain run sets up, warms up, times --steps steps and prints the line; `roofline_step` carries the
+HBM roofline of the CNN step.  --dump-outputs DIR writes what the last timed step computed (see
+dump_outputs).  Everything else needs --full: the run then also times the 1024x1024x1024 fp32
+`matmul` kernel (BASELINE config #2) with HIP events and reports it against the fp32 MFMA peak in
+`roofline`, runs the sustained loop and the extras (GAN, batch 1024, t4_40a, CIFAR, dataset feed,
+first-layer dX on demand, data-parallel overhead), and `cpu_baseline` is the CPU oracle timed on
+this box's cores.
 """
 import argparse
 import ctypes
@@ -45,6 +49,24 @@ def measured_traffic():
 # algorithmic bytes per image and parameter count (SURVEY.md 8d / BASELINE.md 3)
 NETS = {"nn_f": dict(bytes_per_img=494720, params=101030, flop_per_img=3134160),
         "nn_c": dict(bytes_per_img=294800, params=197210, flop_per_img=1605360)}
+# the layers of each net that hold parameters (nn.w / nn.b), by index in NET_WORDS
+PARAM_LAYERS = {"nn_f": (0, 3, 8, 10), "nn_c": (0, 4, 6)}
+
+
+def dump_outputs(vm, net, d):
+    """What the timed path hands its caller after its last step, one float32 .npy per array under `d`: every parameter tensor of
+    the net after the last nn.sgd (l<layer>_w, l<layer>_b) and the output layer's tensor as the step left it (`output`; the
+    reference's backprop writes its loss derivative there in place): under 1 MB of parameters plus 40 B per image.  The net sits
+    on the VM's stack; every fetch pushes it again and drops both."""
+    import numpy as np
+    arrays = {}
+    for L in PARAM_LAYERS[net]:
+        for kind in ("w", "b"):
+            arrays["l%d_%s" % (L, kind)] = vm.fetch("net %d nn.%s" % (L, kind)); vm.eval("drop drop")
+    arrays["output"] = vm.fetch("net -1 n@"); vm.eval("drop drop")
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a, np.float32))
 
 
 def dry_run(rank, world, args):
@@ -270,10 +292,12 @@ def main():
     ap.add_argument("--batch", type=int, default=128, help="images per GPU")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--gemm-iters", type=int, default=200)
-    ap.add_argument("--sustain-s", type=float, default=3.0, help="length of the sustained loop behind the timed region (seconds; 0 = skip)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the GAN / dataset-fed / sustained legs")
+    ap.add_argument("--sustain-s", type=float, default=3.0, help="--full: length of the sustained loop behind the timed region (seconds; 0 = skip)")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the GAN / dataset-fed / sustained legs")
     ap.add_argument("--allow-fallback", action="store_true", help="print the line even when the timed step did not take the conv-stack path (default: exit 4)")
     ap.add_argument("--dry-run", action="store_true", help="launch / rendezvous / reduction plumbing only (gloo, no GPU work, no metric): CPU test of the N-rank path")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: GEMM roofline, sustained loop, extras, CPU baseline, N > 1 exchange figures")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last step computed (parameters, output layer) as DIR/<name>.npy, float32")
     args = ap.parse_args()
 
     # ---- N > 1 asked for from a plain `python bench.py --gpus N`: become N ranks (one process per GPU) or fail - never a 1-rank record
@@ -407,9 +431,12 @@ def main():
         tmax = torch.tensor([dt], device="cuda"); dist.all_reduce(tmax, op=dist.ReduceOp.MAX); dt = float(tmax.cpu()[0])
     ms_step = dt / args.steps * 1e3
     img_s = world * N * args.steps / dt
+    # ---- what the last timed step computed, before anything below steps the net again (replicas are identical: rank 0 writes)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(vm, args.net, args.dump_outputs)
     # ---- sustained loop (same work, >= 3 s): what a long training run sees, and long enough for an external GPU-busy sampler
     sustained = None
-    if args.sustain_s > 0 and not args.no_extras:
+    if args.full and args.sustain_s > 0 and not args.no_extras:
         n_sus = max(args.steps, int(args.sustain_s / (ms_step * 1e-3)))
         barrier()
         t0 = time.perf_counter(); run(n_sus); barrier()
@@ -417,12 +444,12 @@ def main():
         if dp:
             tmax = torch.tensor([sdt], device="cuda"); dist.all_reduce(tmax, op=dist.ReduceOp.MAX); sdt = float(tmax.cpu()[0])
         sustained = (sdt / n_sus * 1e3, n_sus)
-    loss_txt = vm.eval("img forward lbl loss.ce .")       # a fresh forward: after backprop the output tensor holds out - target (reference in-place convention)
+    loss_txt = vm.eval("img forward lbl loss.ce .") if args.full else None   # a fresh forward: after backprop the output tensor holds out - target (reference in-place convention)
     # ---- N > 1, day-one numbers of the exchange (VERDICT r5 #9a; never measured on real xGMI so far): every rank's known-sum probe times, and the EXPOSED
     # exchange time per step = the step above minus the same loop run by every rank on its own (exchange and communicator dropped: the single-GPU step, same
     # process, same clocks).  DESIGN section 6 predicts 5-8 us at 8 ranks.  The replicas diverge from here on - nothing after this reads their weights.
     dp_extra = None
-    if dp and native and world > 1 and os.environ.get("T4_BENCH_DP_EXTRA", "1") != "0":
+    if args.full and dp and native and world > 1 and os.environ.get("T4_BENCH_DP_EXTRA", "1") != "0":
         try:
             probes = [None] * world
             dist.all_gather_object(probes, (neg or {}).get("xchg_probe_us"))
@@ -459,21 +486,22 @@ def main():
             "config": {"workload": "t4_30e %s LeNet-style CNN (examples/t4_30e.4th), 28x28x1, batch %d per GPU, "
                                    "copy-in + forward + backprop + nn.sgd(0.01), dropout on, %s" % (args.net, N, "first layer's dX left to the first reader (T4_LAZY_DX0=1)" if lazy_dx0 else "every layer's dX stored every step incl. the first layer's (the reference's work)"),
                        "global_batch": N * world, "parallelism": "dp%d" % world, "host": "C++ eForth VM (libten4.so) -> C-ABI (libt4hip.so)", "launches_per_step": round(launches, 2), "launches_source": "t4k_launch_count() around the timed loop", "conv_stack": stack_mode, "allreduce": ("one-shot peer exchange inside the optimizer launch (csrc/xchg.hip)" if xchg else ("rccl-native-in-vm" if native else ("torch.distributed" if dp else None))),
-                       "allreduce_fallback_reason": neg["reason"] if neg else None, "ranks_seen": neg["ranks_seen"] if neg else None,
-                       "final_loss_ce": loss_txt.split()[0] if loss_txt.split() else None,
-                       "final_loss_note": "random images and labels, batch-SUM gradients (reference semantics): a throughput run, not a convergence test; training parity vs the oracle is in tests/"},
+                       "allreduce_fallback_reason": neg["reason"] if neg else None, "ranks_seen": neg["ranks_seen"] if neg else None},
             "roofline_step": {"bound": "hbm", "achieved": round(step_bytes / (ms_step * 1e-3) / 1e9, 2), "peak": PEAK_HBM_GBS,
                               "unit": "GB/s", "frac": round(step_bytes / (ms_step * 1e-3) / 1e9 / PEAK_HBM_GBS, 5),
                               "traffic": step_traffic, "traffic_source": traffic_src,
                               "algorithmic_bytes_per_step": step_bytes, "algorithmic_bytes_per_step_eager": step_bytes_eager,
                               "first_layer_dx": "on demand (T4_LAZY_DX0=1): its 2 x 4 B per input element are not in algorithmic_bytes_per_step" if lazy_dx0 else "stored every step"},
         }
+        if loss_txt is not None:
+            out["config"]["final_loss_ce"] = loss_txt.split()[0] if loss_txt.split() else None
+            out["config"]["final_loss_note"] = "random images and labels, batch-SUM gradients (reference semantics): a throughput run, not a convergence test; training parity vs the oracle is in tests/"
         if dp_extra:
             out["dp"] = dp_extra
         if sustained:
             out["sustained_ms_per_step"] = round(sustained[0], 4)
             out["sustained_steps"] = sustained[1]
-        if world == 1 and not dp and not args.no_extras:
+        if args.full and world == 1 and not dp and not args.no_extras:
             # ---- what the data-parallel machinery itself costs on ONE GPU: the same loop with a one-rank exchange in self mode - the optimizer
             # launch takes its exchanging form (k_opt_step<true>: pushes to nobody, adds its own element out of the same code path)
             h = (ctypes.c_ubyte * 64)()
@@ -488,78 +516,79 @@ def main():
                 k.lib.t4k_xchg_self(0)
             k.lib.t4k_xchg_destroy()
             out.update(extras(VM, local, ms_step, args, torch))
-        # ---- GEMM 1024^3 fp32 (word `matmul`), HIP events on the launch stream
-        g = torch.Generator(device="cuda"); g.manual_seed(1234)
-        A = torch.rand(1024, 1024, device="cuda", generator=g); B = torch.rand(1024, 1024, device="cuda", generator=g)
-        O = torch.zeros(1024, 1024, device="cuda")
-        e0 = ctypes.c_void_p(); e1 = ctypes.c_void_p()
-        k.call("t4k_event_create", ctypes.byref(e0)); k.call("t4k_event_create", ctypes.byref(e1))
-        for _ in range(1500):                             # ~35 ms of back-to-back launches: the launch time settles only after the
-            k.call("t4k_gemm", A.data_ptr(), B.data_ptr(), O.data_ptr(), 1.0, 0.0, 0, 0, 1024, 1024, 1024, 1, None)   # clocks ramp (25.3 -> 22.4 us)
-        best = 1e9; tot = 0.0; reps = 5
-        for _ in range(reps):
-            k.call("t4k_event_record", e0, None)
-            for _ in range(args.gemm_iters):
-                k.call("t4k_gemm", A.data_ptr(), B.data_ptr(), O.data_ptr(), 1.0, 0.0, 0, 0, 1024, 1024, 1024, 1, None)
-            k.call("t4k_event_record", e1, None); k.call("t4k_event_sync", e1)
-            ms = ctypes.c_float(0); k.call("t4k_event_elapsed_ms", e0, e1, ctypes.byref(ms))
-            per = ms.value / args.gemm_iters; tot += per; best = min(best, per)
-        avg_ms = tot / reps
-        flops = 2.0 * 1024 ** 3
-        tf = flops / (avg_ms * 1e-3) / 1e12
-        out["roofline"] = {"kernel": "k_gemm_nn_plain (1024^3 fp32 matmul: 64x64 tiles, 8 waves/WG = 2 k-groups x 2x2 v_mfma_f32_32x32x2_f32 accumulator pairs, LDS-DMA from inline asm, 128-deep double-buffered stages)", "bound": "mfma", "achieved": round(tf, 2),
-                           "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": round(tf / PEAK_F32_MFMA_TFLOPS, 4),
-                           "traffic": gemm_traffic, "traffic_source": traffic_src,
-                           "avg_launch_us": round(avg_ms * 1e3, 2), "best_launch_us": round(best * 1e3, 2),
-                           "flop_per_launch": flops}
-        # ---- the same product through the Forth word, reference idiom `for @ drop next` (examples/t4_20a.4th:20-29): per call an arena
-        # allocation for the result, the VM's dispatch, the launch, and `drop` freeing the tensor again
-        vm.eval("1024 1024 matrix rand constant ma\n1024 1024 matrix rand constant mb\n: mx ( A B n -- A B ) 1- for matmul drop next ;\nma mb 1500 mx 2drop\n")
-        torch.cuda.synchronize()
-        wl = []
-        for _ in range(3):
-            t0w = time.perf_counter(); vm.eval("ma mb %d mx 2drop\n" % args.gemm_iters); torch.cuda.synchronize(); wl.append((time.perf_counter() - t0w) / args.gemm_iters * 1e6)
-        out["roofline"]["word_level_us"] = round(sum(wl) / len(wl), 2)
-        out["roofline"]["word_level_note"] = "`ma mb N mx` with `: mx 1- for matmul drop next ;` (t4_20a.4th:20-29 idiom), host clock around the VM call + device sync, %d words per sample" % args.gemm_iters
-        # ---- CPU baseline: the oracle ("port"), bounded sample
-        if not args.no_cpu_baseline and world == 1:       # the CPU baseline is reported by the 1-GPU run only (rank 0 of an N-GPU job just prints)
-            sys.path.insert(0, os.path.join(ROOT, "oracle"))
-            import t4oracle
-            rng = np.random.default_rng(42)
-            lab = rng.integers(0, 10, N).astype(np.uint32)
-            x = rng.random((N, 28, 28, 1)).astype(np.float32)
-            om = build(t4oracle.OracleModel(N, 28, 28, 1, seed=1234))
-            om.forward(x); om.onehot_labels(lab)
-            t0 = time.perf_counter(); nst = 0
-            while True:
-                om.forward(x); om.backprop(); om.sgd(0.01, 0.0); nst += 1
-                if time.perf_counter() - t0 > 3.0 or nst >= 50:
-                    break
-            cdt = time.perf_counter() - t0
-            a = np.random.default_rng(1).random((1024, 1024)).astype(np.float32); o_ = np.zeros((1024, 1024), np.float32)
-            t1 = time.perf_counter()
-            t4oracle.lib().t4o_gemm_host_blocked(t4oracle.P(a), t4oracle.P(a), t4oracle.P(o_), 1.0, 0.0, 1024, 1024, 1024)
-            gdt = time.perf_counter() - t1
-            # all cores: one worker process per core the bench may run on, each training its own batch-N replica (the CPU analogue of
-            # sample sharding), and the blocked host GEMM on row slabs of the same 1024^3 product
-            try:
-                ncore = len(os.sched_getaffinity(0))
-            except Exception:
-                ncore = os.cpu_count() or 1
-            wr = cpu_workers(["step", args.net, N, 4.0], ncore)
-            all_img_s = sum(N * r[0] / r[1] for r in wr if len(r) == 2 and r[1] > 0)
-            rows = max(4, 1024 // ncore)
-            gr = cpu_workers(["gemm", rows, 1024, 1024, 2.0], ncore)
-            all_gflops = sum(r[0] * 2.0 * rows * 1024 * 1024 / r[1] for r in gr if len(r) == 2 and r[1] > 0) / 1e9
-            out["cpu_baseline"] = {"value": round(all_img_s, 1), "unit": "images/s", "cores": len(wr), "kind": "port",
-                                   "sample": "%d worker processes (one per core), each ~4 s of oracle training steps of the same %s batch-%d workload "
-                                             "(%d steps in total); single thread: %d steps in %.1f s" % (len(wr), args.net, N, int(sum(r[0] for r in wr)), nst, cdt),
-                                   "single_thread_value": round(N * nst / cdt, 1),
-                                   "host_cores_available": os.cpu_count(),
-                                   "gemm_1024_host_blocked_ms": round(gdt * 1e3, 1),
-                                   "gemm_1024_host_gflops": round(flops / gdt / 1e9, 2),
-                                   "gemm_1024_host_gflops_all_cores": round(all_gflops, 1), "gemm_all_cores_workers": len(gr),
-                                   "gemm_note": "reference's blocked host GEMM (tensor.cu:97-123 restated): one thread on the full 1024^3 product, then %d workers on %d-row slabs for ~2 s" % (len(gr), rows)}
+        if args.full:
+            # ---- GEMM 1024^3 fp32 (word `matmul`), HIP events on the launch stream
+            g = torch.Generator(device="cuda"); g.manual_seed(1234)
+            A = torch.rand(1024, 1024, device="cuda", generator=g); B = torch.rand(1024, 1024, device="cuda", generator=g)
+            O = torch.zeros(1024, 1024, device="cuda")
+            e0 = ctypes.c_void_p(); e1 = ctypes.c_void_p()
+            k.call("t4k_event_create", ctypes.byref(e0)); k.call("t4k_event_create", ctypes.byref(e1))
+            for _ in range(1500):                             # ~35 ms of back-to-back launches: the launch time settles only after the
+                k.call("t4k_gemm", A.data_ptr(), B.data_ptr(), O.data_ptr(), 1.0, 0.0, 0, 0, 1024, 1024, 1024, 1, None)   # clocks ramp (25.3 -> 22.4 us)
+            best = 1e9; tot = 0.0; reps = 5
+            for _ in range(reps):
+                k.call("t4k_event_record", e0, None)
+                for _ in range(args.gemm_iters):
+                    k.call("t4k_gemm", A.data_ptr(), B.data_ptr(), O.data_ptr(), 1.0, 0.0, 0, 0, 1024, 1024, 1024, 1, None)
+                k.call("t4k_event_record", e1, None); k.call("t4k_event_sync", e1)
+                ms = ctypes.c_float(0); k.call("t4k_event_elapsed_ms", e0, e1, ctypes.byref(ms))
+                per = ms.value / args.gemm_iters; tot += per; best = min(best, per)
+            avg_ms = tot / reps
+            flops = 2.0 * 1024 ** 3
+            tf = flops / (avg_ms * 1e-3) / 1e12
+            out["roofline"] = {"kernel": "k_gemm_nn_plain (1024^3 fp32 matmul: 64x64 tiles, 8 waves/WG = 2 k-groups x 2x2 v_mfma_f32_32x32x2_f32 accumulator pairs, LDS-DMA from inline asm, 128-deep double-buffered stages)", "bound": "mfma", "achieved": round(tf, 2),
+                               "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": round(tf / PEAK_F32_MFMA_TFLOPS, 4),
+                               "traffic": gemm_traffic, "traffic_source": traffic_src,
+                               "avg_launch_us": round(avg_ms * 1e3, 2), "best_launch_us": round(best * 1e3, 2),
+                               "flop_per_launch": flops}
+            # ---- the same product through the Forth word, reference idiom `for @ drop next` (examples/t4_20a.4th:20-29): per call an arena
+            # allocation for the result, the VM's dispatch, the launch, and `drop` freeing the tensor again
+            vm.eval("1024 1024 matrix rand constant ma\n1024 1024 matrix rand constant mb\n: mx ( A B n -- A B ) 1- for matmul drop next ;\nma mb 1500 mx 2drop\n")
+            torch.cuda.synchronize()
+            wl = []
+            for _ in range(3):
+                t0w = time.perf_counter(); vm.eval("ma mb %d mx 2drop\n" % args.gemm_iters); torch.cuda.synchronize(); wl.append((time.perf_counter() - t0w) / args.gemm_iters * 1e6)
+            out["roofline"]["word_level_us"] = round(sum(wl) / len(wl), 2)
+            out["roofline"]["word_level_note"] = "`ma mb N mx` with `: mx 1- for matmul drop next ;` (t4_20a.4th:20-29 idiom), host clock around the VM call + device sync, %d words per sample" % args.gemm_iters
+            # ---- CPU baseline: the oracle ("port"), bounded sample
+            if not args.no_cpu_baseline and world == 1:       # the CPU baseline is reported by the 1-GPU run only (rank 0 of an N-GPU job just prints)
+                sys.path.insert(0, os.path.join(ROOT, "oracle"))
+                import t4oracle
+                rng = np.random.default_rng(42)
+                lab = rng.integers(0, 10, N).astype(np.uint32)
+                x = rng.random((N, 28, 28, 1)).astype(np.float32)
+                om = build(t4oracle.OracleModel(N, 28, 28, 1, seed=1234))
+                om.forward(x); om.onehot_labels(lab)
+                t0 = time.perf_counter(); nst = 0
+                while True:
+                    om.forward(x); om.backprop(); om.sgd(0.01, 0.0); nst += 1
+                    if time.perf_counter() - t0 > 3.0 or nst >= 50:
+                        break
+                cdt = time.perf_counter() - t0
+                a = np.random.default_rng(1).random((1024, 1024)).astype(np.float32); o_ = np.zeros((1024, 1024), np.float32)
+                t1 = time.perf_counter()
+                t4oracle.lib().t4o_gemm_host_blocked(t4oracle.P(a), t4oracle.P(a), t4oracle.P(o_), 1.0, 0.0, 1024, 1024, 1024)
+                gdt = time.perf_counter() - t1
+                # all cores: one worker process per core the bench may run on, each training its own batch-N replica (the CPU analogue of
+                # sample sharding), and the blocked host GEMM on row slabs of the same 1024^3 product
+                try:
+                    ncore = len(os.sched_getaffinity(0))
+                except Exception:
+                    ncore = os.cpu_count() or 1
+                wr = cpu_workers(["step", args.net, N, 4.0], ncore)
+                all_img_s = sum(N * r[0] / r[1] for r in wr if len(r) == 2 and r[1] > 0)
+                rows = max(4, 1024 // ncore)
+                gr = cpu_workers(["gemm", rows, 1024, 1024, 2.0], ncore)
+                all_gflops = sum(r[0] * 2.0 * rows * 1024 * 1024 / r[1] for r in gr if len(r) == 2 and r[1] > 0) / 1e9
+                out["cpu_baseline"] = {"value": round(all_img_s, 1), "unit": "images/s", "cores": len(wr), "kind": "port",
+                                       "sample": "%d worker processes (one per core), each ~4 s of oracle training steps of the same %s batch-%d workload "
+                                                 "(%d steps in total); single thread: %d steps in %.1f s" % (len(wr), args.net, N, int(sum(r[0] for r in wr)), nst, cdt),
+                                       "single_thread_value": round(N * nst / cdt, 1),
+                                       "host_cores_available": os.cpu_count(),
+                                       "gemm_1024_host_blocked_ms": round(gdt * 1e3, 1),
+                                       "gemm_1024_host_gflops": round(flops / gdt / 1e9, 2),
+                                       "gemm_1024_host_gflops_all_cores": round(all_gflops, 1), "gemm_all_cores_workers": len(gr),
+                                       "gemm_note": "reference's blocked host GEMM (tensor.cu:97-123 restated): one thread on the full 1024^3 product, then %d workers on %d-row slabs for ~2 s" % (len(gr), rows)}
         if dp:
             all_alive(dist, torch, world, torch.device("cuda", local))   # a line is printed only by a job whose ranks are ALL still there
         print(json.dumps(out), flush=True)

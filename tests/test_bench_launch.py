@@ -2,12 +2,14 @@
 
 CPU tests drive the self-spawn with the dry-run transport (gloo, no GPU work); the GPU tests check that a 1-GPU box refuses
 `--gpus 2` instead of printing a 1-rank record, and that the forced data-parallel path (one-rank RCCL communicator owned by the
-library, all-reduce inside the VM's `nn.sgd`) produces a valid line."""
+library, all-reduce inside the VM's `nn.sgd`) produces a valid line (with --full), and that a plain run stays headline-only and dumps
+what its last step computed (--dump-outputs)."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -69,7 +71,30 @@ def test_launch_helpers():
 
 @pytest.mark.gpu
 def test_forced_data_parallel_path_on_one_gpu():
-    rc, rec, err = _run(["--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--gemm-iters", "20"], {"T4_BENCH_FORCE_DP": "1"})
+    rc, rec, err = _run(["--full", "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--gemm-iters", "20"], {"T4_BENCH_FORCE_DP": "1"})
     assert rc == 0, err
     assert rec["n_gpus"] == 1 and rec["config"]["allreduce"] == "rccl-native-in-vm" and rec["value"] > 0
     assert rec["roofline"]["frac"] > 0.3 and rec["roofline"]["word_level_us"] > rec["roofline"]["avg_launch_us"] * 0.9
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_what_the_last_step_computed(tmp_path):
+    """A plain run prints the headline line without the figures that take runs of their own (those need --full), and --dump-outputs
+    writes what the last timed step computed: every parameter of the net and the output layer's tensor, float32.  Two runs with the
+    same arguments start from the same inputs, so their dumps agree."""
+    dumps = []
+    for i in range(2):
+        d = tmp_path / ("run%d" % i)
+        rc, rec, err = _run(["--steps", "3", "--warmup", "1", "--dump-outputs", str(d)])
+        assert rc == 0, err
+        assert rec["steps"] == 3 and rec["unit"] == "images/s" and rec["higher_is_better"] is True and rec["dtype"] == "f32"
+        assert rec["value"] > 0 and rec["ms_per_step"] > 0
+        assert not {"roofline", "cpu_baseline", "sustained_ms_per_step", "gan_round_ms", "dp_overhead_us"} & set(rec), sorted(rec)
+        arrs = {f[:-4]: np.load(str(d / f)) for f in os.listdir(str(d)) if f.endswith(".npy")}
+        assert {"l0_w", "l0_b", "l3_w", "l3_b", "l8_w", "l8_b", "l10_w", "l10_b", "output"} == set(arrs)
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrs.values())
+        assert sum(a.size for k, a in arrs.items() if k != "output") == 101030          # nn_f's parameter count (bench.NETS)
+        assert arrs["output"].size == 128 * 10
+        dumps.append(arrs)
+    for k in dumps[0]:
+        np.testing.assert_allclose(dumps[1][k], dumps[0][k], rtol=1e-5, atol=1e-6, err_msg=k)

@@ -8,8 +8,8 @@ O=$R/gpurun_out/$TAG
 RAW=/tmp/t4prof_$TAG            # raw rocprofv3 output (databases, per-dispatch CSVs: tens of MB) stays on the box; only the summaries go to gpurun_out/
 mkdir -p "$O" "$RAW"
 cd /tmp && export TMPDIR=/tmp
-python "$R/bench.py" > "$O/bench.json" 2> "$O/bench.err"
-B="python $R/bench.py --no-cpu-baseline --no-extras"
+python "$R/bench.py" --full > "$O/bench.json" 2> "$O/bench.err"
+B="python $R/bench.py --full --no-cpu-baseline --no-extras"
 timeout 600 rocprofv3 --kernel-trace --stats -d "$RAW/kt" -o bench -- $B > "$O/kt.log" 2>&1
 timeout 600 rocprofv3 --kernel-trace -f csv -d "$RAW/pmc_mfma" -o bench --pmc SQ_WAVES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAVE_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F32 -- $B > "$O/pmc_mfma.log" 2>&1
 timeout 600 rocprofv3 --kernel-trace -f csv -d "$RAW/pmc_hbm" -o bench --pmc TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum -- $B > "$O/pmc_hbm.log" 2>&1
