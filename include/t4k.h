@@ -185,6 +185,13 @@ int t4k_gemm(const float *A, const float *B, float *O, float alpha, float beta,
 /* k_gemm :370 / k_gemm_claude :411 (words gemm1/gemm2): double accumulator, tA/tB ignored */
 int t4k_gemm_f64acc(const float *A, const float *B, float *O, float alpha, float beta,
                     int M, int N, int K, int C, t4k_stream_t s);
+/* NumPy `@` over a batch (tenvm.cpp:277-287; _tdot :328-366 and Tensor::mm tensor.cu:161-180 loop one product per sample):
+ *   O[b] = alpha * op(A[b]) @ op(B[b]) + beta * O[b]  for b in [0, batch), each a per-channel product with element stride C
+ *   exactly as t4k_gemm.  A[b] = A + b*sA (sA == 0 broadcasts A over the batch), likewise B[b], O[b] (sO >= M*N*C when batch > 1).
+ *   cA / cB: 1 when that operand has one channel serving all C output channels (stored without a channel axis), else C.
+ * One launch per call, no allocation, no synchronisation (legal under capture); beta == 0 never reads O.  fp32 MFMA. */
+int t4k_gemm_batched(const float *A, const float *B, float *O, float alpha, float beta, int tA, int tB,
+                     int M, int N, int K, int C, int cA, int cB, int batch, long sA, long sB, long sO, t4k_stream_t s);
 
 /* ------------------------------------------------ linear algebra (t4math.cu) */
 /* Tensor::inverse tensor.cu:344-369 (k_find_pivot/k_swap_rows/k_diag/k_elim :742-836):

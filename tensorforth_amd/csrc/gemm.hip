@@ -2265,9 +2265,71 @@ int gemm_launch(const float *A, const float *B, float *O, const float *bias, flo
     return T4K_OK;
 }
 
+// ------------------------------------------------------------------------------------------
+// Batched products of large matrices (t4k_gemm_batched, gemm_batched.hip): the tile kernel above, one output tile of one batch entry per
+// workgroup - grid = (tiles, batch entries, channels).  Operand b sits at A + b * sA (sA == 0: one A for every entry), likewise B and O.
+// Entries beyond the 65535 of grid.y are walked by the same workgroups.  Split-K, riders and the gates stay off (nsplit = 1).
+template <int BM, int BN, int BK, bool AKC, bool BKC, bool VEC, bool SKEW, bool FULL>
+__global__ void __launch_bounds__(256) k_gemm_mfma_batched(GemmP p, long sA, long sB, long sO, int batch) {
+    for (int b = blockIdx.y; b < batch; b += gridDim.y) {
+        GemmP q = p;
+        q.A += b * sA; q.B += b * sB; q.O += b * sO;
+        gemm_mfma_body<BM, BN, BK, AKC, BKC, VEC, SKEW, FULL>(q, blockIdx.x, 0, blockIdx.z);
+        __syncthreads();                                   // the next entry's first stage overwrites LDS
+    }
+}
+template <int BM, int BN, int BK, bool VEC, bool SKEW, bool FULL>
+void launch_batched(const GemmP &p, dim3 grid, int tA, int tB, long sA, long sB, long sO, int batch, hipStream_t s) {
+    constexpr size_t lds_bytes = (size_t)2 * (BM + BN) * BK * sizeof(float);
+    auto pick = [&](auto kern) {
+        static bool attr_done = false;
+        if (!attr_done) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+            attr_done = true;
+        }
+        T4K_LAUNCH(kern, grid, dim3(256), lds_bytes, s, p, sA, sB, sO, batch);
+    };
+    if (!tA && !tB) pick(k_gemm_mfma_batched<BM, BN, BK, true,  false, VEC, SKEW, FULL>);
+    else if (!tA)   pick(k_gemm_mfma_batched<BM, BN, BK, true,  true,  VEC, SKEW, FULL>);
+    else if (!tB)   pick(k_gemm_mfma_batched<BM, BN, BK, false, false, VEC, SKEW, FULL>);
+    else            pick(k_gemm_mfma_batched<BM, BN, BK, false, true,  VEC, SKEW, FULL>);
+}
+
 } // namespace
 
 namespace t4k {
+// every channel of every operand present (no channel broadcast); the caller has checked the arguments
+int gemm_batched_tiles(const float *A, const float *B, float *O, float alpha, float beta, int tA, int tB,
+                       int M, int N, int K, int C, int batch, long sA, long sB, long sO, hipStream_t hs) {
+    GemmP p;
+    p.A = A; p.B = B; p.O = O; p.bias = nullptr; p.part = nullptr;
+    p.M = M; p.N = N; p.K = K; p.C = C; p.alpha = alpha; p.beta = beta;
+    p.kchunk = K; p.nsplit = 1; p.pair = 0; p.sync = st().d_sync;
+    p.cs_X = nullptr; p.cs_out = nullptr; p.cs_rows = 0; p.cs_E = 0; p.xmap = 0; p.Z = nullptr;
+    // 16-byte loads: C == 1, every entry's base aligned (strides too), contiguous extents divisible by 4
+    const int a_contig = tA ? M : K, b_contig = tB ? K : N;
+    const bool vec = C == 1 && aligned16(A) && aligned16(B) && sA % 4 == 0 && sB % 4 == 0 && a_contig % 4 == 0 && b_contig % 4 == 0;
+    const long per = (long)batch * C;
+    const long t128 = (long)((M + 127) / 128) * ((N + 127) / 128);
+    const bool big = t128 * per >= (long)st().cu_count * 3 / 4;
+    const int BMv = big ? 128 : 64;
+    p.tiles_m = (M + BMv - 1) / BMv; p.tiles_n = (N + BMv - 1) / BMv;
+    const dim3 grid((unsigned)(p.tiles_m * p.tiles_n), (unsigned)std::min(batch, 65535), (unsigned)C);
+    if (big) {
+        const bool full = vec && K % 32 == 0 && M >= 4 && N >= 4;
+        if (full)     launch_batched<128, 128, 32, true, true, true>(p, grid, tA, tB, sA, sB, sO, batch, hs);
+        else if (vec) launch_batched<128, 128, 32, true, true, false>(p, grid, tA, tB, sA, sB, sO, batch, hs);
+        else          launch_batched<128, 128, 32, false, false, false>(p, grid, tA, tB, sA, sB, sO, batch, hs);
+    } else if (!vec) {
+        launch_batched<64, 64, 32, false, false, false>(p, grid, tA, tB, sA, sB, sO, batch, hs);
+    } else if (K % 64 == 0 && M >= 4 && N >= 4) {
+        launch_batched<64, 64, 64, true, false, true>(p, grid, tA, tB, sA, sB, sO, batch, hs);
+    } else {
+        launch_batched<64, 64, 64, true, true, false>(p, grid, tA, tB, sA, sB, sO, batch, hs);
+    }
+    T4K_LAUNCH_CHECK();
+    return T4K_OK;
+}
 void gemm_set_spin_err(int *p) { (void)hipMemcpyToSymbol(HIP_SYMBOL(g_spin_err_dev), &p, sizeof(p)); }
 
 int colsum_add(const float *X, float *OUT, long rows, int E, hipStream_t hs);

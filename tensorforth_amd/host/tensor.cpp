@@ -279,6 +279,28 @@ Tensor &Tensor::mm(Tensor &A, Tensor &B, Tensor &O, bool inc, bool tA, bool tB) 
         chk(t4k_gemm(A.slice(Na == 1 ? 0 : n), B.slice(Nb == 1 ? 0 : n), O.slice(n), 1.0f, inc ? 1.0f : 0.0f, tA, tB, H, W, Ka, C, stream()), "gemm");
     return O;
 }
+// The batched products `@` gains beyond the reference's _tdot (tenvm.cpp:277-287 gives NumPy @ as the meaning): O[n] = A[n] @ B[n]
+// for n < max(Na, Nb), an operand with N == 1 broadcast over the batch and one with C == 1 over the channels.  A is [M,K] per
+// sample (a vector is [1,K]), B [K,P], O [M,P].  One t4k_gemm_batched launch; t4k_gemm_batched is referenced weakly so that the
+// host sources still link over a C-ABI without it (the CPU oracle), which then takes the per-matrix t4k_gemm loop below.
+#pragma weak t4k_gemm_batched
+Tensor &Tensor::bmm(Tensor &A, Tensor &B, Tensor &O, uint32_t M, uint32_t K, uint32_t P) {
+    const uint32_t Na = A.N(), Nb = B.N(), Ca = A.C(), Cb = B.C(), N = std::max(Na, Nb), C = std::max(Ca, Cb);
+    const long sA = Na == 1 ? 0 : (long)A.HWC(), sB = Nb == 1 ? 0 : (long)B.HWC(), sO = (long)O.HWC();
+    if (t4k_gemm_batched) {
+        chk(t4k_gemm_batched(A.data, B.data, O.data, 1.0f, 0.0f, 0, 0, M, P, K, C, Ca, Cb, N, sA, sB, sO, stream()), "gemm_batched");
+        return O;
+    }
+    for (uint32_t n = 0; n < N; n++) {
+        const float *a = A.data + n * sA, *b = B.data + n * sB;
+        float *o = O.data + n * sO;
+        if (Ca == Cb)  chk(t4k_gemm(a, b, o, 1.0f, 0.0f, 0, 0, M, P, K, C, stream()), "gemm");
+        else if (Ca == 1) chk(t4k_gemm(a, b, o, 1.0f, 0.0f, 0, 0, M, P * C, K, 1, stream()), "gemm");   // [M,K] @ [K,P*C]
+        else for (uint32_t m = 0; m < M; m++)                                                         // row m: [P,C] = B^T @ A[m] ([K,C])
+            chk(t4k_gemm(b, a + (size_t)m * K * C, o + (size_t)m * P * C, 1.0f, 0.0f, 1, 0, P, C, K, 1, stream()), "gemm");
+    }
+    return O;
+}
 Tensor &Tensor::gemm(int variant, Tensor &A, Tensor &B, Tensor &O, DU alpha, DU beta) {   // words gemm, gemm1..4 (tensor.cu:97-201)
     const uint32_t H = A.H(), W = B.W(), Ka = A.W(), Kb = B.H();
     const uint32_t Na = A.N(), Nb = B.N(), C = B.C(), N = std::max(Na, Nb);

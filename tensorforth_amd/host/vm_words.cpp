@@ -85,6 +85,15 @@ void VM::blas2(int op, bool keep) {
         else if (A.rank == 2 && B.rank == 2 && A.W() == B.H()) { C = &st().tensor(A.H(), B.W()); Tensor::mm(A, B, *C); }
         else if ((A.N() == 1 || B.N() == 1) && A.N() != B.N() && A.C() == B.C() && A.W() == B.H()) {
             C = &st().tensor(std::max(A.N(), B.N()), A.H(), B.W(), A.C()); Tensor::mm(A, B, *C);
+        }
+        // beyond _tdot (NumPy @, tenvm.cpp:277-287): batched rank-4 pairs, N or C broadcast from either side, vector on the left
+        else if (A.rank != 1 && B.rank != 1 && (A.rank == 4 || B.rank == 4) && A.W() == B.H() &&
+                 (A.N() == B.N() || A.N() == 1 || B.N() == 1) && (A.C() == B.C() || A.C() == 1 || B.C() == 1)) {
+            C = &st().tensor(std::max(A.N(), B.N()), A.H(), B.W(), std::max(A.C(), B.C())); Tensor::bmm(A, B, *C, A.H(), A.W(), B.W());
+        } else if (A.rank == 1 && B.rank == 2 && A.numel == B.H()) {
+            C = &st().tensor(B.W()); Tensor::bmm(A, B, *C, 1, B.H(), B.W());
+        } else if (A.rank == 1 && B.rank == 4 && A.numel == B.H()) {
+            C = &st().tensor(B.N(), 1, B.W(), B.C()); Tensor::bmm(A, B, *C, 1, B.H(), B.W());
         } else { pstr("A.W != B.H dim?"); return; }
         if (!keep) { DROP(POP()); DROP(POP()); }
         PUSH(*C);
