@@ -383,6 +383,11 @@ typedef struct t4k_conv_stage {
     t4k_poolblock run;        /* all-zero layers + KS = 1: no run */
 } t4k_conv_stage;
 int t4k_conv_stack_ok(const t4k_conv_stage *st, int n_stage, int N);           /* 1 when the stack qualifies (shapes, layers, LDS) and its kernels are built */
+/* read-only: the launch plan t4k_conv_stack_fwd / _bwd take for this stack and batch - *split = bands per image of the forward, *bsplit = bands
+ * of the banded backward (1: whole image per workgroup).  Both follow from N and the CU count (as many bands, <= 4, as give every CU a
+ * workgroup while every band keeps a row of every grid and the LDS plan fits).  Returns 1 and fills both, or 0 (nothing written) when the
+ * stack does not qualify (t4k_conv_stack_ok == 0). */
+int t4k_conv_stack_plan(const t4k_conv_stage *st, int n_stage, int N, int *split, int *bsplit);
 int t4k_conv_stack_selftest(void);   /* the stack kernels are compiled at run time (hipRTC) for the model's shapes: this compiles two reference
                                       * shape sets for gfx950 - no device needed - and returns 0, or an error with the compiler log in t4k_last_error() */
 /* The stack AND the classifier head behind its flatten in ONE launch: [conv + run] x n, flatten, linear E1 -> E0a, one element-wise layer

@@ -302,6 +302,7 @@ int t4k_xchg_active(void) { return 0; }
 
 // the sample-resident conv stack is a launch-count optimisation of the product: the oracle VM always runs the separate layers
 int t4k_conv_stack_ok(const t4k_conv_stage *, int, int) { return 0; }
+int t4k_conv_stack_plan(const t4k_conv_stage *, int, int, int *, int *) { return 0; }
 int t4k_conv_stack_release(const float *) { return T4K_OK; }
 int t4k_conv_stack_dx0_pending(const float *) { return 0; }
 int t4k_conv_stack_dx0(const t4k_conv_stage *, int, t4k_stream_t) { return T4K_OK; }

@@ -8,6 +8,7 @@ import ctypes
 import numpy as np
 import pytest
 
+import f64_witness as wt
 from test_gpu_parity import Dev, PoolBlock, p, rel
 
 pytestmark = pytest.mark.gpu
@@ -113,6 +114,114 @@ def _params(rng, Cin, stages):
     return out
 
 
+_lay_base = _lay
+
+
+def _lay(oracle):
+    """the layer codes above, plus the element-wise layers only the geometry sweep runs"""
+    return dict(_lay_base(oracle), selu=(oracle.L_SELU, 0.0), sigmoid=(oracle.L_SIGMOID, 0.0))
+
+
+FWD_KEYS = ("O", "pre_mask", "pre_out", "pool_out", "post_mask", "post_out", "copy_out")
+BWD_KEYS = ("O", "pre_out", "pool_out", "post_out", "DXS", "DF", "DB")
+
+
+def down_stage(dev, bufs, ref, keys):
+    """host copies of the stack's buffers (shaped as the oracle's tensors; DXS as the conv input, DF / DB as stored)"""
+    out = []
+    for si, d in enumerate(bufs):
+        t = {}
+        for k_ in keys:
+            if k_ in d and (k_ in ref[si] or k_ in ("DXS", "DF", "DB")):
+                v = dev.down(d[k_])
+                t[k_] = v.reshape(ref[si][k_].shape) if k_ in ref[si] else (v.reshape(ref[si]["in"].shape) if k_ == "DXS" else v)
+        out.append(t)
+    return out
+
+
+ALPHA = {"dropout": 0.5, "relu": 0.0, "leaky": 0.1, "tanh": 0.0, "elu": 1.0, "selu": 0.0, "sigmoid": 0.0}
+
+
+def _last_key(st_):
+    C0, K, pre, pool, post = st_
+    return "post_out" if post else ("pool_out" if pool else ("pre_out" if pre else "O"))
+
+
+def _witness_act(name, kind, x, mask, out):
+    """an element-wise layer of a run against float64 on its own stored input: relu / leaky masks exact, dropout's output = input x its
+    stored mask (the mask itself is bit-exact against the oracle's Philox slice), the transcendental layers within their ulp bounds"""
+    if kind == "dropout":
+        wt.check(name + " out", out, wt.act_from(kind, x, ALPHA[kind], mask), kind="dropout out")
+        return
+    wo, wm = wt.act(kind, x, ALPHA[kind])
+    wt.check(name + " out", out, wo, kind=kind + " out")
+    wt.check(name + " mask", mask, wm, kind=kind + " mask")
+
+
+def witness_forward(X, stages, params, t, who="stack"):
+    """every tensor a stack forward wrote (t: per stage host copies of O, pre_mask, pre_out, pool_out, post_mask, post_out, copy_out) against
+    float64 applied to the operands the same forward stored: stage s's conv reads stage s-1's stored output, each layer of a run its stored
+    input - errors do not compound across stages"""
+    x = X
+    for si, (C0, K, pre, pool, post) in enumerate(stages):
+        F, B = params[si]; d = t[si]; nm = "%s stage %d" % (who, si)
+        wt.check(nm + " O", d["O"], wt.conv_fwd(x, F, B), kind="conv O")
+        cur = d["O"]
+        if pre:
+            _witness_act(nm + " pre " + pre, pre, cur, d["pre_mask"], d["pre_out"]); cur = d["pre_out"]
+        if pool:
+            wt.check(nm + " pool " + pool, d["pool_out"], wt.pool(pool, cur), kind=pool + "pool"); cur = d["pool_out"]
+        if post:
+            _witness_act(nm + " post " + post, post, cur, d["post_mask"], d["post_out"]); cur = d["post_out"]
+        if "copy_out" in d:
+            wt.equal(nm + " copy_out", d["copy_out"], cur)
+        x = cur
+
+
+def witness_backward(stages, params, fwd, got, DY, DF0, DB0, who="stack", skip_dx0=False):
+    """every tensor a stack backward wrote against float64 on the operands it used: fwd = per stage the forward state the backward read
+    ("in" = the conv input, the run's masks and pool inputs), got = per stage the buffers after the backward (O holds dO: the in-place
+    convention; the run's inner tensors their gradients; DXS, DF, DB).  Each step is witnessed from the stack's own stored predecessor:
+    mask multiplies within one rounding, pool routing exact from the stored pool input, dX / dF / dB from the stored dO.  DF0 / DB0: what
+    the gradients held before (the fold adds)."""
+    g = DY
+    for si in range(len(stages) - 1, -1, -1):
+        C0, K, pre, pool, post = stages[si]
+        F, B = params[si]; t = fwd[si]; b = got[si]; nm = "%s stage %d" % (who, si)
+        g = np.asarray(g).reshape(t[_last_key(stages[si])].shape)
+        if post:
+            tgt = "pool_out" if pool else ("pre_out" if pre else "O")
+            wt.check(nm + " bwd " + tgt, b[tgt], wt.mul(g, t["post_mask"]), kind="mask multiply"); g = b[tgt]
+        if pool:
+            tgt = "pre_out" if pre else "O"
+            wt.check(nm + " dpool " + pool, b[tgt], wt.dpool(pool, g, t[tgt]), kind="d" + pool + "pool"); g = b[tgt]
+        if pre:
+            wt.check(nm + " bwd O", b["O"], wt.mul(g, t["pre_mask"]), kind="mask multiply"); g = b["O"]
+        dO = g
+        X = t["in"]; N, H, Wd, C1 = X.shape
+        if not (skip_dx0 and si == 0):
+            wt.check(nm + " dX", b["DXS"], wt.conv_dx(dO, F, H, Wd), kind="conv dX")
+        wt.check(nm + " dF", b["DF"], wt.conv_df(X, dO, K, acc=DF0), kind="conv dF")
+        wt.check(nm + " dB", b["DB"], wt.conv_db(dO, acc=DB0), kind="conv dB")
+        g = b["DXS"]
+
+
+def witness_head(xf, W1, B1, W2, B2, mid, Y1, Fm, Am, Y2, Pr, who="stack"):
+    """the classifier head behind the stack: linear 1 on the stored flattened image, the element-wise layer on the stored Y1, linear 2 on
+    its stored output, softmax on the stored Y2 - every probability within its own ulp bound, however small"""
+    wt.check(who + " head Y1", Y1, wt.linear(xf, W1, B1), kind="linear")
+    cur = Y1
+    if mid:
+        _witness_act(who + " head " + mid, mid, Y1, Fm, Am); cur = Am
+    wt.check(who + " head Y2", Y2, wt.linear(cur, W2, B2), kind="linear")
+    wt.check(who + " head P", Pr, wt.softmax(Y2), kind="softmax")
+
+
+def oracle_bwd_as_got(want):
+    """the oracle's backward buffers in the layout witness_backward reads"""
+    return [dict(t, DXS=t["DX"]) for t in want]
+
+
 @pytest.mark.parametrize("case", range(len(CASES)))
 def test_conv_stack_forward_matches_the_separate_layers(t4k, dev, oracle, case):
     N, H, W, Cin, stages, flat = CASES[case]
@@ -143,6 +252,9 @@ def test_conv_stack_forward_matches_the_separate_layers(t4k, dev, oracle, case):
                     assert np.mean(np.abs(got - t[k_]) > 1e-3) < 1e-4, "stage %d %s" % (si, k_)
                 continue
             assert rel(got, t[k_]) < RTOL, "stage %d %s: %.3g" % (si, k_, rel(got, t[k_]))
+    # float64 witness, element by element: the stack's tensors on its own stored operands, and the oracle's on its own
+    witness_forward(X, stages, params, down_stage(dev, bufs, ref, FWD_KEYS))
+    witness_forward(X, stages, params, ref, who="oracle")
 
 
 def _oracle_backward(oracle, ref, stages, flat, params, DY):
@@ -223,6 +335,8 @@ def test_conv_stack_backward_matches_the_separate_layers(t4k, dev, oracle, case,
                 continue                                   # the run's last tensor without a flatten behind it: nothing writes it
             got = dev.down(d[k_]).reshape(t[k_].shape)
             assert rel(got, t[k_]) < RTOL, "stage %d bwd %s: %.3g" % (si, k_, rel(got, t[k_]))
+    witness_backward(stages, params, ref, down_stage(dev, bufs, ref, BWD_KEYS), DY, 0.25, -0.5)
+    witness_backward(stages, params, ref, oracle_bwd_as_got(want), DY, None, None, who="oracle")
 
 
 @pytest.mark.parametrize("case", range(len(CASES)))
@@ -267,6 +381,9 @@ def test_conv_stack_forward_then_backward_uses_what_the_forward_saved(t4k, dev, 
             if k_ not in t or (si + 1 < len(stages) and k_ == last) or (k_ == last and "copy_out" not in t):
                 continue
             assert rel(dev.down(d[k_]).reshape(t[k_].shape), t[k_]) < RTOL, "stage %d bwd %s: %.3g" % (si, k_, rel(dev.down(d[k_]).reshape(t[k_].shape), t[k_]))
+    witness_forward(X, stages, params, got_fwd)
+    witness_backward(stages, params, got_fwd, down_stage(dev, bufs, ref, BWD_KEYS), DY, 0.25, -0.5)
+    witness_backward(stages, params, got_fwd, oracle_bwd_as_got(want), DY, None, None, who="oracle")
 
 
 def test_conv_stack_refuses_what_it_cannot_hold(t4k, dev, oracle):
@@ -371,6 +488,10 @@ def test_conv_stack_with_classifier_head_in_one_launch(t4k, dev, oracle, case, E
             assert rel(dev.down(d["Am"]), Am) < RTOL, "rep %d activation" % rep
         assert rel(dev.down(d["Y2"]), Y2) < RTOL, "rep %d linear 2: %.3g" % (rep, rel(dev.down(d["Y2"]), Y2))
         assert rel(dev.down(d["P"]), Pr) < RTOL, "rep %d softmax: %.3g" % (rep, rel(dev.down(d["P"]), Pr))
+    witness_forward(X, stages, params, down_stage(dev, bufs, ref, FWD_KEYS))
+    witness_head(xf, W1, B1, W2, B2, mid, Y1, Fm, Am, Y2, Pr, who="oracle")
+    witness_head(dev.down(bufs[-1]["copy_out"]).reshape(N, -1), W1, B1, W2, B2, mid, dev.down(d["Y1"]), dev.down(d["Fm"]), dev.down(d["Am"]),
+                 dev.down(d["Y2"]), dev.down(d["P"]))
 
 
 def test_lenet_steps_while_another_stream_hogs_the_device_are_deterministic():

@@ -6,6 +6,8 @@ import ctypes
 import numpy as np
 import pytest
 
+import f64_witness as wt
+
 pytestmark = pytest.mark.gpu
 RTOL = 1e-4
 
@@ -93,6 +95,8 @@ def test_gemm_vs_oracle(t4k, dev, oracle, M, N, K, tA, tB):
         dA, dB_, dO = dev.up(A), dev.up(B), dev.up(O0)
         t4k.call("t4k_gemm", p(dA), p(dB_), p(dO), alpha, beta, tA, tB, M, N, K, 1, None)
         assert relx(dev.down(dO), ref, D) < RTOL
+        w = wt.gemm(A, B, O0, alpha, beta, tA, tB)                      # float64, every element within its own bound
+        wt.check("gemm %dx%dx%d" % (M, N, K), dev.down(dO), w); wt.check("oracle gemm", ref, w)
 
 
 def test_gemm_channel_interleaved_and_unaligned(t4k, dev, oracle):
@@ -229,15 +233,22 @@ def test_conv2d(t4k, dev, oracle, K, S, P_, N, H1, C1, C0):
     dI, dF, dB_, dO = dev.up(I), dev.up(F), dev.up(B), dev.zeros(ref.shape)
     t4k.call("t4k_conv2d_fwd", p(dI), p(dO), p(dF), p(dB_), N, H1, H1, C1, H0, H0, C0, K, S, P_, None)
     assert relx(dev.down(dO), ref, D) < RTOL
+    w = wt.conv_fwd(I, F, B, S, P_)
+    wt.check("conv2d fwd", dev.down(dO), w); wt.check("oracle conv2d fwd", ref, w)
     g = rng.standard_normal(ref.shape).astype(np.float32)
     DX = np.zeros_like(I); DF = rng.standard_normal(F.shape).astype(np.float32); DB = rng.standard_normal(C0).astype(np.float32)
+    DF0, DB0 = DF.copy(), DB.copy()
     dDX, dDF, dDB, dg = dev.zeros(I.shape), dev.up(DF), dev.up(DB), dev.up(g)
     o.t4o_conv2d_bwd(P(I), P(g), P(DX), P(F), P(DF), P(DB), N, H1, H1, C1, H0, H0, C0, K, S, P_, 1)
     t4k.call("t4k_conv2d_bwd", p(dI), p(dg), p(dDX), p(dF), p(dDF), p(dDB), N, H1, H1, C1, H0, H0, C0, K, S, P_, 1, None)
     assert relx(dev.down(dDX), DX, D) < RTOL and relx(dev.down(dDF), DF, D) < RTOL and relx(dev.down(dDB), DB, D) < RTOL
+    wdx, wdf, wdb = wt.conv_dx(g, F, H1, H1, S, P_), wt.conv_df(I, g, K, S, P_, acc=DF0), wt.conv_db(g, acc=DB0)
+    wt.check("conv2d dX", dev.down(dDX), wdx); wt.check("conv2d dF", dev.down(dDF), wdf); wt.check("conv2d dB", dev.down(dDB), wdb)
+    wt.check("oracle conv2d dX", DX, wdx); wt.check("oracle conv2d dF", DF, wdf); wt.check("oracle conv2d dB", DB, wdb)
     # train == 0 leaves DF/DB untouched
     t4k.call("t4k_conv2d_bwd", p(dI), p(dg), p(dDX), p(dF), p(dDF), p(dDB), N, H1, H1, C1, H0, H0, C0, K, S, P_, 0, None)
     assert relx(dev.down(dDF), DF, D) < RTOL
+    wt.check("conv2d dF (train 0)", dev.down(dDF), wdf)
 
 
 def test_conv2d_unsupported_geometry_is_reported(t4k, dev):
