@@ -244,3 +244,272 @@ def mul(g, m):
     """g * mask (backward of an element-wise layer): one rounding"""
     e = f64(g) * f64(m)
     return W(e, np.abs(e), 1, 1.0)
+
+
+# ----------------------------------------------------------------------------- reductions (k_reduce1 / k_reduce2, k_dot, k_dlinear_db)
+# ulps of an fp32 natural log on either side, relative to |log x|: libm's logf <= 1 ulp (the oracle passes with ULP_LOG_LIBM = 2).  The GPU's
+# __logf is v_log_f32 (a base-2 log) times ln 2; neither kernel guide states the instruction's error near 1, so it was MEASURED: worst
+# |__logf(x) - ln x| / (2^-24 |ln x|) over x in [0.01, 0.99 + 1e-6] (the BCE arguments, |ln x| >= 0.01; t4k_math LN on 1.5 M points and single-term
+# t4k_bce calls) - see MEASURED_LOG below and tests/README.md.  The allowance is twice the measurement, rounded up.
+MEASURED_LOG = 3.137    # MI355X: t4k_math LN 3.137, single BCE terms 2.234 (tests/test_gpu_small_kernels_sweep.py::test_device_log_error_is_inside_the_allowance prints both)
+ULP_LOG = 6.3           # 2 x 3.137, rounded up
+ULP_LOG_LIBM = 2.0
+EPS = float(np.float32(1.0e-6))                                    # DU_EPS as the kernels hold it
+
+
+def is_int_exact(n, max_term):
+    """every fp32 partial sum of n terms of magnitude <= max_term (integers) is an integer below 2^24: exact in ANY order"""
+    return float(n) * float(max_term) < 2.0 ** 24
+
+
+def _sum_w(terms, n_extra=0, exact=False, axis=None):
+    t = f64(terms)
+    if exact:                                                      # small-integer operands: the result must be bit-equal
+        assert is_int_exact(t.shape[0] if axis == 0 else t.size, np.max(np.abs(t)) if t.size else 0.0) and np.all(t == np.rint(t)), "not integer-exact"
+        return W(t.sum(axis), 0.0, 0)
+    return W(t.sum(axis), np.abs(t).sum(axis), (t.shape[0] if axis == 0 else t.size) + n_extra)
+
+
+def reduce_sum(x, exact=False):
+    return _sum_w(np.ravel(x), 0, exact)
+
+
+def reduce_nvar(x, avg, exact=False):
+    """sum (x - avg)^2 with avg as the fp32 scalar the ABI passes: a subtraction and a product behind every term"""
+    d = f64(np.ravel(x)) - float(np.float32(avg))
+    return _sum_w(d * d, 3, exact)
+
+
+def reduce_ext(x, op):
+    """max / min: exact (fmaxf / fminf pick one of the operands; +0 / -0 compare equal, see the sweep's signed-zero case)"""
+    return W(np.max(f64(x)) if op == "max" else np.min(f64(x)), 0.0, 0)
+
+
+def nan_inf(x):
+    x = np.asarray(x); return W(float(np.count_nonzero(np.isnan(x) | np.isinf(x))), 0.0, 0)
+
+
+def dot(A, B, O0=None, alpha=1.0, beta=0.0, exact=False):
+    """O[c] = alpha <A[:, c], B[:, c]> + beta O[c] on [K, C] operands; beta == 0 leaves O unread (the BLAS convention, as `gemm` above)"""
+    A = f64(A); B = f64(B); K = A.shape[0]
+    alpha = float(np.float32(alpha)); beta = float(np.float32(beta))
+    ex = alpha * (A * B).sum(0); mg = abs(alpha) * (np.abs(A) * np.abs(B)).sum(0)
+    if beta != 0:
+        ex = ex + beta * f64(O0); mg = mg + abs(beta) * np.abs(f64(O0))
+    if exact:
+        assert is_int_exact(1, np.max(mg)) and np.all(ex == np.rint(ex)), "not integer-exact"
+        return W(ex, 0.0, 0)
+    return W(ex, mg, K + 2)
+
+
+def dlinear_db(DY, DB0):
+    """DB[e] += sum_n DY[n, e]"""
+    return conv_db(DY, acc=DB0)
+
+
+def bce_terms(T, O):
+    """the float64 terms t ln(o + eps) + (1 - t) ln(1 - o + eps) and their two halves' magnitudes"""
+    t = f64(np.ravel(T)); o = f64(np.ravel(O))
+    a = t * np.log(o + EPS); b = (1.0 - t) * np.log(1.0 - o + EPS)
+    return a + b, np.abs(a) + np.abs(b), np.abs(t) + np.abs(1.0 - t)
+
+
+def bce(T, O, ulp_log=None):
+    """sum of the terms.  Per term: each log carries ulp_log ulps of its own value plus the rounding of its argument (o + eps, 1 - o + eps:
+    two roundings of a number near its own size = an ABSOLUTE 2 u on the log), the (1 - t), the two products and the addition three more
+    roundings of the term's magnitude; the sum adds n roundings of sum |terms| (any order).  Encoded as n * (sum|terms| + E / n)."""
+    ulp_log = ULP_LOG if ulp_log is None else ulp_log
+    term, mg, tw = bce_terms(T, O)
+    n = term.size
+    E = float(((ulp_log + 3.0) * mg + 2.0 * tw).sum())
+    return W(term.sum(), np.abs(term).sum() + E / max(1, n), n)
+
+
+# ----------------------------------------------------------------------------- batch norm ([NHW, C] view; stat = [1 / (sigma + eps) | mean | -])
+def bn_stats(X):
+    """(mean witness, 1 / (sigma + eps) witness) per channel, as the reference writes them: var = E[x^2] - mean^2, eps OUTSIDE the root.
+    The computed q = E[x^2] and m = mean each carry gamma = C_SUM (n + 2) u of sum |terms| (n terms, the products, the division), so
+        |var_hat - var| <= dvar = gamma (q + 2 |m| mean|x|) + 2 u (q + m^2)        (m^2's product and the subtraction)
+    - the cancellation in q - m^2 is NOT in a constant: dvar / var grows as (mean / sigma)^2.  1 / (sigma + eps) is monotone in var, so the
+    result lies between r(var + dvar) and r(max(var - dvar, 0)) (first order: dvar / (2 sigma (sigma + eps)^2)), plus three roundings
+    (root, sum, quotient) of r itself."""
+    x = f64(X).reshape(-1, X.shape[-1]); n = x.shape[0]
+    m = x.mean(0); a = np.abs(x).mean(0); q = (x * x).mean(0)
+    var = np.maximum(q - m * m, 0.0); sig = np.sqrt(var); r = 1.0 / (sig + EPS)
+    gam = C_SUM * (n + 2) * U
+    dvar = gam * (q + 2.0 * np.abs(m) * a) + 2.0 * U * (q + m * m)
+    lo = 1.0 / (np.sqrt(var + dvar) + EPS); hi = 1.0 / (np.sqrt(np.maximum(var - dvar, 0.0)) + EPS)
+    br = np.maximum(hi - r, r - lo) + 3.0 * U * r
+    return W(m, a, n + 1), W(r, br / U, 1, 1.0)
+
+
+def bn_xhat(X, stat):
+    """xhat = (x - mean) * rstd from the STORED statistics: two roundings"""
+    x = f64(X).reshape(-1, X.shape[-1]); C = x.shape[1]; s = f64(stat)
+    e = (x - s[C:2 * C]) * s[:C]
+    return W(e, np.abs(e), 2, 1.0)
+
+
+def bn_y(XH, Wg, B):
+    """y = xhat * gamma + beta from the STORED xhat: a product and a sum (or one fused rounding)"""
+    xh = f64(XH).reshape(-1, XH.shape[-1]); g = f64(Wg); b = f64(B)
+    return W(xh * g + b, np.abs(xh * g) + np.abs(b), 2, 1.0)
+
+
+def bn_bwd_stats(DY, XH, DW0, DB0, train):
+    """(s1 = mean dy, s2 = mean dy * xhat, DW, DB): the MEANS are accumulated into the parameter gradients (reference quirk), train == 0
+    leaves them untouched (exact)"""
+    dy = f64(DY).reshape(-1, DY.shape[-1]); xh = f64(XH).reshape(dy.shape); n = dy.shape[0]
+    s1, a1 = dy.mean(0), np.abs(dy).mean(0); s2, a2 = (dy * xh).mean(0), np.abs(dy * xh).mean(0)
+    if train:
+        wdw = W(f64(DW0) + s2, np.abs(f64(DW0)) + a2, n + 3); wdb = W(f64(DB0) + s1, np.abs(f64(DB0)) + a1, n + 2)
+    else:
+        wdw = W(f64(DW0), 0.0, 0); wdb = W(f64(DB0), 0.0, 0)
+    return W(s1, a1, n + 1), W(s2, a2, n + 2), wdw, wdb
+
+
+def bn_dx(Wg, DY, XH, stat):
+    """dx = (rstd * gamma) * (dy - s1 - xhat * s2) from the STORED rstd / s1 / s2: five roundings of the magnitude"""
+    dy = f64(DY).reshape(-1, DY.shape[-1]); xh = f64(XH).reshape(dy.shape); C = dy.shape[1]; s = f64(stat); g = f64(Wg)
+    k = s[:C] * g; s1 = s[C:2 * C]; s2 = s[2 * C:3 * C]
+    return W(k * (dy - s1 - xh * s2), np.abs(k) * (np.abs(dy) + np.abs(s1) + np.abs(xh * s2)), 5, 1.0)
+
+
+# ----------------------------------------------------------------------------- log-softmax layer as the reference writes it
+def logsoftmax(X, ulp_log=None):
+    """O = exp(x) - log10(max(sum_c exp(x), 1e-6)).  e_j errs by E_j = ULP_EXP + 2 |x_j| ulps; the row sum S by (max E + C) ulps, which
+    moves log10 S by that much / ln 10 ABSOLUTELY; the log itself ulp_log ulps of |log10 S|; the subtraction one rounding of e + |log10 S|."""
+    ulp_log = ULP_LOG if ulp_log is None else ulp_log
+    x = f64(X); C = x.shape[-1]
+    e = np.exp(x); E = ULP_EXP + 2.0 * np.abs(x)
+    S = np.maximum(e.sum(-1, keepdims=True), EPS); ls = np.log10(S)
+    mag = E * e + (E.max(-1, keepdims=True) + C) / np.log(10.0) + ulp_log * np.abs(ls) + (e + np.abs(ls))
+    return W(e - ls, mag, 1, 1.0)
+
+
+# ----------------------------------------------------------------------------- optimizers: one step, element-wise (a handful of roundings)
+def _f(v):
+    return float(np.float32(v))
+
+
+def sgd(G, DG, M, Nw, lr, b):
+    """(weights, momentum or None): d = dg / Nw; b == 0: g - lr d (3 roundings); else m' = b m + (1 - b) d (5), g' = g - lr m' (7 in all)"""
+    g, d, lr, b = f64(G), f64(DG) / float(Nw), _f(lr), _f(b)
+    if abs(b) < EPS:
+        return W(g - lr * d, np.abs(g) + np.abs(lr * d), 3, 1.0), None
+    m = b * f64(M) + (1.0 - b) * d; mm = np.abs(b * f64(M)) + np.abs((1.0 - b) * d)
+    return W(g - lr * m, np.abs(g) + lr * mm, 7, 1.0), W(m, mm, 5, 1.0)
+
+
+def _moments(DG, M, V, b1, b2):
+    d = f64(DG)
+    m = b1 * f64(M) + (1.0 - b1) * d; mm = np.abs(b1 * f64(M)) + np.abs((1.0 - b1) * d)
+    v = b2 * f64(V) + (1.0 - b2) * d * d; vm = np.abs(b2 * f64(V)) + (1.0 - b2) * d * d
+    return d, m, mm, v, vm
+
+
+def adam(G, DG, M, V, lr, b1, b2):
+    """(weights, m, v): m' 4 roundings, v' 5, g' = g - lr m' / (sqrt v' + eps): m's 4, half of v's 5, root, sum, product, quotient, difference
+    <= 12 of |g| + lr mag(m') / (sqrt v' + eps); no bias correction, eps outside the root (the reference's Adam)"""
+    lr, b1, b2 = _f(lr), _f(b1), _f(b2)
+    d, m, mm, v, vm = _moments(DG, M, V, b1, b2)
+    den = np.sqrt(np.maximum(v, 0.0)) + EPS
+    return W(f64(G) - lr * m / den, np.abs(f64(G)) + lr * mm / den, 12, 1.0), W(m, mm, 4, 1.0), W(v, vm, 5, 1.0)
+
+
+def adamw(G, DG, M, V, lr, b1, b2, wd):
+    """g' = g - lr (m' / (sqrt v' + eps) - wd d) as the reference writes it (the decay multiplies the GRADIENT): 14 roundings"""
+    lr, b1, b2, wd = _f(lr), _f(b1), _f(b2), _f(wd)
+    d, m, mm, v, vm = _moments(DG, M, V, b1, b2)
+    den = np.sqrt(np.maximum(v, 0.0)) + EPS
+    return (W(f64(G) - lr * (m / den - wd * d), np.abs(f64(G)) + lr * (mm / den + np.abs(wd * d)), 14, 1.0), W(m, mm, 4, 1.0), W(v, vm, 5, 1.0))
+
+
+# ----------------------------------------------------------------------------- transposed convolution (dconv.hip: K = 4, S = 2, P = 1)
+def dconv_out(H1, K=4, S=2, P=1):
+    """output extent of the layer, with the output padding the odd grids take"""
+    return (H1 - 1) * S - 2 * P + K + (H1 + 2 * P - K) % S
+
+
+def dconv_fwd(I, F, B, H0, W0, S=2, P=1):
+    """O[n, i S + ky - P, j S + kx - P, co] = B[co] + sum_ci F[ci, ky, kx, co] I[n, i, j, ci] (no tap flip): the dX of the virtual conv O -> I,
+    whose filter is F with the channel roles swapped; conv_dx applies the reference's flip, so the taps are flipped here to cancel it"""
+    Fv = np.ascontiguousarray(f64(F).transpose(3, 1, 2, 0)[:, ::-1, ::-1, :])
+    w = conv_dx(I, Fv, H0, W0, S, P)
+    return W(w.exact + f64(B), w.mag + np.abs(f64(B)), w.n + 1)
+
+
+def dconv_bwd(I, dO, F, DF0, DB0, S=2, P=1):
+    """(dX, dF, dB): dX is the plain convolution of dO with F (channel roles swapped), dF the virtual conv's filter gradient folded back
+    (one more rounding: it is formed apart and added), dB the column sum of dO"""
+    K = F.shape[1]
+    Fv = np.ascontiguousarray(f64(F).transpose(3, 1, 2, 0))
+    wdx = conv_fwd(dO, Fv, np.zeros(F.shape[0]), S, P)
+    w = conv_df(dO, I, K, S, P)
+    wdf = W(w.exact.transpose(3, 1, 2, 0) + f64(DF0), w.mag.transpose(3, 1, 2, 0) + np.abs(f64(DF0)), w.n + 2)
+    return wdx, wdf, conv_db(dO, acc=DB0)
+
+
+# ----------------------------------------------------------------------------- linear algebra, by residual
+# c of the residual bounds.  PLU: |P A - L U| <= gamma_K |L| |U| (Higham 9.3) -> C_SUM.  A column of the inverse solved from computed factors:
+# |A x - e| <= 3 gamma_K |L| |U| |x| (Higham 9.4); |L| |U| is held to |A| by the pivot growth (the issue's form), and Gauss-Jordan eliminates
+# above the diagonal as well (twice the operations): c = 3 * 2 * 1.01 rounded up.
+C_LINALG = 8.0
+
+
+def perm_of(piv):
+    """row order after the sequential swaps row k <-> row piv[k]"""
+    p = np.arange(len(piv))
+    for k, q in enumerate(np.asarray(piv)):
+        if q != k:
+            p[[k, q]] = p[[q, k]]
+    return p
+
+
+def pivot_growth(A, piv=None):
+    """max_k max|a^(k)_ij| / max|a_ij| of Gaussian elimination in float64 on the given pivot order (None: partial pivoting), and that order"""
+    a = f64(A).copy(); K = a.shape[0]; top = g = float(np.max(np.abs(a))); used = []
+    for z in range(K):
+        u = int(piv[z]) if piv is not None else z + int(np.argmax(np.abs(a[z:, z])))
+        used.append(u)
+        if u != z:
+            a[[z, u]] = a[[u, z]]
+        if a[z, z] == 0.0:
+            break
+        a[z + 1:, z + 1:] -= np.outer(a[z + 1:, z] / a[z, z], a[z, z + 1:]); a[z + 1:, z] = 0.0
+        g = max(g, float(np.max(np.abs(a))))
+    return g / max(top, 1e-300), np.array(used)
+
+
+def inverse_residual(A, X, piv=None):
+    """witness of R = A @ X (float64 product of the fp32 A and the fp32 X the implementation returned) against I"""
+    A = f64(A); K = A.shape[0]; rho, _ = pivot_growth(A, piv)
+    return W(np.eye(K), (np.abs(A) @ np.abs(f64(X))) * rho, K, C_LINALG)
+
+
+def plu_residual(A, piv):
+    """witness of L @ U (float64 product of the stored factors) against P A; the magnitude |L| |U| is the caller's (see plu_check)"""
+    return f64(A)[perm_of(piv)]
+
+
+def split_lu(LU):
+    LU = f64(LU); return np.tril(LU, -1) + np.eye(LU.shape[0]), np.triu(LU)
+
+
+def plu_check(name, A, LU, piv, kind=None):
+    L, Uu = split_lu(LU); K = L.shape[0]
+    return check(name, L @ Uu, W(plu_residual(A, piv), np.abs(L) @ np.abs(Uu), K, C_SUM), kind=kind)
+
+
+def inverse_check(name, A, X, piv=None, kind=None):
+    return check(name, f64(A) @ f64(X), inverse_residual(A, X, piv), kind=kind)
+
+
+def logdet(LU):
+    """(sum log |u_ii| on the STORED factors: K logs of 2 ulps each and K additions; sign exact)"""
+    d = np.diag(f64(LU)); l = np.log(np.abs(d)); K = d.size
+    return W(l.sum(), np.abs(l).sum(), K + 3, 1.0), int(np.prod(np.sign(d)))
+
+
+def lu_extract(LU, get_u):
+    L, Uu = split_lu(LU); return W(Uu if get_u else L, 0.0, 0)

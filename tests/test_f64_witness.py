@@ -246,3 +246,267 @@ def test_defect_table_against_both_bars(oracle, o):
     assert np.mean(np.abs(m - (x > 0)) > 1e-3) < 1e-4
     assert not passes(m, wt.act("relu", x)[1])
     print("%-32s old bar fraction %.3g (misses)  witness rejects" % ("relu mask flipped at one element", np.mean(np.abs(m - (x > 0)) > 1e-3)))
+
+
+# ============================================================================= the small kernels (tests/test_gpu_small_kernels_sweep.py)
+# The oracle runs through EVERY shape of the GPU sweep (tests/small_kernel_cases.py) and a second honest fp32 order with it: the inputs are
+# known to keep an honest implementation inside each bound before a GPU sees them.  Then the defects a tiled reduction makes.
+import ctypes
+
+import small_kernel_cases as sk
+
+
+def old_sum_bar(got, x):
+    """tests/test_gpu_parity.py::test_reductions' bar for a sum: within 1e-4 sum |x|"""
+    return abs(float(got) - f64sum(x)) < 1e-4 * max(1.0, float(np.abs(np.asarray(x, np.float64)).sum()))
+
+
+def f64sum(x):
+    return float(np.asarray(x, np.float64).sum())
+
+
+def relx_old(a, b, depth=1):
+    """test_gpu_parity.relx's figure (tensor norm and element-aware, the floor growing with the depth)"""
+    a = np.atleast_1d(np.asarray(a, np.float64)); b = np.atleast_1d(np.asarray(b, np.float64))
+    floor = 1e-3 * max(1.0, (float(depth) / 32.0) ** 0.5); mx = max(1e-30, float(np.max(np.abs(b)))); d = np.abs(a - b)
+    r = np.sort((d / (np.abs(b) + floor * mx)).ravel()); allowed = int((1.0 - 0.9999) * r.size + 1e-9)
+    return max(float(np.max(d)) / mx, float(r[r.size - 1 - allowed]))
+
+
+def test_reductions_every_sweep_size_and_the_defects_of_a_tiled_sum(oracle, o):
+    rng = np.random.default_rng(60)
+    x = sk.ints(rng, sk.RED_N[-1] + 8)
+    for n in sk.RED_N:
+        for off in sk.RED_OFFSETS:
+            s = x[off:off + n]; w = wt.reduce_sum(s, exact=True)
+            wt.check("oracle int sum n=%d" % n, oracle.reduce(oracle.RED_SUM, s), w); wt.check("pairwise int sum", np.sum(s, dtype=np.float32), w)
+            if wt.is_int_exact(n, 16):
+                wv = wt.reduce_nvar(s, 1.0, exact=True)
+                wt.check("oracle int nvar n=%d" % n, oracle.reduce(oracle.RED_NVAR, s, 1.0), wv); wt.check("pairwise int nvar", np.sum((s - np.float32(1)) ** 2, dtype=np.float32), wv)
+        assert oracle.reduce(oracle.RED_NVAR, np.sign(x[:n]), 0.0) == n
+    for kind in ("normal", "scaled"):
+        f = sk.floats(rng, sk.RED_FLOAT_N[-1] + 8, kind); avg = float(np.float32(f.mean()))
+        for n in sk.RED_FLOAT_N:
+            s = f[1:1 + n]
+            wt.check("oracle sum", oracle.reduce(oracle.RED_SUM, s), wt.reduce_sum(s)); wt.check("pairwise sum", np.sum(s, dtype=np.float32), wt.reduce_sum(s))
+            wt.check("reversed sum", seq_reversed(s[:4097], 0), wt.reduce_sum(s[:4097]))
+            wt.check("oracle nvar", oracle.reduce(oracle.RED_NVAR, s, avg), wt.reduce_nvar(s, avg)); wt.check("pairwise nvar", np.sum((s - np.float32(avg)) ** 2, dtype=np.float32), wt.reduce_nvar(s, avg))
+            wt.check("max", oracle.reduce(oracle.RED_MAX, s), wt.reduce_ext(s, "max")); wt.check("min", oracle.reduce(oracle.RED_MIN, s), wt.reduce_ext(s, "min"))
+    # defects.  One element dropped from a 5 M-element sum; a workgroup's 4096-element slice dropped; the same slice counted twice
+    n = 5000003; s = x[:n]; w = wt.reduce_sum(s, exact=True); good = np.float32(f64sum(s))
+    assert passes(good, w)
+    assert not passes(np.float32(f64sum(s) - float(s[n - 1])), w), "dropped element"
+    sl = f64sum(s[5 * 4096:6 * 4096]) or f64sum(s[6 * 4096:7 * 4096])
+    assert sl != 0.0
+    assert not passes(np.float32(f64sum(s) + sl), w), "slice counted twice"
+    assert not passes(np.float32(f64sum(s) - sl), w), "slice dropped"
+    # ... the OLD bars accept the dropped slice (that is why the integer-exact cases exist): 1e-4 sum|x| on the sum, relx with depth on nvar
+    assert old_sum_bar(np.float32(f64sum(s) - sl), s)
+    m = 1 << 20; fx = rng.standard_normal(m).astype(np.float32); a = float(fx.mean())
+    nv = ((fx.astype(np.float64) - a) ** 2).sum(); gone = ((fx[:4096].astype(np.float64) - a) ** 2).sum()
+    assert old_sum_bar(np.float32(f64sum(fx) - f64sum(fx[:4096])), fx) or abs(f64sum(fx[:4096])) < 1e-4 * np.abs(fx).sum()
+    assert relx_old(np.float32(nv - gone), nv, m) >= RTOL                    # (relx alone does see 4096 of 2^20 terms of a positive sum ...)
+    assert relx_old(np.float32(nv - ((fx[:64].astype(np.float64) - a) ** 2).sum()), nv, m) < RTOL      # ... but not a wave's 64)
+    y = np.sign(x[:n]); assert not passes(np.float32(n - 64), wt.reduce_nvar(y, 0.0, exact=True)), "a wave's 64 terms dropped from nvar"
+    assert wt.nan_inf(np.array([1.0, np.nan, np.inf, -np.inf], np.float32)).exact == 3
+
+
+def test_bce_dot_and_bias_gradient_witnesses(oracle, o):
+    P = oracle.P
+    rng = np.random.default_rng(61)
+    N = sk.RED_N[-1] + 8
+    T = rng.integers(0, 2, N).astype(np.float32); O = rng.uniform(0.01, 0.99, N).astype(np.float32); Ts = rng.random(N).astype(np.float32)
+    for n in sk.RED_N:
+        for t in (T, Ts):
+            tn, on = t[:n].copy(), O[:n].copy()
+            r = np.zeros(1, np.float32); o.t4o_bce(P(tn), P(on), n, P(r))
+            w = wt.bce(t[:n], O[:n], wt.ULP_LOG_LIBM)                                  # libm: 2 ulp
+            wt.check("oracle bce n=%d" % n, r[0], w)
+            t32 = (t[:n] * np.log(O[:n] + np.float32(1e-6)) + (np.float32(1) - t[:n]) * np.log(np.float32(1) - O[:n] + np.float32(1e-6))).astype(np.float32)
+            wt.check("pairwise bce n=%d" % n, np.sum(t32, dtype=np.float32), w)
+    n = 257; w = wt.bce(T[:n], O[:n]); term, _, _ = wt.bce_terms(T[:n], O[:n])       # (where the any-order bound of a float sum still sees one term)
+    assert passes(np.float32(term.sum()), w) and not passes(np.float32(term.sum() - term[-1]), w), "BCE: last (tail) term dropped"
+    assert not passes(np.float32(np.sum(T[:n] * np.log(O[:n].astype(np.float64)) + (1 - T[:n]) * np.log(1 - O[:n].astype(np.float64))) * 1.001), w), "BCE 1e-3 off"
+    for K in sk.DOT_K:
+        for C in sk.DOT_C:
+            for ints in (True, False):
+                A = sk.ints(rng, (K, C)) if ints else rng.standard_normal((K, C)).astype(np.float32)
+                B = sk.ints(rng, (K, C)) if ints else rng.standard_normal((K, C)).astype(np.float32)
+                O0 = sk.ints(rng, C) if ints else rng.standard_normal(C).astype(np.float32)
+                for alpha, beta in sk.DOT_AB:
+                    w = wt.dot(A, B, O0, alpha, beta, exact=ints)
+                    r = O0.copy(); o.t4o_dot(P(A), P(B), P(r), alpha, beta, K, C); wt.check("oracle dot K=%d C=%d" % (K, C), r, w)
+                    wt.check("reversed dot", np.float32(alpha) * seq_reversed(A * B, 0) + np.float32(beta) * O0, w)
+                    if beta != 0 and ints:                                  # (integer operands: exact, so the miss shows at every K)
+                        assert not passes(r - np.float32(beta) * O0, w), "dot: beta * O missing"
+                r = np.full(C, np.nan, np.float32); o.t4o_dot(P(A), P(B), P(r), 1.0, 0.0, K, C)
+                assert np.all(np.isnan(r))                      # the reference's 0 * stale-O quirk; the witness (and the kernel) follow BLAS: O unread
+    for E0 in sk.DB_E0:
+        for N_ in sk.DB_N:
+            DY = rng.standard_normal((N_, E0)).astype(np.float32); DB0 = rng.standard_normal(E0).astype(np.float32); w = wt.dlinear_db(DY, DB0)
+            r = DB0.copy(); o.t4o_dlinear_db(P(DY), P(r), N_, E0); wt.check("oracle db", r, w); wt.check("reversed db", seq_reversed(DY, 0) + DB0, w)
+            assert not passes(r - DB0, w) or np.all(np.abs(DB0) <= w.bound()), "db: accumulation dropped"
+            DI = sk.ints(rng, (N_, E0)); r = np.zeros(E0, np.float32); o.t4o_dlinear_db(P(DI), P(r), N_, E0); assert np.array_equal(r, DI.astype(np.float64).sum(0))
+
+
+def _oracle_bn(oracle, o, x, g, b, gy, DW0, DB0, train=1):
+    P = oracle.P; rows, C = x.shape; N, HW = sk.bn_split(rows)
+    y = np.zeros_like(x); xh = np.zeros_like(x); stat = np.zeros(3 * C, np.float32)
+    o.t4o_batchnorm_fwd(P(x), P(y), P(xh), P(g), P(b), P(stat), N, HW, C)
+    st1 = stat.copy(); DX = np.zeros_like(x); DW = DW0.copy(); DB = DB0.copy()
+    o.t4o_batchnorm_bwd(P(g), P(gy), P(xh), P(DX), P(DW), P(DB), P(stat), N, HW, C, train)
+    return y, xh, st1, DX, DW, DB, stat
+
+
+def _bn_numpy(x, chunks=None, rows_used=None, eps_inside=False):
+    """fp32 statistics in numpy's pairwise order (a second honest order), or with a defect"""
+    rows, C = x.shape; xs = x if chunks is None else x[:chunks]
+    n = np.float32(rows if rows_used is None else rows_used)
+    m = np.sum(xs, 0, dtype=np.float32) / n; q = np.sum(xs * xs, 0, dtype=np.float32) / n
+    var = np.maximum(q - m * m, np.float32(0))
+    r = np.float32(1) / np.sqrt(var + np.float32(1e-6)) if eps_inside else np.float32(1) / (np.sqrt(var) + np.float32(1e-6))
+    return np.concatenate([r, m]).astype(np.float32)
+
+
+@pytest.mark.parametrize("rows,C", sk.BN_SHAPES)
+def test_batchnorm_witness_at_every_sweep_shape(oracle, o, rows, C):
+    rng = np.random.default_rng(62 + rows + C)
+    means = sk.BN_MEANS if (rows, C) in sk.BN_MEAN_SHAPES else (0.0,)
+    for mean in means:
+        x = sk.bn_input(rng, rows, C, mean); g = rng.standard_normal(C).astype(np.float32); b = rng.standard_normal(C).astype(np.float32)
+        gy = rng.standard_normal((rows, C)).astype(np.float32); DW0 = rng.standard_normal(C).astype(np.float32); DB0 = rng.standard_normal(C).astype(np.float32)
+        for train in (1, 0):
+            y, xh, st1, DX, DW, DB, st2 = _oracle_bn(oracle, o, x, g, b, gy, DW0, DB0, train)
+            wm, wr = wt.bn_stats(x)
+            wt.check("mean", st1[C:2 * C], wm); wt.check("rstd", st1[:C], wr); wt.check("xhat", xh, wt.bn_xhat(x, st1)); wt.check("y", y, wt.bn_y(xh, g, b))
+            w1, w2, wdw, wdb = wt.bn_bwd_stats(gy, xh, DW0, DB0, train)
+            wt.check("s1", st2[C:2 * C], w1); wt.check("s2", st2[2 * C:], w2); wt.check("dW", DW, wdw); wt.check("dB", DB, wdb)
+            wt.check("dx", DX, wt.bn_dx(g, gy, xh, st2))
+        s = _bn_numpy(x)                                                     # the second honest order
+        wt.check("pairwise mean", s[C:], wm); wt.check("pairwise rstd", s[:C], wr)
+        wt.check("pairwise xhat", (x - s[C:]) * s[:C], wt.bn_xhat(x, np.concatenate([s, np.zeros(C, np.float32)])))
+        xi = sk.ints(rng, (rows, C)); _, _, sti, _, _, _, _ = _oracle_bn(oracle, o, xi, g, b, gy, DW0, DB0)
+        assert np.array_equal(sti[C:2 * C], xi.astype(np.int64).sum(0).astype(np.float32) / np.float32(rows))
+        # defects, on the integer operands (exact in any order, so one row or one chunk shows at every size; a float mean's any-order bound
+        # is wider than one row in thousands): the mean taken over N*HW - 1, the last chunk of the column sums dropped
+        assert not np.array_equal(sti[C:2 * C], xi.astype(np.int64).sum(0).astype(np.float32) / np.float32(rows - 1)), "mean over N*HW - 1"
+        if rows >= sk.BN_CHUNKED_ROWS:
+            nch, rpc = sk.bn_plan(rows); part = xi[:(nch - 1) * rpc].astype(np.int64).sum(0)
+            assert part.any() and not np.array_equal(sti[C:2 * C], part.astype(np.float32) / np.float32(rows)), "last chunk dropped"
+
+
+def test_batchnorm_eps_inside_the_root_and_the_cancellation_term(oracle, o):
+    """eps inside the root shows on a channel of sigma = 1e-3; the bound for 1 / (sigma + eps) grows with (mean / sigma)^2 and the oracle stays
+    inside it: 2.5e-4 of the value at mean 0, 1e-3 at 1 sigma, 5e-2 at 8 sigma - the largest offset of the sweep; at 64 sigma the any-order error of
+    E[x^2] exceeds the variance itself (dvar >= var) and the bound opens to 1 / eps: no fp32 implementation has a variance left to speak of there"""
+    rng = np.random.default_rng(63)
+    rows, C = 4099, 4
+    x = (rng.standard_normal((rows, C)) * 1e-3).astype(np.float32)
+    wm, wr = wt.bn_stats(x)
+    assert passes(_bn_numpy(x)[:C], wr) and not passes(_bn_numpy(x, eps_inside=True)[:C], wr), "eps inside the root"
+    g = np.ones(C, np.float32); last = None
+    for mean in (0.0, 1.0, 8.0, 64.0, 512.0):
+        x = sk.bn_input(rng, rows, C, mean); y, xh, st1, *_ = _oracle_bn(oracle, o, x, g, g, x, g, g)
+        wm, wr = wt.bn_stats(x)
+        wt.check("rstd at mean %g sigma" % mean, st1[:C], wr); wt.check("mean", st1[C:2 * C], wm)
+        rb = float(np.max(wr.bound() / wr.exact))
+        assert (last is None or rb > last) if mean <= 8.0 else rb > 1e5      # the cancellation term at work: the relative bound grows with the offset, then opens
+        assert mean > 8.0 or rb < 0.1; last = rb
+        print("mean %5g sigma: relative bound of 1/(sigma+eps) %.3g, oracle uses %.3g of it" % (mean, rb, wt.ratio(st1[:C], wr)[0]))
+
+
+def test_softmax_and_logsoftmax_at_every_sweep_shape(oracle, o):
+    P = oracle.P
+    rng = np.random.default_rng(64)
+    for C in sk.SOFTMAX_C:
+        for N in sk.SOFTMAX_N:
+            Z = sk.softmax_rows(rng, N, C); y = np.zeros_like(Z); o.t4o_softmax(P(Z), P(y), N, C)
+            wt.check("softmax N=%d C=%d" % (N, C), y, wt.softmax(Z))
+            assert np.all(np.abs(y.astype(np.float64).sum(1) - 1.0) <= C * wt.U)
+    for N, C in sk.LOGSOFTMAX_NC:
+        X = (rng.standard_normal((N, C)) * 2).astype(np.float32); X[0] = -40.0
+        if N > 2:
+            X[2] = 80.0 - np.log(C)
+        e = np.exp(X.astype(np.float64)).astype(np.float32); s = np.zeros(N, np.float32)
+        for c in range(C): s = (s + e[:, c]).astype(np.float32)
+        seq = e - np.log10(np.maximum(s, np.float32(1e-6)))[:, None].astype(np.float32)
+        w = wt.logsoftmax(X, wt.ULP_LOG_LIBM)
+        wt.check("logsoftmax sequential", seq, w)
+        wt.check("logsoftmax pairwise", e - np.log10(np.maximum(np.sum(e, 1, dtype=np.float32), np.float32(1e-6)))[:, None].astype(np.float32), w)
+        if N > 1:
+            assert not passes(e - np.log(np.maximum(s, np.float32(1e-6)))[:, None].astype(np.float32), w), "natural log instead of log10"
+
+
+@pytest.mark.parametrize("kind", ["sgd0", "sgdm", "adam", "adamw"])
+def test_optimizer_witnesses(oracle, o, kind):
+    P = oracle.P
+    rng = np.random.default_rng(65)
+    for n in sk.OPT_N + sk.OPT_CHUNKED_SIZES + sk.OPT_MULTI_SIZES:
+        w0 = rng.standard_normal(n).astype(np.float32); g0 = rng.standard_normal(n).astype(np.float32)
+        m0 = (rng.standard_normal(n) * 0.1).astype(np.float32); v0 = (np.abs(rng.standard_normal(n)) * 0.1).astype(np.float32)
+        W_, G, M, V = w0.copy(), g0.copy(), m0.copy(), v0.copy()
+        if kind == "sgd0": o.t4o_sgd(P(W_), P(G), P(M), 3, 0.01, 0.0, n); ws = wt.sgd(w0, g0, m0, 3, 0.01, 0.0) + (None,)
+        elif kind == "sgdm": o.t4o_sgd(P(W_), P(G), P(M), 2, 0.01, 0.9, n); ws = wt.sgd(w0, g0, m0, 2, 0.01, 0.9) + (None,)
+        elif kind == "adam": o.t4o_adam(P(W_), P(G), P(M), P(V), 1e-3, 0.9, 0.999, n); ws = wt.adam(w0, g0, m0, v0, 1e-3, 0.9, 0.999)
+        else: o.t4o_adamw(P(W_), P(G), P(M), P(V), 1e-3, 0.9, 0.999, 0.01, n); ws = wt.adamw(w0, g0, m0, v0, 1e-3, 0.9, 0.999, 0.01)
+        wt.check("%s w n=%d" % (kind, n), W_, ws[0]); assert not G.any()
+        if ws[1] is not None: wt.check("m", M, ws[1])
+        if ws[2] is not None: wt.check("v", V, ws[2])
+    if kind == "sgd0":
+        assert not passes(w0 - np.float32(0.01) * g0, ws[0]), "Nw scaling missing"
+    if kind in ("adam", "adamw"):
+        b2 = np.float32(0.999); bad = b2 * v0 + (np.float32(1) - b2) * g0
+        assert not passes(bad, ws[2]), "v updated with g instead of g^2"
+        assert not passes(w0 - np.float32(1e-3) * M / np.sqrt(V + np.float32(1e-6)), ws[0]) or kind == "adamw", "eps inside the root"
+
+
+@pytest.mark.parametrize("K", sk.LINALG_K)
+def test_linear_algebra_residual_witnesses(oracle, o, K):
+    P = oracle.P
+    rng = np.random.default_rng(66 + K)
+    eye = np.eye(K, dtype=np.float32); st = ctypes.c_int(0)
+    for kind in sk.LINALG_KINDS:
+        A = sk.matrix(rng, K, kind)
+        a, I = A.copy(), eye.copy(); o.t4o_inverse(P(a), P(I), K, ctypes.byref(st)); assert st.value == 0
+        wt.inverse_check("inverse K=%d %s" % (K, kind), A, I)
+        wt.inverse_check("numpy inverse", A, np.linalg.inv(A.astype(np.float32)).astype(np.float32))       # LAPACK's blocked order
+        a, I2, piv = A.copy(), eye.copy(), np.zeros(K, np.int32); o.t4o_plu(P(a), P(I2), P(piv), K, ctypes.byref(st)); assert st.value == 0
+        wt.plu_check("plu K=%d %s" % (K, kind), A, a, piv)
+        assert np.array_equal(piv, wt.pivot_growth(A)[1]) or kind == "cond1e4"                # float64 picks the same pivots where they are clear
+        wl, sg = wt.logdet(a); ld = np.zeros(1, np.float32); sgo = ctypes.c_int(0); o.t4o_logdet(P(a), K, P(ld), ctypes.byref(sgo))
+        wt.check("logdet", ld, wl); assert sgo.value == sg
+        for get_u in (0, 1):
+            ref = a.copy(); o.t4o_lu_extract(P(ref), get_u, K); wt.equal("lu_extract", ref, wt.lu_extract(a, get_u).exact)
+        a2, I3, piv2 = A.copy(), eye.copy(), np.zeros(K, np.int32); o.t4o_lu_inverse(P(a2), P(I3), P(piv2), K, ctypes.byref(st)); assert st.value == 0
+        wt.inverse_check("lu_inverse K=%d %s" % (K, kind), A, I3, piv2)
+        if K >= 5 and kind == "permuted":
+            # a stale row after a pivot swap: the inverse of A with two rows exchanged back (what a swap that missed I would leave)
+            bad = I3.copy(); bad[:, [0, 1]] = bad[:, [1, 0]]
+            assert not passes(A.astype(np.float64) @ bad, wt.inverse_residual(A, bad, piv2)), "stale row after a swap"
+            badlu = a.copy(); badlu[[1, 2], :1] = badlu[[2, 1], :1]            # L's multipliers not swapped with their rows
+            L, Uu = wt.split_lu(badlu)
+            assert not passes(L @ Uu, wt.W(wt.plu_residual(A, piv), np.abs(L) @ np.abs(Uu), K, wt.C_SUM)), "stale multipliers after a swap"
+    for kind, want in (("singular_last", K), ("singular_first", 1)):
+        A = sk.matrix(rng, K, kind); a, I = A.copy(), eye.copy(); o.t4o_inverse(P(a), P(I), K, ctypes.byref(st)); assert st.value == want
+
+
+@pytest.mark.parametrize("N,H1,W1,C1,C0", sk.DCONV_SHAPES)
+def test_transposed_conv_witness(oracle, o, N, H1, W1, C1, C0):
+    P = oracle.P
+    K, S, Pd = 4, 2, 1
+    H0, W0 = wt.dconv_out(H1), wt.dconv_out(W1)
+    rng = np.random.default_rng(67 + N * 100 + C0)
+    I = rng.standard_normal((N, H1, W1, C1)).astype(np.float32); F = (rng.standard_normal((C1, K, K, C0)) * 0.2).astype(np.float32)
+    B = rng.standard_normal(C0).astype(np.float32); G = rng.standard_normal((N, H0, W0, C0)).astype(np.float32)
+    O = np.zeros((N, H0, W0, C0), np.float32)
+    assert o.t4o_dconv2d_fwd(P(I), P(O), P(F), P(B), N, H1, W1, C1, H0, W0, C0, K, S, Pd) == 0
+    w = wt.dconv_fwd(I, F, B, H0, W0); wt.check("dconv fwd", O, w)
+    d = O.copy(); d[..., 0] -= B[0]; assert not passes(d, w), "bias"
+    DX = np.zeros_like(I); DF = np.full_like(F, 0.25); DB = np.full_like(B, -0.5)
+    for rep in range(2):
+        DF0, DB0 = DF.copy(), DB.copy()
+        assert o.t4o_dconv2d_bwd(P(I), P(G), P(DX), P(F), P(DF), P(DB), N, H1, W1, C1, H0, W0, C0, K, S, Pd, 1) == 0
+        wdx, wdf, wdb = wt.dconv_bwd(I, G, F, DF0, DB0)
+        wt.check("dconv dX", DX, wdx); wt.check("dconv dF", DF, wdf); wt.check("dconv dB", DB, wdb)
+    assert not passes(DF - DF0, wdf), "dF not accumulated"
+    assert not passes(np.ascontiguousarray(DF[:, ::-1, ::-1, :]), wdf), "taps flipped"
