@@ -207,6 +207,28 @@ int t4k_lu_inverse(float *A, float *I, int *piv_dev, int K, int *status_dev, t4k
 int t4k_lu_extract(float *LU, int get_u, int K, t4k_stream_t s);
 /* k_logdet :952: *logdet_dev = sum ln|U[j,j]|, *sign_dev = prod sign(U[j,j]) */
 int t4k_logdet(const float *LU, int K, float *logdet_dev, int *sign_dev, t4k_stream_t s);
+/* The same over a BATCH of `batch` row-major K x K matrices, entry b at A + b*K*K (likewise X, Pm; piv_dev + b*K; status_dev[b]; det_dev[b]).
+ * No reference definition for the batch: the reference's words take one rank-2 matrix (tenvm.cpp:134-216).  Exactly ONE kernel launch
+ * per call whatever `batch` is, no allocation, no synchronisation; batch == 0 is T4K_OK and launches nothing.  Pivot rule and status as
+ * the per-matrix entries: largest |a|, lowest row on a tie, |pivot| < 1e-6 = singular -> status_dev[b] = z + 1 (else 0).  A singular
+ * entry does not stop the others; what it leaves in its outputs is unspecified, except det_dev[b] = 0.
+ * Unlike the per-matrix entries, X and Pm are pure OUTPUTS: the kernel writes the identity itself.
+ * K <= 0, batch < 0 or a NULL pointer: T4K_ERR_ARG; K > 1024: T4K_ERR_UNSUPPORTED. */
+/* Tensor::inverse tensor.cu:344-369 (k_find_pivot/k_swap_rows/k_diag/k_elim :742-836); no reference definition for the batch.
+ * X[b] = inverse(A[b]) by Gauss-Jordan.  A is scratch: K <= 140 leaves it untouched, above that it holds the eliminated rows (column z
+ * of it is not maintained) - treat it as undefined after the call. */
+int t4k_inverse_batched(float *A, float *X, int K, int batch, int *status_dev, t4k_stream_t s);
+/* Tensor::plu tensor.cu:371-398 (k_lu_col :854, k_pivot :887); no reference definition for the batch.
+ * A[b] -> packed L\U, piv_dev[b*K + z] = pivot row of column z (-1 at the singular column), Pm (may be NULL) = the permutation matrix P. */
+int t4k_plu_batched(float *A, float *Pm, int *piv_dev, int K, int batch, int *status_dev, t4k_stream_t s);
+/* Tensor::lu_inverse tensor.cu:400-417 (k_fsub :904, k_bsub :920); no reference definition for the batch.
+ * A[b] -> packed L\U, X[b] = inverse(A[b]) by substitution on the columns of P. */
+int t4k_lu_inverse_batched(float *A, float *X, int *piv_dev, int K, int batch, int *status_dev, t4k_stream_t s);
+/* Tensor::lu tensor.cu:419-429 (k_lu :936); no reference definition for the batch. */
+int t4k_lu_extract_batched(float *LU, int get_u, int K, int batch, t4k_stream_t s);
+/* Tensor::det tensor.cu:431-456 (k_logdet :952); no reference definition for the batch.  A[b] -> packed L\U,
+ * det_dev[b] = expf(sum ln|u_jj|) * (parity of the swaps) * (product of the signs of u_jj), finished on the device. */
+int t4k_det_batched(float *A, int *piv_dev, int K, int batch, float *det_dev, int *status_dev, t4k_stream_t s);
 
 /* ------------------------------------------------------- RNG (util.cu:28-70) */
 /* Counter-based Philox4x32-10 replaces the reference's 1024 cuRAND XORWOW states

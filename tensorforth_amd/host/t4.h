@@ -152,6 +152,12 @@ struct Tensor : Obj {
     static Tensor &lu_inverse(Tensor &A, Tensor &I);
     static Tensor &plu(Tensor &A, Tensor &I, int *piv_dev);
     static Tensor &lu(Tensor &LU, bool get_u);
+    // the same over a batch T4[N,K,K,1] (beyond the reference): one launch and one status read-back per call
+    bool is_batch() const { return rank == 4 && shape[0] == shape[1] && shape[2] == 1; }
+    static Tensor &inverse_b(Tensor &A, Tensor &X, bool use_lu);   // A: scratch (Gauss-Jordan) or L\U; X: pure output
+    static Tensor &plu_b(Tensor &A, Tensor &Pm);                   // A -> L\U, Pm = permutation matrices (pure output)
+    static Tensor &lu_b(Tensor &LU, bool get_u);
+    static Tensor &det_b(Tensor &A, Tensor &D);                    // A -> L\U, D = vector [N] of determinants (0 for a singular entry)
 };
 
 // ---------------------------------------------------------------- object store

@@ -367,5 +367,90 @@ DU Tensor::det() {                                      // tensor.cu:431-456
     DU d = expf(ld) * sign * dsign;
     return SCALAR(d);
 }
+// The linear-algebra words over a batch T4[N,K,K,1] (beyond the reference, whose words take one rank-2 matrix: tenvm.cpp:134-216):
+// entry n is treated as the rank-2 word treats its matrix.  One t4k_*_batched launch and ONE read-back of an int[N] status array per
+// call; a singular entry prints the rank-2 word's line with " entry n" appended and does not stop the others.  The five symbols are
+// referenced weakly: over a C-ABI without them (the CPU oracle) the same methods loop over the entries with the per-matrix calls,
+// the host filling the identity those expect.
+#pragma weak t4k_inverse_batched
+#pragma weak t4k_plu_batched
+#pragma weak t4k_lu_inverse_batched
+#pragma weak t4k_lu_extract_batched
+#pragma weak t4k_det_batched
+static void batch_status(const int *st_dev, int N, bool gauss_jordan, std::vector<int> *keep = nullptr) {
+    std::vector<int> st(N);
+    t4k_memcpy_d2h(st.data(), st_dev, sizeof(int) * N, stream()); t4k_sync(stream());
+    for (int n = 0; n < N; n++) {
+        if (!st[n]) continue;
+        if (gauss_jordan) hprintf("  tensor#inverse: singular matrix at column %d entry %d\n", st[n] - 1, n);
+        else              hprintf("  tensor#plu: singular at column %d entry %d\n", st[n] - 1, n);
+    }
+    if (keep) keep->swap(st);
+}
+Tensor &Tensor::inverse_b(Tensor &A, Tensor &X, bool use_lu) {
+    const int K = A.W(), N = A.N();
+    if (use_lu) hprintf("  tensor#lu_inverse [%d,%d]\n", K, K); else hprintf("  tensor#inverse [%d,%d]\n", K, K);
+    Tensor &ws = Store::get().tensor((uint64_t)N * (K + 1));             // int piv[N][K], status[N]
+    int *piv = (int *)ws.data, *st = piv + (size_t)N * K;
+    if (use_lu ? t4k_lu_inverse_batched != nullptr : t4k_inverse_batched != nullptr) {
+        if (use_lu) chk(t4k_lu_inverse_batched(A.data, X.data, piv, K, N, st, stream()), "lu_inverse_batched");
+        else        chk(t4k_inverse_batched(A.data, X.data, K, N, st, stream()), "inverse_batched");
+    } else {
+        X.identity();
+        for (int n = 0; n < N; n++) {
+            if (use_lu) chk(t4k_lu_inverse(A.slice(n), X.slice(n), piv + (size_t)n * K, K, st + n, stream()), "lu_inverse");
+            else        chk(t4k_inverse(A.slice(n), X.slice(n), K, st + n, stream()), "inverse");
+        }
+    }
+    batch_status(st, N, !use_lu);
+    Store::get().free(ws);
+    return X;
+}
+Tensor &Tensor::plu_b(Tensor &A, Tensor &Pm) {
+    const int K = A.W(), N = A.N();
+    Tensor &ws = Store::get().tensor((uint64_t)N * (K + 1));
+    int *piv = (int *)ws.data, *st = piv + (size_t)N * K;
+    if (t4k_plu_batched) chk(t4k_plu_batched(A.data, Pm.data, piv, K, N, st, stream()), "plu_batched");
+    else {
+        Pm.identity();
+        for (int n = 0; n < N; n++) chk(t4k_plu(A.slice(n), Pm.slice(n), piv + (size_t)n * K, K, st + n, stream()), "plu");
+    }
+    batch_status(st, N, false);
+    Store::get().free(ws);
+    return Pm;
+}
+Tensor &Tensor::lu_b(Tensor &LU, bool get_u) {
+    const int K = LU.W(), N = LU.N();
+    if (t4k_lu_extract_batched) chk(t4k_lu_extract_batched(LU.data, get_u, K, N, stream()), "lu_batched");
+    else for (int n = 0; n < N; n++) chk(t4k_lu_extract(LU.slice(n), get_u, K, stream()), "lu");
+    return LU;
+}
+Tensor &Tensor::det_b(Tensor &A, Tensor &D) {             // per entry the formula of Tensor::det; 0 for an entry found singular
+    const int K = A.W(), N = A.N();
+    Tensor &ws = Store::get().tensor((uint64_t)N * (K + 3));             // int piv[N][K], status[N]; fallback: float logdet[N], int sign[N]
+    int *piv = (int *)ws.data, *st = piv + (size_t)N * K;
+    if (t4k_det_batched) {
+        chk(t4k_det_batched(A.data, piv, K, N, D.data, st, stream()), "det_batched");
+        batch_status(st, N, false);
+    } else {
+        float *ld = (float *)(st + N); int *sg = (int *)(ld + N);
+        for (int n = 0; n < N; n++) {
+            chk(t4k_plu(A.slice(n), nullptr, piv + (size_t)n * K, K, st + n, stream()), "plu");
+            t4k_logdet(A.slice(n), K, ld + n, sg + n, stream());
+        }
+        std::vector<int> hst, hp((size_t)N * K), hs(N); std::vector<float> hl(N), d(N);
+        batch_status(st, N, false, &hst);
+        t4k_memcpy_d2h(hp.data(), piv, sizeof(int) * hp.size(), stream());
+        t4k_memcpy_d2h(hl.data(), ld, sizeof(float) * N, stream());
+        t4k_memcpy_d2h(hs.data(), sg, sizeof(int) * N, stream()); t4k_sync(stream());
+        for (int n = 0; n < N; n++) {
+            int cnt = 0; for (int i = 0; i < K; i++) if (hp[(size_t)n * K + i] != i) cnt++;
+            d[n] = hst[n] ? 0.0f : expf(hl[n]) * ((cnt % 2 == 0) ? 1 : -1) * hs[n];
+        }
+        D.from_host(d.data(), N);
+    }
+    Store::get().free(ws);
+    return D;
+}
 
 } // namespace t4

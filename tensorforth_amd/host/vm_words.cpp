@@ -54,7 +54,21 @@ static Tensor &tinv(Tensor &A, bool use_lu) {
 }
 void VM::blas1(int op) {
     Tensor &A = TTOS();
-    if (!TOS1T() || A.rank != 2) { pstr("tensor2?"); return; }
+    const bool batch = TOS1T() && A.is_batch() && op != B_XPOS;   // beyond the reference: T4[N,K,K,1] = N matrices, each treated as the rank-2 word treats its one
+    if (!TOS1T() || (A.rank != 2 && !batch)) { pstr("tensor2?"); return; }
+    if (batch) {
+        const uint32_t N = A.N(), K = A.H();
+        Tensor &T = st().copy(A);
+        switch (op) {
+        case B_INV: case B_LUINV: { Tensor &X = st().tensor(N, K, K, 1); Tensor::inverse_b(T, X, op == B_LUINV); PUSH(X); st().free(T); } break;
+        case B_PLU:  { Tensor &Pm = st().tensor(N, K, K, 1); Tensor::plu_b(T, Pm); PUSH(Pm); PUSH(T); } break;
+        case B_TRIU: Tensor::lu_b(T, true);  PUSH(T); break;
+        case B_TRIL: Tensor::lu_b(T, false); PUSH(T); break;
+        case B_DET:  { Tensor &D = st().tensor((uint64_t)N); Tensor::det_b(T, D); PUSH(D); st().free(T); } break;   // a VECTOR of N determinants
+        default: st().free(T);
+        }
+        return;
+    }
     Tensor &T = st().copy(A);
     bool tx = true;
     switch (op) {
@@ -99,6 +113,16 @@ void VM::blas2(int op, bool keep) {
         PUSH(*C);
     } break;
     case B_DIV: {                                        // C = A @ inverse(B)
+        if (A.rank == 4 || B.rank == 4) {                // beyond the reference: B a batch T4[N,K,K,1], A T4[N,M,K,1] or a matrix [M,K] used for every entry
+            if (!B.is_batch() || A.rank == 1 || A.C() != 1 || A.W() != B.H() || (A.rank == 4 && A.N() != B.N())) { pstr("batch dim?"); return; }
+            const uint32_t N = B.N(), K = B.H(), M = A.H();
+            Tensor &T = st().copy(B);                    // factored on a copy: B stays intact (the rank-2 branch below clobbers it, as the reference does)
+            Tensor &I = st().tensor(N, K, K, 1); Tensor::inverse_b(T, I, true);
+            Tensor &O = st().tensor(N, M, K, 1); Tensor::bmm(A, I, O, M, K, K);
+            st().free(I); st().free(T);
+            PUSH(O);
+            break;
+        }
         if (B.H() != B.W() || A.W() != B.H()) return;
         Tensor &I = tinv(B, true);
         Tensor &O = st().tensor(A.H(), B.W());
@@ -107,6 +131,16 @@ void VM::blas2(int op, bool keep) {
     } break;
     case B_SOLV: {                                       // ( B A -- B A X ) solve B = A X   (_solv: note A,B flipped)
         Tensor &Am = B, &Bv = A;
+        if (Am.rank == 4 || Bv.rank == 4) {              // beyond the reference: A a batch T4[N,K,K,1]; B T4[N,K,P,1], or a matrix [K,P] / vector [K] used for every entry
+            if (!Am.is_batch() || Bv.C() != 1 || Bv.H() != Am.H() || (Bv.rank == 4 && Bv.N() != Am.N())) { pstr("batch dim?"); return; }
+            const uint32_t N = Am.N(), K = Am.H(), P = Bv.W();       // a vector is [K,1]
+            Tensor &T = st().copy(Am);
+            Tensor &I = st().tensor(N, K, K, 1); Tensor::inverse_b(T, I, true);
+            Tensor &O = st().tensor(N, K, P, 1); Tensor::bmm(I, Bv, O, K, K, P);   // X[n] = luinv(A[n]) @ B[n]: the rank-2 word's own definition
+            st().free(I); st().free(T);
+            PUSH(O);
+            break;
+        }
         if (Bv.rank != 1 || Am.H() != Am.W() || Am.W() != Bv.H()) { PUSH(Bv); return; }
         Tensor &T = st().copy(Am);
         Tensor &I = tinv(T, true);
