@@ -84,7 +84,7 @@ int t4k_init(int device) {
     T4K_HIP(hipStreamSynchronize(g.stream));            // ... and complete before any stream (a caller's own, t4k_set_default_stream) can launch
     if (!g.spin_err) {                                  // error word of the bounded inter-workgroup waits: pinned host memory the kernels can write
         T4K_HIP(hipHostMalloc((void **)&g.spin_err, 64, hipHostMallocMapped)); *g.spin_err = 0;
-        gemm_set_spin_err(g.spin_err); linsmall_set_spin_err(g.spin_err);
+        gemm_set_spin_err(g.spin_err); linear_set_spin_err(g.spin_err); linsmall_set_spin_err(g.spin_err);
     }
     g.device = device;
     g.ready  = true;

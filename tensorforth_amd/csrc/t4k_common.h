@@ -118,6 +118,7 @@ inline float *ws_for(const void *s) {            // accepts a t4k_stream_t or an
 #define T4K_SPIN_WAIT(cond_not_met, code) do { int _it = 0; while (cond_not_met) { __builtin_amdgcn_s_sleep(1); \
         if (++_it > T4K_SPIN_MAX) { if (g_spin_err_dev) __hip_atomic_store(g_spin_err_dev, (code), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); break; } } } while (0)
 void gemm_set_spin_err(int *p);          // gemm.hip
+void linear_set_spin_err(int *p);        // linear.hip
 void linsmall_set_spin_err(int *p);      // linear_small.hip
 inline bool gates_ok();                  // may a launcher pick a kernel whose workgroups wait for each other (arrival gates, tickets, band exchange)?
 int  spin_check();                       // runtime.hip: T4K_OK, or T4K_ERR_HIP when a wait timed out since the last check (clears the word)

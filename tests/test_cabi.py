@@ -58,6 +58,7 @@ def test_release_library_has_no_lab_switches():
     """The conv-stack ablation hooks (T4K_STACK_LAB_*: kernels that skip work, wrong results) and the stamp pointer hook exist only in a
     LAB build (make -C tensorforth_amd/csrc LAB=1 -> libt4hip_lab.so); the shipped library does not even contain their names, so no
     environment variable can switch them on."""
+    import re
     blob = open(os.path.join(ROOT, "tensorforth_amd", "libt4hip.so"), "rb").read()
     for name in (b"T4K_STACK_LAB_NOSTORE", b"T4K_STACK_LAB_NOW1", b"T4K_STACK_LAB_NOXCHG", b"T4K_STACK_PROF_PTR"):
         assert name + b"\0" not in blob, name               # as a C string of its own (what getenv would be handed); comments of the embedded source may mention it
@@ -66,8 +67,10 @@ def test_release_library_has_no_lab_switches():
     # round 6: the engine-selection / tuning knobs (T4K_LAB_ENV, csrc/t4k_common.h) are compile-time constants of the release build
     for name in (b"T4K_GEMM_S32", b"T4K_GEMM_DUAL", b"T4K_GEMM_PLAIN128", b"T4K_CONVBIG8", b"T4K_CONV_THIN", b"T4K_STACK_SPLIT", b"T4K_LINTHIN", b"T4K_HB_LAB", b"T4K_GEMM_VARIANT"):
         assert name + b"\0" not in blob, name
+    # the head-backward kernel's ablation word is compile-time too: the release kernel's last parameter is its HeadBwd block, no `int lab` behind it
+    hb = set(re.findall(rb"(?<![0-9A-Za-z_])_ZN12_GLOBAL__N_114k_head_bwd_l32E[0-9A-Za-z_]*", blob))
+    assert hb and all(n.endswith(b"HeadBwdE") for n in hb), hb
     # ... and the release libraries read a short documented list: every T4K_* / T4_* name they hold as a C string
-    import re
     names = set(re.findall(rb"\0(T4K?_[A-Z0-9_]{3,})\0", blob + open(os.path.join(ROOT, "tensorforth_amd", "libten4.so"), "rb").read()))
     names = {n.decode() for n in names if not n.startswith((b"T4K_ERR", b"T4K_L_", b"T4K_OK", b"T4K_OP"))}
     documented = {"T4K_RCCL_PATH", "T4K_XCHG_TIMEOUT_MS", "T4K_CACHE_DIR", "T4K_STACK_JIT", "T4K_STACK_DISK_CACHE",

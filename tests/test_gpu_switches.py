@@ -1,7 +1,7 @@
 """GPU: the non-default dispatch paths of the GEMM / linear kernels cannot rot, and the gated one-launch kernels survive a busy device.
 
 * the integer-exact products run on the default dispatch, with the gated kernels switched off, and (LAB library, opt-in) under every
-  `T4K_GEMM_*` / head LAB switch (csrc/gemm.hip, linear_small.hip), each in a process of its own: plain / transposed / alpha-beta GEMMs incl. ragged and sliver shapes, and the linear layer both ways (forward with bias,
+  `T4K_GEMM_*` / head LAB switch (csrc/gemm_types.h GemmLab: gemm.hip, linear.hip; linear_small.hip), each in a process of its own: plain / transposed / alpha-beta GEMMs incl. ragged and sliver shapes, and the linear layer both ways (forward with bias,
   backward dW += dY^T X, dB += column sums, dX = dY W written IN PLACE over X - the arrival-gate path) - entries in {-2..2} keep every
   fp32 sum exact, so whatever kernel the switch selects must reproduce numpy's integer result bit for bit;
 * the same set runs while a bandwidth-hogging elementwise kernel chain occupies the device on another stream (the situation of a

@@ -12,7 +12,7 @@
 //   dW|dB    dW += dY^T X, dB += .. A = dY [K,M] m-contiguous,  B = X  [K,N] n-contiguous + a virtual all-ones column N
 // Split-K partials meet in the workspace: every wave stores its 32x32 block with agent-scope (write-through) stores,
 // takes a ticket, and the LAST arriver of a tile sums the S blocks in slice order (deterministic) and runs the
-// epilogue - no second launch, no fence (a release fence per workgroup costs an L2 write-back, see gemm.hip).
+// epilogue - no second launch, no fence (a release fence per workgroup costs an L2 write-back, see gemm_tile.h).
 // Reference: Tensor::linear / gemm3 tensor.cu:79-87,161-180; _flinear forward.cu:157-198; _blinear backprop.cu:193-254.
 #include "t4k_common.h"
 
