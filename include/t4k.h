@@ -192,6 +192,20 @@ int t4k_gemm_f64acc(const float *A, const float *B, float *O, float alpha, float
  * One launch per call, no allocation, no synchronisation (legal under capture); beta == 0 never reads O.  fp32 MFMA. */
 int t4k_gemm_batched(const float *A, const float *B, float *O, float alpha, float beta, int tA, int tB,
                      int M, int N, int K, int C, int cA, int cB, int batch, long sA, long sB, long sO, t4k_stream_t s);
+/* NumPy broadcasting for the arithmetic words (tenvm.cpp:277-287 names NumPy as the meaning of the tensor operators); no reference
+ * definition: k_tt_op :222 takes two flat tensors of one size and Tensor::ten_op tensor.cu:28-53 loops one launch per sample.
+ *   O[n,h,w,c] = A[n*sA[0] + h*sA[1] + w*sA[2] + c*sA[3]]  op  B[n*sB[0] + h*sB[1] + w*sB[2] + c*sB[3]],  op in {ADD,SUB,MUL,DIV}
+ *   O is dense NHWC of extents dim = {N,H,W,C}; strides are in elements, a stride of 0 broadcasts that axis (the stride of an axis of
+ *   extent 1 is not looked at).  Every element goes through k_tt_op's own expression: bit-identical to t4k_tt_op on operands expanded
+ *   to the full shape.  O may alias an operand all of whose strides are the dense ones; it must not overlap a broadcast operand.
+ * Exactly one launch per call, no allocation, no synchronisation (legal under capture); an empty dim is T4K_OK without a launch.
+ * NULL, a negative extent or a negative stride: T4K_ERR_ARG; an unknown op: T4K_ERR_UNSUPPORTED. */
+int t4k_tt_op_bcast(int op, const float *A, const float *B, float *O,
+                    const int dim[4], const long sA[4], const long sB[4], t4k_stream_t s);
+/* k_transpose :150 over a batch; no reference definition for the batch (the reference's `transpose` takes one rank-2 matrix).
+ *   dst[b] = transpose(src[b]) for b in [0, batch): each entry [H,W,C] -> [W,H,C] exactly as t4k_transpose, entries H*W*C apart.
+ * Bit-exact, one launch per call; batch == 0 is T4K_OK without a launch; H, W, C <= 0, batch < 0 or NULL: T4K_ERR_ARG. */
+int t4k_transpose_batched(const float *src, float *dst, int H, int W, int C, int batch, t4k_stream_t s);
 
 /* ------------------------------------------------ linear algebra (t4math.cu) */
 /* Tensor::inverse tensor.cu:344-369 (k_find_pivot/k_swap_rows/k_diag/k_elim :742-836):

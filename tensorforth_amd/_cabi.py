@@ -19,7 +19,7 @@ def _ctype(decl):
     decl = decl.strip()
     if decl == "void" or decl == "":
         return None
-    if "*" in decl:
+    if "*" in decl or "[" in decl:                       # `const int dim[4]` is a pointer parameter
         if decl.replace(" ", "").startswith("constchar*"):
             return ctypes.c_char_p
         return ctypes.c_void_p
@@ -53,7 +53,7 @@ def parse_header(path, prefix):
             for a in args.split(","):
                 a = a.strip()
                 # strip trailing parameter name for scalars ("int M" -> "int")
-                if "*" not in a:
+                if "*" not in a and "[" not in a:
                     parts = a.split()
                     if len(parts) > 1 and parts[-1] not in _SCALARS and parts[-1] not in _HANDLES:
                         a = " ".join(parts[:-1])

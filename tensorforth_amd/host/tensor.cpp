@@ -258,6 +258,8 @@ Tensor &Tensor::ten_op(int op, Tensor &A, DU v, Tensor &O) {     // tensor.cu:16
     chk(t4k_ts_op(op, A.data, v, O.data, (long)A.numel, stream()), "ten_op");
     return O;
 }
+#pragma weak t4k_tt_op_bcast
+#pragma weak t4k_transpose_batched
 Tensor &Tensor::ten_op(int op, Tensor &A, Tensor &B, Tensor &O) {   // tensor.cu:28-53 (N broadcast)
     const uint32_t Na = A.N(), Nb = B.N(), N = std::max(Na, Nb);
     if (A.HWC() != B.HWC() || (Na == 1 ? B.numel : A.numel) != O.numel) {
@@ -265,9 +267,59 @@ Tensor &Tensor::ten_op(int op, Tensor &A, Tensor &B, Tensor &O) {   // tensor.cu
         return O;
     }
     if ((Na == 1 || Nb == 1) && Na != Nb) {
+        const long hwc = (long)A.HWC();
+        if (t4k_tt_op_bcast && hwc <= 0x7fffffffL) {     // one launch for the whole batch (the same values as the loop below)
+            const int dim[4] = { (int)N, 1, 1, (int)hwc };
+            const long sA[4] = { Na == 1 ? 0 : hwc, 0, 0, 1 }, sB[4] = { Nb == 1 ? 0 : hwc, 0, 0, 1 };
+            chk(t4k_tt_op_bcast(op, A.data, B.data, O.data, dim, sA, sB, stream()), "ten_op");
+            return O;
+        }
         for (uint32_t n = 0; n < N; n++)
             t4k_tt_op(op, A.slice(Na == 1 ? 0 : n), B.slice(Nb == 1 ? 0 : n), O.slice(n), (long)A.HWC(), stream());
     } else chk(t4k_tt_op(op, A.data, B.data, O.data, (long)A.numel, stream()), "ten_op");
+    return O;
+}
+// NumPy broadcasting for + - * / beyond ten_op (tenvm.cpp:277-287 gives NumPy as the meaning of the tensor operators):
+// O[n,h,w,c] = A[..] op B[..], an operand's axis of extent 1 serving every index of O's.  O has the axis-wise maximum shape (the caller
+// checked that the extents agree or are 1).  One t4k_tt_op_bcast launch; the symbol is referenced weakly, and over a C-ABI without it
+// (the CPU oracle) each broadcast operand is first expanded into a temporary of O's shape, innermost axis first - t4k_broadcast_rows
+// where nothing lies inside the axis, copies of the inner block otherwise - and one t4k_tt_op does the arithmetic.
+static void nhwc_of(Tensor &T, long e[4]) { e[0] = T.N(); e[1] = T.H(); e[2] = T.W(); e[3] = T.C(); }
+static Tensor *expand_to(Tensor &X, const long dim[4]) {  // nullptr: X has O's shape already
+    long cur[4]; nhwc_of(X, cur);
+    Tensor *have = nullptr;
+    float *src = X.data;
+    for (int k = 3; k >= 0; k--) {
+        if (cur[k] == dim[k]) continue;                  // cur[k] == 1 < dim[k]
+        long outer = 1, inner = 1;
+        for (int i = 0; i < k; i++) outer *= cur[i];
+        for (int i = k + 1; i < 4; i++) inner *= cur[i];
+        const long D = dim[k];
+        Tensor &T = Store::get().tensor((uint64_t)(outer * D * inner));
+        if (inner == 1) chk(t4k_broadcast_rows(src, T.data, (int)outer, (int)D, stream()), "broadcast_rows");
+        else for (long o = 0; o < outer; o++) for (long d = 0; d < D; d++)
+            chk(t4k_copy(src + o * inner, T.data + (o * D + d) * inner, inner, stream()), "copy");
+        if (have) Store::get().free(*have);
+        have = &T; src = T.data; cur[k] = D;
+    }
+    return have;
+}
+Tensor &Tensor::ten_bcast(int op, Tensor &A, Tensor &B, Tensor &O) {
+    long ea[4], eb[4], eo[4]; nhwc_of(A, ea); nhwc_of(B, eb); nhwc_of(O, eo);
+    if (t4k_tt_op_bcast) {
+        int dim[4]; long sA[4], sB[4], da = 1, db = 1;
+        for (int i = 3; i >= 0; i--) {
+            dim[i] = (int)eo[i];
+            sA[i] = ea[i] == 1 ? 0 : da; da *= ea[i];
+            sB[i] = eb[i] == 1 ? 0 : db; db *= eb[i];
+        }
+        chk(t4k_tt_op_bcast(op, A.data, B.data, O.data, dim, sA, sB, stream()), "ten_bcast");
+        return O;
+    }
+    Tensor *Ta = expand_to(A, eo), *Tb = expand_to(B, eo);
+    chk(t4k_tt_op(op, Ta ? Ta->data : A.data, Tb ? Tb->data : B.data, O.data, (long)O.numel, stream()), "ten_bcast");
+    if (Ta) Store::get().free(*Ta);
+    if (Tb) Store::get().free(*Tb);
     return O;
 }
 Tensor &Tensor::mm(Tensor &A, Tensor &B, Tensor &O, bool inc, bool tA, bool tB) {   // Tensor::mm/gemm3 tensor.cu:73-77,161-180
@@ -317,6 +369,10 @@ Tensor &Tensor::gemm(int variant, Tensor &A, Tensor &B, Tensor &O, DU alpha, DU 
     return O;
 }
 Tensor &Tensor::transpose(Tensor &A, Tensor &T) {
+    if (A.rank == 4 && t4k_transpose_batched) {          // a batch T4[N,H,W,C] -> T4[N,W,H,C] in one launch (beyond the reference)
+        chk(t4k_transpose_batched(A.data, T.data, A.H(), A.W(), A.C(), A.N(), stream()), "transpose_batched");
+        return T;
+    }
     for (uint32_t n = 0; n < A.N(); n++) chk(t4k_transpose(A.slice(n), T.slice(n), A.H(), A.W(), A.C(), stream()), "transpose");
     return T;
 }

@@ -35,6 +35,19 @@ void VM::xop2(int op, bool keep) {
     } break;
     case 3: {                                            // tensor-tensor
         Tensor &A = TNOS(), &B = TTOS();
+        if (A.HWC() != B.HWC()) {                        // beyond the reference (NumPy broadcasting, tenvm.cpp:277-287): every axis of (N,H,W,C) equal or 1 on one side; a vector [K] is the column (1,K,1,1)
+            const uint32_t a[4] = { A.N(), A.H(), A.W(), A.C() }, b[4] = { B.N(), B.H(), B.W(), B.C() };
+            bool fits = true;
+            for (int i = 0; i < 4; i++) fits = fits && (a[i] == b[i] || a[i] == 1 || b[i] == 1);
+            if (fits) {
+                const uint32_t n = std::max(a[0], b[0]), h = std::max(a[1], b[1]), w = std::max(a[2], b[2]), c = std::max(a[3], b[3]);
+                Tensor &O = (A.rank == 4 || B.rank == 4) ? st().tensor(n, h, w, c) : (A.rank == 1 && B.rank == 1) ? st().tensor((uint64_t)h) : st().tensor(h, w);
+                Tensor::ten_bcast(op, A, B, O);
+                if (!keep) { DROP(POP()); DROP(POP()); }
+                PUSH(O);
+                break;
+            }
+        }
         if ((A.N() == 1 || B.N() == 1) && A.HWC() != B.HWC()) { pstr("} dim?\n"); break; }
         Tensor &O = st().copy(A.N() == 1 ? B : A);
         Tensor::ten_op(op, A, B, O);
@@ -55,6 +68,12 @@ static Tensor &tinv(Tensor &A, bool use_lu) {
 void VM::blas1(int op) {
     Tensor &A = TTOS();
     const bool batch = TOS1T() && A.is_batch() && op != B_XPOS;   // beyond the reference: T4[N,K,K,1] = N matrices, each treated as the rank-2 word treats its one
+    if (TOS1T() && A.rank == 4 && op == B_XPOS) {        // beyond the reference: T4[N,H,W,C] -> T4[N,W,H,C], every entry and channel in one launch
+        Tensor &T = st().tensor(A.N(), A.W(), A.H(), A.C());
+        Tensor::transpose(A, T);
+        PUSH(T);
+        return;
+    }
     if (!TOS1T() || (A.rank != 2 && !batch)) { pstr("tensor2?"); return; }
     if (batch) {
         const uint32_t N = A.N(), K = A.H();
