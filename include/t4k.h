@@ -153,6 +153,18 @@ int t4k_graph_destroy(t4k_graph_t g);
 /* k_sum :23, k_nvar :48, k_max/d__max :85-131 via Tensor::sum/std/norm/max/min
  * (tensor.cu:224-277).  Result is written (not accumulated) to *out_dev. */
 int t4k_reduce(int red_op, const float *src, long n, float avg, float *out_dev, t4k_stream_t s);
+/* The same reductions along any subset of the axes, NumPy keepdims=True; no reference definition: k_sum :23, k_nvar :48 and
+ * k_max :85-131 fold a whole tensor into one scalar, and the reference's only axis reductions are parts of nn layers (k_dlinear_db
+ * nmath.cu:274, k_batchnorm_1 nmath.cu:177, the softmax row sum forward.cu:222-243).
+ *   src is dense NHWC of extents dim = {N,H,W,C}; mask adds N = 8, H = 4, W = 2, C = 1 for the axes folded; dst is dense NHWC with
+ *   every masked axis at extent 1.  red_op as t4k_reduce (SUM: sum x, NVAR: sum (x - c)^2, MAX, MIN); center is read for NVAR only,
+ *   laid out as dst: the value c subtracted for that output (NULL: 0).  A masked axis of extent 1 has no effect.
+ * One launch, or two when few outputs stand behind long reductions (partials in the stream's workspace, folded in index order);
+ * no allocation, no synchronisation, no floating-point atomics: the same bits on every run.
+ * NULL src / dst / dim, an extent < 1, a mask outside 1..15, an unknown red_op, more than 2^40 elements or dst overlapping src:
+ * T4K_ERR_ARG. */
+int t4k_reduce_axes(int red_op, const float *src, float *dst, const int dim[4], int mask,
+                    const float *center, t4k_stream_t s);
 /* k_nan_inf :278 / Tensor::has_nan tensor.cu:326-333: count of NaN/Inf -> *cnt_dev (int) */
 int t4k_nan_inf(const float *src, long n, int *cnt_dev, t4k_stream_t s);
 /* k_copy :134 */

@@ -322,6 +322,59 @@ Tensor &Tensor::ten_bcast(int op, Tensor &A, Tensor &B, Tensor &O) {
     if (Tb) Store::get().free(*Tb);
     return O;
 }
+// Axis reductions (beyond the reference, whose sum / avg / std / norm fold a whole tensor: tensor.cu:224-250): T is viewed
+// as (N,H,W,C) - a matrix (1,H,W,1), a vector the column (1,K,1,1) - and R has T's rank with every masked axis at extent 1.  One
+// t4k_reduce_axes launch (two for few outputs behind long reductions) plus the element-wise sqrt / division of the word: a count
+// that no extent changes, and no scalar is read back.  The symbol is referenced weakly: over a C-ABI without it (the CPU oracle)
+// every output element gathers what it folds into a temporary with t4k_copy and takes one t4k_reduce written straight to its place.
+#pragma weak t4k_reduce_axes
+static void reduce_into(int red_op, Tensor &T, int mask, Tensor *center, Tensor &R) {
+    long e[4]; nhwc_of(T, e);
+    if (t4k_reduce_axes) {
+        const int dim[4] = { (int)e[0], (int)e[1], (int)e[2], (int)e[3] };
+        chk(t4k_reduce_axes(red_op, T.data, R.data, dim, mask, center ? center->data : nullptr, stream()), "reduce_axes");
+        return;
+    }
+    bool red[4]; long str[4], d = 1, cnt = 1;
+    for (int i = 3; i >= 0; i--) { red[i] = (mask & (8 >> i)) != 0; str[i] = d; d *= e[i]; if (red[i]) cnt *= e[i]; }
+    int tail = 4; long run = 1;                          // the trailing reduced axes are one contiguous run
+    while (tail > 0 && (red[tail - 1] || e[tail - 1] == 1)) { run *= e[tail - 1]; tail--; }
+    Tensor &tmp = Store::get().tensor((uint64_t)cnt);
+    long k[4], r[4], o = 0;                              // k: the output's index, r: the reduced axes' (both 0 where the other walks)
+    const long K[4] = { red[0] ? 1 : e[0], red[1] ? 1 : e[1], red[2] ? 1 : e[2], red[3] ? 1 : e[3] };
+    for (k[0] = 0; k[0] < K[0]; k[0]++) for (k[1] = 0; k[1] < K[1]; k[1]++) for (k[2] = 0; k[2] < K[2]; k[2]++) for (k[3] = 0; k[3] < K[3]; k[3]++, o++) {
+        long Rn[4], at = 0;
+        for (int i = 0; i < 4; i++) Rn[i] = (i < tail && red[i]) ? e[i] : 1;
+        for (r[0] = 0; r[0] < Rn[0]; r[0]++) for (r[1] = 0; r[1] < Rn[1]; r[1]++) for (r[2] = 0; r[2] < Rn[2]; r[2]++) for (r[3] = 0; r[3] < Rn[3]; r[3]++, at += run) {
+            long off = 0;
+            for (int i = 0; i < 4; i++) off += (k[i] + r[i]) * str[i];
+            chk(t4k_copy(T.data + off, tmp.data + at, run, stream()), "copy");
+        }
+        chk(t4k_reduce(red_op, tmp.data, cnt, center ? center->get((uint64_t)o) : 0.0f, R.data + o, stream()), "reduce");
+    }
+    Store::get().free(tmp);
+}
+Tensor &Tensor::reduce_axes(int word, Tensor &T, int mask) {
+    long e[4], cnt = 1; nhwc_of(T, e);
+    for (int i = 0; i < 4; i++) if (mask & (8 >> i)) { cnt *= e[i]; e[i] = 1; }
+    auto result = [&]() -> Tensor & {
+        return T.rank == 4 ? Store::get().tensor((uint32_t)e[0], (uint32_t)e[1], (uint32_t)e[2], (uint32_t)e[3])
+             : T.rank == 2 ? Store::get().tensor((uint32_t)e[1], (uint32_t)e[2]) : Store::get().tensor((uint64_t)e[1]);
+    };
+    Tensor &R = result();
+    switch (word) {
+    case AX_SUM:  reduce_into(T4K_RED_SUM, T, mask, nullptr, R); break;
+    case AX_AVG:  reduce_into(T4K_RED_SUM, T, mask, nullptr, R); ten_op(T4K_DIV, R, (DU)cnt, R); break;            // sum / cnt: one fp32 division, as Tensor::avg
+    case AX_NORM: reduce_into(T4K_RED_NVAR, T, mask, nullptr, R); R.map(T4K_SQRT); break;
+    case AX_STD: {                                       // sqrt(sum (x - avg)^2) / cnt, avg the fp32 tensor `avg` returns (Tensor::std, tensor.cu:242-250)
+        Tensor &A = reduce_axes(AX_AVG, T, mask);
+        reduce_into(T4K_RED_NVAR, T, mask, &A, R);
+        R.map(T4K_SQRT); ten_op(T4K_DIV, R, (DU)cnt, R);
+        Store::get().free(A);
+    } break;
+    }
+    return R;
+}
 Tensor &Tensor::mm(Tensor &A, Tensor &B, Tensor &O, bool inc, bool tA, bool tB) {   // Tensor::mm/gemm3 tensor.cu:73-77,161-180
     const uint32_t H = tA ? A.W() : A.H(), W = tB ? B.H() : B.W();
     const uint32_t Ka = tA ? A.H() : A.W(), Kb = tB ? B.W() : B.H();

@@ -208,10 +208,19 @@ void VM::init_tensor() {
     CODE("rand",  [rnd] { rnd(T4K_UNIFORM); });
     CODE("randn", [rnd] { rnd(T4K_NORMAL); });
     CODE("normalize", [this] { DU std = POP(), avg = POP(); if (TOS1T()) TTOS().normalize(std, avg); });   // args swapped as in tenvm.cpp:513-515
-    CODE("sum",  [this] { if (TOS1T()) PUSH(TTOS().sum()); });
-    CODE("avg",  [this] { if (TOS1T()) PUSH(TTOS().avg()); });
-    CODE("std",  [this] { if (TOS1T()) PUSH(TTOS().std()); });
-    CODE("norm", [this] { if (TOS1T()) PUSH(TTOS().norm()); });
+    // beyond the reference ( T m -- T R ): a scalar axis mask on top of a tensor folds the masked axes, N = 8, H = 4, W = 2, C = 1;
+    // any other cell under the scalar leaves the words the no-ops they are there (tenvm.cpp:516-519 look at the top of the stack alone)
+    auto axes = [this](const char *name, int word) {
+        if (IS_OBJ(tos_) || SP() < 1 || !is_t(SS(-1))) return;
+        const DU m = POP();
+        const int mask = (m >= 1.0f && m <= 15.0f) ? (int)m : 0;
+        if (!mask || (DU)mask != m) { pstr(std::string(name) + ": axes 1..15?\n"); return; }
+        PUSH(Tensor::reduce_axes(word, TTOS(), mask));
+    };
+    CODE("sum",  [this, axes] { if (TOS1T()) PUSH(TTOS().sum());  else axes("sum", Tensor::AX_SUM); });
+    CODE("avg",  [this, axes] { if (TOS1T()) PUSH(TTOS().avg());  else axes("avg", Tensor::AX_AVG); });
+    CODE("std",  [this, axes] { if (TOS1T()) PUSH(TTOS().std());  else axes("std", Tensor::AX_STD); });
+    CODE("norm", [this, axes] { if (TOS1T()) PUSH(TTOS().norm()); else axes("norm", Tensor::AX_NORM); });
     CODE("{", [this] { if (TOS1T() && ten_lvl_ > 0) ++ten_lvl_; });
     CODE("}", [this, lit_flush] { if (TOS1T() && ten_lvl_ > 0) { if (--ten_lvl_ == 0) lit_flush(); } });
     CODE("slice", [this] {
