@@ -12,9 +12,7 @@
 // are decomposed into (n, y, x) once.  NHWC makes every operand row a contiguous 128-byte run: all global loads are
 // coalesced 16-byte loads, out-of-image taps load nothing and stage zeros.
 // Arithmetic restates k_conv2d / k_dconv2d (src/nn/nmath.tcu:34-104, 211-338) incl. the flipped-filter dX.
-#include "t4k_common.h"
-
-using namespace t4k;
+#include "conv_types.h"
 
 namespace {
 
@@ -934,167 +932,152 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(BKP ==
     }
 }
 
+// ---- admission tests of the 8-wave LDS-DMA kernels
+// k_convbig8: stride 1, "same" padding, whole 64-channel stages, a full pixel tile; byte offsets of the buffer loads are 32-bit
+bool big8_shape(int K, int S, int P, const float *X, const float *F, long npix, int Hx, int Wx, int Cin, int Hy, int Wy, int Cout, int C0f) {
+    return S == 1 && P == K / 2 && (K == 1 || K == 3 || K == 5) && Cin % 64 == 0 && Cout % 4 == 0 && Hx == Hy && Wx == Wy &&
+           aligned16(X) && aligned16(F) && npix >= 128 && npix * Cin < (1L << 29) && (long)(Cin > Cout ? Cin : Cout) * K * K * C0f < (1L << 29);
+}
+// k_convbig_dfw: stride 1, same size, whole 128s of input channels (T4K_CONVBIG_DFW >= 3: 32 or 64 too), whole 64s of output channels
+bool dfw_shape(int K, int S, int P, const float *I, const float *DO, long npix, int H1, int W1, int C1, int H0, int W0, int C0) {
+    return S == 1 && P == K / 2 && (K == 1 || K == 3 || K == 5) && H1 == H0 && W1 == W0 && (C1 % 128 == 0 || (conv_lab().dfw >= 3 && (C1 == 32 || C1 == 64))) && C0 % 64 == 0 &&
+           npix * C1 < (1L << 29) && npix * C0 < (1L << 29) && aligned16(I) && aligned16(DO);
+}
+// k_convbig_df8: row offsets are ints in 16-byte units; needs the page of zeros
+bool df8_shape(long npix, int W1, int C1, int C0) { return npix * (C0 > C1 ? C0 : C1) / 4 + (long)4 * W1 * C1 < (1L << 31) && st().d_zero; }
+// 128-wide tiles only when they still give every CU `per_cu` workgroups, 64-wide otherwise (CIFAR conv3 dX: 128 -> 256 workgroups) and for 64 output channels
+bool wide_tiles(int tiles_m, int Cout, int per_cu) { return Cout > 64 && (long)tiles_m * ((Cout + 127) / 128) >= (long)st().cu_count * per_cu; }
+
 } // namespace
 
 namespace t4k {
 
 bool conv_big_ok(int Cin, int Cout) { return Cin >= 32 && (Cin % 32) == 0 && Cout >= 16 && (Cout % 4) == 0; }
 
-// forward (BWD = false) or dX (BWD = true); X/Cin are the gathered tensor, Y/Cout the produced one
 template <bool BWD>
 void launch_conv_big(int K, int S, int P, hipStream_t hs, const float *X, float *Y, float *Y2, const float *F, const float *B,
                      int N, int Hx, int Wx, int Cin, int Hy, int Wy, int Cout, int C0f, float *bn_part, size_t bn_part_floats, int *bn_chunks) {
+    const ConvLab &lab = conv_lab();
     if (bn_chunks) *bn_chunks = 0;
     const long npix = (long)N * Hy * Wy;
-    {   // stride 1, "same" padding, whole 64-channel stages: the 8-wave LDS-DMA kernel (k_convbig8), every such layer since round 5 (round 4 kept the 9-stage
-        // layers on k_convbig: with buffer-addressed DMA, the branch-free epilogue and two workgroups per CU on 32-channel stages they gain most -
-        // 64 -> 128 @ 16x16 forward 96.2 -> 83.9 us, 64 -> 64 @ 32x32 221 -> 194.5 us, dX 185 -> 168 us); T4K_CONVBIG8=0: off
-        static const int on = T4K_LAB_ENV("T4K_CONVBIG8", 1);
-        const bool shape = S == 1 && P == K / 2 && (K == 1 || K == 3 || K == 5) && Cin % 64 == 0 && Cout % 4 == 0 && Hx == Hy && Wx == Wy &&
-                           aligned16(X) && aligned16(F) && npix >= 128 && npix * Cin < (1L << 29) && (long)(Cin > Cout ? Cin : Cout) * K * K * C0f < (1L << 29);   // byte offsets of the buffer loads are 32-bit
-        if (on && shape) {
-            const int tiles_m = (int)((npix + 127) / 128);
-            // 128-wide tiles when they still give every CU a workgroup, 64-wide otherwise (CIFAR conv3 dX: 128 -> 256 workgroups) and for 64 output channels
-            const bool wide = Cout > 64 && (long)tiles_m * ((Cout + 127) / 128) >= (long)st().cu_count;
-            const int BN = wide ? 128 : 64;
-            float *rider = nullptr;                         // batch-norm statistics from the epilogue: forward, every tile interior, the slab fits
-            if (!BWD && bn_part && bn_chunks && npix % 128 == 0 && Cout % BN == 0 && (size_t)tiles_m * 2 * 2 * Cout <= bn_part_floats) { rider = bn_part; *bn_chunks = tiles_m * 2; }
-            Cb8 q = { X, F, B, Y, Y2, rider, N, Hy, Wy, Cin, Cout, C0f, (Cout + BN - 1) / BN };
-            const dim3 g8((unsigned)(tiles_m * q.tiles_n)), b8(512);
-            // grids of two or more tiles per CU: 32-channel stages, half the LDS, at most 128 registers - two workgroups share a CU and one's stage barrier
-            // (and prologue, and epilogue) runs under the other's MFMAs (as k_gemm_plain128<.., 32>)
-            static const int bk32 = T4K_LAB_ENV("T4K_CONVBIG8_BK32", 1);
-            const bool two = bk32 && (bk32 >= 2 || (long)tiles_m * q.tiles_n >= 2L * st().cu_count);
-            const size_t lds8 = std::max(sizeof(float) * 2 * (128 + BN) * (two ? 32 : 64), sizeof(float) * 4 * 2 * (BN / 64) * 16 * 64);   // stages | the k-groups' meeting
-#define CB8_(k, pd, ntw, nt, bk) do { static bool a1 = false; if (!a1) { (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_convbig8<k, pd, BWD, ntw, nt, bk>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds8); a1 = true; } \
-                                      T4K_LAUNCH((k_convbig8<k, pd, BWD, ntw, nt, bk>), g8, b8, lds8, hs, q); } while (0)
-#define CB8n(k, pd, ntw) do { if (two) { if (nts) CB8_(k, pd, ntw, true, 32); else CB8_(k, pd, ntw, false, 32); } else { if (nts) CB8_(k, pd, ntw, true, 64); else CB8_(k, pd, ntw, false, 64); } } while (0)
-#define CB8(k, pd) do { if (wide) CB8n(k, pd, 2); else CB8n(k, pd, 1); } while (0)
-            static const int nts = T4K_LAB_ENV("T4K_CONVBIG8_NT", 0);
-            if (K == 1) CB8(1, 0); else if (K == 3) CB8(3, 1); else CB8(5, 2);
-#undef CB8n
-#undef CB8_
-#undef CB8
-            return;
-        }
+    const int tiles_m = (int)((npix + 127) / 128);
+    // the 8-wave LDS-DMA kernel (k_convbig8), every such layer since round 5 (round 4 kept the 9-stage layers on k_convbig: with buffer-addressed DMA,
+    // the branch-free epilogue and two workgroups per CU on 32-channel stages they gain most - 64 -> 128 @ 16x16 forward 96.2 -> 83.9 us,
+    // 64 -> 64 @ 32x32 221 -> 194.5 us, dX 185 -> 168 us)
+    if (lab.big8 && big8_shape(K, S, P, X, F, npix, Hx, Wx, Cin, Hy, Wy, Cout, C0f)) {
+        const bool wide = wide_tiles(tiles_m, Cout, 1);
+        const int BN = wide ? 128 : 64;
+        float *rider = nullptr;                         // batch-norm statistics from the epilogue: forward, every tile interior, the slab fits
+        if (!BWD && bn_part && bn_chunks && npix % 128 == 0 && Cout % BN == 0 && (size_t)tiles_m * 2 * 2 * Cout <= bn_part_floats) { rider = bn_part; *bn_chunks = tiles_m * 2; }
+        Cb8 q = { X, F, B, Y, Y2, rider, N, Hy, Wy, Cin, Cout, C0f, (Cout + BN - 1) / BN };
+        const dim3 g8((unsigned)(tiles_m * q.tiles_n)), b8(512);
+        // grids of two or more tiles per CU: 32-channel stages, half the LDS, at most 128 registers - two workgroups share a CU and one's stage barrier
+        // (and prologue, and epilogue) runs under the other's MFMAs (as k_gemm_plain128<.., 32>)
+        const bool two = lab.big8_bk32 && (lab.big8_bk32 >= 2 || (long)tiles_m * q.tiles_n >= 2L * st().cu_count);
+        const size_t lds8 = std::max(sizeof(float) * 2 * (128 + BN) * (two ? 32 : 64), sizeof(float) * 4 * 2 * (BN / 64) * 16 * 64);   // stages | the k-groups' meeting
+        with_geometry(K, S, P, [&](auto geo) {
+            using Ge = decltype(geo);
+            if constexpr (Ge::K != 4)                   // big8_shape(): K 1, 3 or 5
+                with_flags([&](auto wd, auto nt, auto tw) {
+                    launch_lds<k_convbig8<Ge::K, Ge::P, BWD, (wd.value ? 2 : 1), nt.value, (tw.value ? 32 : 64)>>(g8, b8, lds8, hs, q);
+                }, wide, lab.big8_nt != 0, two);
+        });
+        return;
     }
     CbP p = { X, F, B, Y, Y2, N, Hx, Wx, Cin, Hy, Wy, Cout, C0f, 0 };
-    const int tiles_m = (int)((npix + 127) / 128);
-    static const int wmul = T4K_LAB_ENV("T4K_CONVBIG_WIDE_MUL", 1);
-    const bool wide = Cout > 64 && (long)tiles_m * ((Cout + 127) / 128) >= (long)st().cu_count * wmul;   // 128-wide tiles only when they still give every CU a workgroup (CIFAR conv3 dX: 128 -> 256 workgroups)
+    const bool wide = wide_tiles(tiles_m, Cout, lab.wide_mul);
     const int BN = wide ? 128 : 64;
     p.tiles_n = (Cout + BN - 1) / BN;
     const dim3 g((unsigned)(tiles_m * p.tiles_n)), b(256);
     const size_t lds = sizeof(float) * 2 * (128 + BN) * BK;
-#define CB(k, s, pd) do { if (wide) { static bool a1 = false; if (!a1) { (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_convbig<k, s, pd, BWD, 128>), hipFuncAttributeMaxDynamicSharedMemorySize, 65536); a1 = true; } \
-                                       T4K_LAUNCH((k_convbig<k, s, pd, BWD, 128>), g, b, lds, hs, p); } \
-                          else T4K_LAUNCH((k_convbig<k, s, pd, BWD, 64>), g, b, lds, hs, p); } while (0)
-    switch ((K << 8) | (S << 4) | P) {
-    case 0x110: CB(1, 1, 0); break;
-    case 0x311: CB(3, 1, 1); break;
-    case 0x421: CB(4, 2, 1); break;
-    case 0x512: CB(5, 1, 2); break;
-    }
-#undef CB
+    with_geometry(K, S, P, [&](auto geo) {
+        using Ge = decltype(geo);
+        if (wide) launch_lds<k_convbig<Ge::K, Ge::S, Ge::P, BWD, 128>>(g, b, lds, hs, p);
+        else      launch_lds<k_convbig<Ge::K, Ge::S, Ge::P, BWD, 64>>(g, b, lds, hs, p);
+    });
 }
 template void launch_conv_big<false>(int, int, int, hipStream_t, const float *, float *, float *, const float *, const float *, int, int, int, int, int, int, int, int, float *, size_t, int *);
 template void launch_conv_big<true>(int, int, int, hipStream_t, const float *, float *, float *, const float *, const float *, int, int, int, int, int, int, int, int, float *, size_t, int *);
 
-// dF partial slabs; returns the number of slices written (0: workspace too small).  Layout [slice][C1*K*K][C0].
 int launch_conv_big_df(int K, int S, int P, hipStream_t hs, const float *I, const float *DO, float *part, size_t part_floats,
                        int N, int H1, int W1, int C1, int H0, int W0, int C0) {
+    const ConvLab &lab = conv_lab();
     const long npix = (long)N * H0 * W0;
     const int ci_tiles = (C1 + 63) / 64, co_tiles = (C0 + 63) / 64, KK = K * K;
-    const int tiles = KK * ci_tiles * co_tiles;
-    static const int wpc = std::max(1, T4K_LAB_ENV("T4K_DF_WGS_PER_CU", 3));
-    long nslice = ((long)wpc * st().cu_count + tiles - 1) / tiles; if (nslice < 1) nslice = 1;      // workgroups per CU in total
-    long pps = (npix + nslice - 1) / nslice; pps = (pps + BK - 1) / BK * BK; if (pps < 8 * BK) pps = 8 * BK;
-    nslice = (npix + pps - 1) / pps;
-    // Workgroups go to XCD (linear block id % 8) and the grid is slice-major: with a slice count that is a multiple of 8 every
-    // tap / channel tile of one pixel slice lands on the SAME XCD, so the K*K-fold re-read of I and dO is served by that XCD's
-    // L2 instead of crossing the fabric once per tap (a trailing slice may be empty: it writes a zero slab)
-    static const int x8 = T4K_LAB_ENV("T4K_DF_XCD", 1);
-    if (x8 && nslice >= 8) { nslice = (nslice + 7) / 8 * 8; pps = (npix + nslice - 1) / nslice; pps = (pps + BK - 1) / BK * BK; }
-    {   // stride 1, same size, whole 128s of input channels, whole 64s of output channels: 128-row tiles (k_convbig_dfw; 128 -> 256 @ 8x8, N = 256: 92.0 -> 88.4 us).
-        // Two or four taps of 64 / 32 channels per tile work too (T4K_CONVBIG_DFW=3) but lose: 9 taps fill 10 / 12 tap slots and the fold reads 51 slices
-        // (64 -> 128 @ 16x16: 96.3 + 24 us of fold against 89 + 12)
-        static const int dfw = T4K_LAB_ENV("T4K_CONVBIG_DFW", 1);
-        const bool shape = S == 1 && P == K / 2 && (K == 1 || K == 3 || K == 5) && H1 == H0 && W1 == W0 && (C1 % 128 == 0 || (dfw >= 3 && (C1 == 32 || C1 == 64))) && C0 % 64 == 0 &&
-                           npix * C1 < (1L << 29) && npix * C0 < (1L << 29) && aligned16(I) && aligned16(DO);
-        if (dfw && shape) {
-            const int ciw = C1 >= 128 ? 128 : C1, tpt = 128 / ciw, kks = (KK + tpt - 1) / tpt;
-            const int ntw = C0 % 128 == 0 ? 2 : 1, bn = 64 * ntw;
-            const int cit = (C1 + ciw - 1) / ciw, cot = C0 / bn, ctl = cit * cot, tilesw = kks * ctl;
-            // 1: 64-pixel stages, one workgroup per CU; 2: 32-pixel stages, two per CU (twice the slices, twice the slab bytes)
-            const int bkp = (dfw == 2 || dfw == 4) ? 32 : 64;
-            const long slots = (long)st().cu_count * (bkp == 32 ? 2 : 1);
-            long ns = slots / tilesw; if (ns < 1) ns = 1;
-            long pp = (npix + ns - 1) / ns; pp = (pp + bkp - 1) / bkp * bkp; if (pp < 4 * bkp) pp = 4 * bkp;
-            ns = (npix + pp - 1) / pp;
-            if ((size_t)ns * C1 * KK * C0 <= part_floats) {
-                Cdw q = { I, DO, part, H0, W0, C1, C0, (int)pp, (int)ns, cit, ctl, kks, npix };
-                const long T = ns * ctl * kks;
-                const dim3 gw((unsigned)(8 * ((T + 7) / 8))), bw(512);
-                const size_t ldsw = std::max(sizeof(float) * 2 * (128 + bn) * bkp, sizeof(float) * 4 * 2 * ntw * 16 * 64);
-#define DFW_(k, pd, cw, nt, bk) do { static bool a1 = false; if (!a1) { (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_convbig_dfw<k, pd, cw, nt, bk>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsw); a1 = true; } \
-                                     T4K_LAUNCH((k_convbig_dfw<k, pd, cw, nt, bk>), gw, bw, ldsw, hs, q); } while (0)
-#define DFWb(k, pd, cw, nt) do { if (bkp == 32) DFW_(k, pd, cw, nt, 32); else DFW_(k, pd, cw, nt, 64); } while (0)
-#define DFWn(k, pd, cw) do { if (ntw == 2) DFWb(k, pd, cw, 2); else DFWb(k, pd, cw, 1); } while (0)
-#define DFW(k, pd) do { if (ciw == 128) DFWn(k, pd, 128); else if (ciw == 64) DFWn(k, pd, 64); else DFWn(k, pd, 32); } while (0)
-                if (K == 1) DFW(1, 0); else if (K == 3) DFW(3, 1); else DFW(5, 2);
-#undef DFW
-#undef DFWn
-#undef DFWb
-#undef DFW_
-                return (int)ns;
-            }
+    // 128-row tiles (k_convbig_dfw; 128 -> 256 @ 8x8, N = 256: 92.0 -> 88.4 us)
+    if (lab.dfw && dfw_shape(K, S, P, I, DO, npix, H1, W1, C1, H0, W0, C0)) {
+        const int ciw = C1 >= 128 ? 128 : C1, tpt = 128 / ciw, kks = (KK + tpt - 1) / tpt;
+        const int ntw = C0 % 128 == 0 ? 2 : 1, bn = 64 * ntw;
+        const int cit = (C1 + ciw - 1) / ciw, cot = C0 / bn, ctl = cit * cot, tilesw = kks * ctl;
+        // 1: 64-pixel stages, one workgroup per CU; 2: 32-pixel stages, two per CU (twice the slices, twice the slab bytes)
+        const int bkp = (lab.dfw == 2 || lab.dfw == 4) ? 32 : 64;
+        const long slots = (long)st().cu_count * (bkp == 32 ? 2 : 1);
+        long ns = slots / tilesw; if (ns < 1) ns = 1;
+        long pp = (npix + ns - 1) / ns; pp = (pp + bkp - 1) / bkp * bkp; if (pp < 4 * bkp) pp = 4 * bkp;
+        ns = (npix + pp - 1) / pp;
+        if ((size_t)ns * C1 * KK * C0 <= part_floats) {
+            Cdw q = { I, DO, part, H0, W0, C1, C0, (int)pp, (int)ns, cit, ctl, kks, npix };
+            const long T = ns * ctl * kks;
+            const dim3 gw((unsigned)(8 * ((T + 7) / 8))), bw(512);
+            const size_t ldsw = std::max(sizeof(float) * 2 * (128 + bn) * bkp, sizeof(float) * 4 * 2 * ntw * 16 * 64);
+            with_geometry(K, S, P, [&](auto geo) {
+                using Ge = decltype(geo);
+                if constexpr (Ge::K != 4)               // dfw_shape(): K 1, 3 or 5
+                    pick<128, 64, 32>(ciw, [&](auto cw) { pick<2, 1>(ntw, [&](auto nt) { pick<32, 64>(bkp, [&](auto bk) {
+                        launch_lds<k_convbig_dfw<Ge::K, Ge::P, cw.value, nt.value, bk.value>>(gw, bw, ldsw, hs, q);
+                    }); }); });
+            });
+            return (int)ns;
         }
     }
-    static const int df8 = T4K_LAB_ENV("T4K_CONVBIG_DF8", 64);     // 0: the 4-wave register-staged kernel; 64 / 128: pixels per stage of the 8-wave LDS-DMA kernel
-    if (df8 && npix * (C0 > C1 ? C0 : C1) / 4 + (long)4 * W1 * C1 < (1L << 31) && st().d_zero) {      // row offsets are ints in 16-byte units
+    if (lab.df8 && df8_shape(npix, W1, C1, C0)) {
         // 64-pixel stages: 64 KiB of LDS, two workgroups per CU (one's barrier under the other's MFMAs) -> up to 2 x CUs workgroups at once, all resident
-        const int bkp = df8 >= 128 ? 128 : df8 >= 64 ? 64 : 32;
-        static const int wpc8 = T4K_LAB_ENV("T4K_CONVBIG_DF8_WPC", 0);
-        static const int nstb = T4K_LAB_ENV("T4K_CONVBIG_DF8_NST", (bkp == 32 ? 4 : 2));
-        const int lds_kb = (bkp == 128 ? 2 : bkp == 64 ? (nstb == 3 ? 3 : 2) : (nstb >= 5 ? 5 : nstb == 4 ? 4 : 3)) * 128 * bkp * 4 / 1024;
-        const long slots = (long)st().cu_count * (wpc8 > 0 ? wpc8 : std::max(1, std::min(160 / lds_kb, 3)));
-        static const int tp2on = T4K_LAB_ENV("T4K_CONVBIG_DF8_TP2", 1);
-        const int tp2 = (tp2on && C1 == 32) ? 1 : 0;         // two taps per 64-row tile
+        const int bkp = lab.df8 >= 128 ? 128 : lab.df8 >= 64 ? 64 : 32;
+        // the (pixels per stage, stage buffers) pairs that exist as kernels
+        const int nst = bkp == 128 ? 2 : bkp == 64 ? (lab.df8_nst == 3 ? 3 : 2) : (lab.df8_nst >= 5 ? 5 : lab.df8_nst == 4 ? 4 : 3);
+        const int lds_kb = nst * 128 * bkp * 4 / 1024;
+        const long slots = (long)st().cu_count * (lab.df8_wpc > 0 ? lab.df8_wpc : std::max(1, std::min(160 / lds_kb, 3)));
+        const int tp2 = (lab.df8_tp2 && C1 == 32) ? 1 : 0;   // two taps per 64-row tile
         const int kks = tp2 ? (KK + 1) / 2 : KK;
         const int tiles8 = kks * ci_tiles * co_tiles;
         long ns = slots / tiles8; if (ns < 1) ns = 1;
         long pp = (npix + ns - 1) / ns; pp = (pp + bkp - 1) / bkp * bkp; if (pp < 4 * bkp) pp = 4 * bkp;
         ns = (npix + pp - 1) / pp;
         if ((size_t)ns * C1 * KK * C0 > part_floats) return 0;
-        static const int dbg8 = T4K_LAB_ENV("T4K_CONVBIG_DF8_DBG", 0);
         const int ctl = ci_tiles * co_tiles;
-        Cd8 q = { I, DO, st().d_zero, part, N, H1, W1, C1, H0, W0, C0, (int)pp, ci_tiles, npix, dbg8, (int)ns, ctl, tp2 };
+        Cd8 q = { I, DO, st().d_zero, part, N, H1, W1, C1, H0, W0, C0, (int)pp, ci_tiles, npix, lab.df8_dbg, (int)ns, ctl, tp2 };
         const long groups = ns * ctl;
         const dim3 g8((unsigned)(8 * kks * ((groups + 7) / 8))), b8(512);
-#define DF8_(k, s, pd, bk, ns_) do { static bool a1 = false; const int lb = ns_ * 128 * bk * 4; \
-            if (!a1) { (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_convbig_df8<k, s, pd, bk, ns_>), hipFuncAttributeMaxDynamicSharedMemorySize, lb); a1 = true; } \
-            T4K_LAUNCH((k_convbig_df8<k, s, pd, bk, ns_>), g8, b8, lb, hs, q); } while (0)
-#define DF8(k, s, pd) do { if (bkp == 128) DF8_(k, s, pd, 128, 2); else if (bkp == 64 && nstb == 3) DF8_(k, s, pd, 64, 3); else if (bkp == 64) DF8_(k, s, pd, 64, 2); \
-                           else if (nstb >= 5) DF8_(k, s, pd, 32, 5); else if (nstb == 4) DF8_(k, s, pd, 32, 4); else DF8_(k, s, pd, 32, 3); } while (0)
-        switch ((K << 8) | (S << 4) | P) {
-        case 0x110: DF8(1, 1, 0); break;
-        case 0x311: DF8(3, 1, 1); break;
-        case 0x421: DF8(4, 2, 1); break;
-        case 0x512: DF8(5, 1, 2); break;
-        }
-#undef DF8
-#undef DF8_
+        with_geometry(K, S, P, [&](auto geo) {
+            using Ge = decltype(geo);
+            auto go = [&](auto bk, auto ns_) { launch_lds<k_convbig_df8<Ge::K, Ge::S, Ge::P, bk.value, ns_.value>>(g8, b8, (size_t)ns_.value * 128 * bk.value * 4, hs, q); };
+            switch (bkp * 8 + nst) {                    // a list, not a cross product: six kernels per geometry
+            case 128 * 8 + 2: go(int_c<128>{}, int_c<2>{}); break;
+            case 64 * 8 + 3:  go(int_c<64>{}, int_c<3>{}); break;
+            case 64 * 8 + 2:  go(int_c<64>{}, int_c<2>{}); break;
+            case 32 * 8 + 5:  go(int_c<32>{}, int_c<5>{}); break;
+            case 32 * 8 + 4:  go(int_c<32>{}, int_c<4>{}); break;
+            case 32 * 8 + 3:  go(int_c<32>{}, int_c<3>{}); break;
+            }
+        });
         return (int)ns;
     }
+    // the 4-wave register-staged kernel (k_convbig_df): workgroups per CU in total -> slices
+    const int tiles = KK * ci_tiles * co_tiles;
+    long nslice = ((long)lab.df_wpc * st().cu_count + tiles - 1) / tiles; if (nslice < 1) nslice = 1;
+    long pps = (npix + nslice - 1) / nslice; pps = (pps + BK - 1) / BK * BK; if (pps < 8 * BK) pps = 8 * BK;
+    nslice = (npix + pps - 1) / pps;
+    // Workgroups go to XCD (linear block id % 8) and the grid is slice-major: with a slice count that is a multiple of 8 every
+    // tap / channel tile of one pixel slice lands on the SAME XCD, so the K*K-fold re-read of I and dO is served by that XCD's
+    // L2 instead of crossing the fabric once per tap (a trailing slice may be empty: it writes a zero slab)
+    if (lab.df_xcd && nslice >= 8) { nslice = (nslice + 7) / 8 * 8; pps = (npix + nslice - 1) / nslice; pps = (pps + BK - 1) / BK * BK; }
     if ((size_t)nslice * C1 * KK * C0 > part_floats) return 0;
     CdP p = { I, DO, part, N, H1, W1, C1, H0, W0, C0, (int)pps, ci_tiles };
     const dim3 g((unsigned)nslice, (unsigned)(KK * ci_tiles), (unsigned)co_tiles), b(256);
-    switch ((K << 8) | (S << 4) | P) {
-    case 0x110: T4K_LAUNCH((k_convbig_df<1, 1, 0>), g, b, 0, hs, p); break;
-    case 0x311: T4K_LAUNCH((k_convbig_df<3, 1, 1>), g, b, 0, hs, p); break;
-    case 0x421: T4K_LAUNCH((k_convbig_df<4, 2, 1>), g, b, 0, hs, p); break;
-    case 0x512: T4K_LAUNCH((k_convbig_df<5, 1, 2>), g, b, 0, hs, p); break;
-    }
+    with_geometry(K, S, P, [&](auto geo) {
+        using Ge = decltype(geo);
+        T4K_LAUNCH((k_convbig_df<Ge::K, Ge::S, Ge::P>), g, b, 0, hs, p);
+    });
     return (int)nslice;
 }
 

@@ -8,9 +8,7 @@
 // by the memory system instead: a thread owns one 2x2 pool window = 4 output pixels x all output channels, reads its 4x4 input patch
 // once (16 loads per input channel, issued together), takes the filter from LDS as wave-wide broadcasts, and every tensor leaves in runs
 // that are contiguous across the wave (2*Cout floats per lane for the conv-sized tensors, Cout per lane for the pooled ones).
-#include "t4k_common.h"
-
-using namespace t4k;
+#include "conv_types.h"
 
 namespace {
 
@@ -147,15 +145,7 @@ __global__ void __launch_bounds__(64) k_conv_img_block(ImgBlk p) {
 
 template <int CIN, bool NTV>
 bool launch_cout(const ImgBlk &p, int Cout, unsigned grid, hipStream_t hs) {
-    switch (Cout) {
-    case 4:  T4K_LAUNCH((k_conv_img_block<CIN, 4, NTV>),  dim3(grid), dim3(64), 0, hs, p); return true;
-    case 6:  T4K_LAUNCH((k_conv_img_block<CIN, 6, NTV>),  dim3(grid), dim3(64), 0, hs, p); return true;
-    case 8:  T4K_LAUNCH((k_conv_img_block<CIN, 8, NTV>),  dim3(grid), dim3(64), 0, hs, p); return true;
-    case 10: T4K_LAUNCH((k_conv_img_block<CIN, 10, NTV>), dim3(grid), dim3(64), 0, hs, p); return true;
-    case 12: T4K_LAUNCH((k_conv_img_block<CIN, 12, NTV>), dim3(grid), dim3(64), 0, hs, p); return true;
-    case 16: T4K_LAUNCH((k_conv_img_block<CIN, 16, NTV>), dim3(grid), dim3(64), 0, hs, p); return true;
-    default: return false;
-    }
+    return pick<4, 6, 8, 10, 12, 16>(Cout, [&](auto co) { T4K_LAUNCH((k_conv_img_block<CIN, co.value, NTV>), dim3(grid), dim3(64), 0, hs, p); });
 }
 
 
@@ -396,59 +386,42 @@ namespace t4k {
 // true when the layer was launched here (t4k_conv2d_fwd2 falls through to its other kernels otherwise); ICOPY may be null
 bool conv_thin_fwd(const float *I, float *ICOPY, float *O, const float *F, const float *B, int N, int H, int W, int C1, int C0, hipStream_t hs,
                    float *bn_part, size_t bn_part_floats, int *bn_chunks) {
+    const ConvLab &lab = conv_lab();
     if (bn_chunks) *bn_chunks = 0;
-    static const int on = T4K_LAB_ENV("T4K_CONV_THIN", 1);
-    if (!on || C1 < 1 || C1 > 4 || (C0 != 32 && C0 != 64) || (long)N * H * W >= 0x7fffff00L) return false;
+    if (!lab.thin || C1 < 1 || C1 > 4 || (C0 != 32 && C0 != 64) || (long)N * H * W >= 0x7fffff00L) return false;
     if (!aligned16(I) || !aligned16(O) || (ICOPY && !aligned16(ICOPY))) return false;       // 16-byte pieces of the batch copy and of the output rows
     const long ntile = ((long)N * H * W + 31) / 32;
-    static const int cap = std::max(1, T4K_LAB_ENV("T4K_CONV_THIN_WG", 512));
-    long wg = (ntile + 3) / 4; if (wg > cap) wg = cap;         // a wave walks ntile / (4 wg) tiles with its filter in registers
+    long wg = (ntile + 3) / 4; if (wg > lab.thin_wg) wg = lab.thin_wg;
     const dim3 g((unsigned)wg), b(256);
-    static const int nts = T4K_LAB_ENV("T4K_CONV_THIN_NT", 1);
     const bool stat = bn_part && bn_chunks && ((long)N * H * W) % 32 == 0 && (size_t)wg * 2 * C0 <= bn_part_floats;    // batch-norm sums from the epilogue: whole tiles only
     if (stat) *bn_chunks = (int)wg;
-#define T4K_THIN3(C_, T_, N_, S_) do { if (ICOPY) T4K_LAUNCH((k_conv_thin_fwd<C_, T_, true, N_, S_>), g, b, 0, hs, I, O, ICOPY, F, B, N, H, W, ntile, bn_part); \
-                                   else T4K_LAUNCH((k_conv_thin_fwd<C_, T_, false, N_, S_>), g, b, 0, hs, I, O, ICOPY, F, B, N, H, W, ntile, bn_part); } while (0)
-#define T4K_THIN2(C_, T_, N_) do { if (stat) T4K_THIN3(C_, T_, N_, true); else T4K_THIN3(C_, T_, N_, false); } while (0)
-#define T4K_THIN(C_, T_) do { if (nts) T4K_THIN2(C_, T_, true); else T4K_THIN2(C_, T_, false); } while (0)
-    switch (C1 * 4 + C0 / 32) {
-    case 5: T4K_THIN(1, 1); break; case 6: T4K_THIN(1, 2); break;
-    case 9: T4K_THIN(2, 1); break; case 10: T4K_THIN(2, 2); break;
-    case 13: T4K_THIN(3, 1); break; case 14: T4K_THIN(3, 2); break;
-    case 17: T4K_THIN(4, 1); break; case 18: T4K_THIN(4, 2); break;
-    default: return false;
-    }
-#undef T4K_THIN
-#undef T4K_THIN2
-#undef T4K_THIN3
+    pick<1, 2, 3, 4>(C1, [&](auto c1) { pick<1, 2>(C0 / 32, [&](auto nt) {
+        with_flags([&](auto copy, auto nts, auto st_) {
+            T4K_LAUNCH((k_conv_thin_fwd<c1.value, nt.value, copy.value, nts.value, st_.value>), g, b, 0, hs, I, O, ICOPY, F, B, N, H, W, ntile, bn_part);
+        }, ICOPY != nullptr, lab.thin_nt != 0, stat);
+    }); });
     return true;
 }
 // dF | dB partial slabs of the same layer: true when launched here, *nslice = slab rows ((9 C1 + 1) x C0 floats each) for k_conv_df_fold
 bool conv_thin_df(const float *I, const float *DO, float *part, size_t part_bytes, int N, int H, int W, int C1, int C0, int *nslice, hipStream_t hs) {
-    static const int on = T4K_LAB_ENV("T4K_CONV_THIN_DF", 1);
-    if (!on || C1 < 1 || C1 > 3 || (C0 != 32 && C0 != 64) || W < 2 || (long)N * H * W >= 0x7fffff00L) return false;
+    const ConvLab &lab = conv_lab();
+    if (!lab.thin_df || C1 < 1 || C1 > 3 || (C0 != 32 && C0 != 64) || W < 2 || (long)N * H * W >= 0x7fffff00L) return false;
     const long ntile = ((long)N * H * W + 31) / 32;
-    static const int cap = std::max(1, T4K_LAB_ENV("T4K_CONV_THIN_DF_WG", 512));
-    long wg = (ntile + 3) / 4; if (wg > cap) wg = cap;
+    long wg = (ntile + 3) / 4; if (wg > lab.thin_df_wg) wg = lab.thin_df_wg;
     while (wg > 1 && (size_t)wg * (9 * C1 + 1) * C0 * sizeof(float) > part_bytes) wg >>= 1;
     if ((size_t)wg * (9 * C1 + 1) * C0 * sizeof(float) > part_bytes) return false;
     const dim3 g((unsigned)wg), b(256);
-#define T4K_TDF(C_, T_) T4K_LAUNCH((k_conv_thin_df<C_, T_>), g, b, 0, hs, I, DO, part, N, H, W, ntile)
-    switch (C1 * 4 + C0 / 32) {
-    case 5: T4K_TDF(1, 1); break; case 6: T4K_TDF(1, 2); break;
-    case 9: T4K_TDF(2, 1); break; case 10: T4K_TDF(2, 2); break;
-    case 13: T4K_TDF(3, 1); break; case 14: T4K_TDF(3, 2); break;
-    default: return false;
-    }
-#undef T4K_TDF
+    pick<1, 2, 3>(C1, [&](auto c1) { pick<1, 2>(C0 / 32, [&](auto nt) {
+        T4K_LAUNCH((k_conv_thin_df<c1.value, nt.value>), g, b, 0, hs, I, DO, part, N, H, W, ntile);
+    }); });
     *nslice = (int)wg;
     return true;
 }
 // true when the block was launched here (t4k_conv2d_block_fwd falls through to its other kernels otherwise)
 bool conv_img_block_fwd(const float *I, float *ICOPY, float *O, const float *F, const float *B, const t4k_poolblock *blk,
                         int N, int H, int W, int C1, int C0, hipStream_t hs) {
-    static const int on = T4K_LAB_ENV("T4K_CONV_IMG", 1);
-    if (!on || (C1 != 1 && C1 != 3) || C0 > 16 || (H & 1) || (W & 1) || blk->KS != 2 || !blk->pool_layer) return false;
+    const ConvLab &lab = conv_lab();
+    if (!lab.img || (C1 != 1 && C1 != 3) || C0 > 16 || (H & 1) || (W & 1) || blk->KS != 2 || !blk->pool_layer) return false;
     if (blk->pre_layer == T4K_L_DROPOUT || blk->post_layer == T4K_L_DROPOUT) return false;      // mask draws stay with the Philox-carrying kernels
     if ((C0 & 1) == 0 && (!aligned16(O) || !aligned16(blk->pool_out))) return false;
     ImgBlk p;
@@ -458,8 +431,8 @@ bool conv_img_block_fwd(const float *I, float *ICOPY, float *O, const float *F, 
     p.N = N; p.H = H; p.W = W;
     const long nwin = (long)N * (H / 2) * (W / 2);
     const unsigned grid = (unsigned)((nwin + 63) / 64);
-    static const int nt = T4K_LAB_ENV("T4K_CONV_IMG_NT", 1);
-    if (nt) return C1 == 1 ? launch_cout<1, true>(p, C0, grid, hs) : launch_cout<3, true>(p, C0, grid, hs);
-    return C1 == 1 ? launch_cout<1, false>(p, C0, grid, hs) : launch_cout<3, false>(p, C0, grid, hs);
+    bool done = false;
+    pick<1, 3>(C1, [&](auto c1) { with_flags([&](auto nt) { done = launch_cout<c1.value, nt.value>(p, C0, grid, hs); }, lab.img_nt != 0); });
+    return done;
 }
 }

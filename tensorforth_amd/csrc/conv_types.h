@@ -1,0 +1,94 @@
+// conv_types.h - what the convolution units share (conv.hip, conv_few.hip, conv_big.hip, conv_img.hip, dconv.hip): every host function that crosses
+// a unit, declared once with its default arguments; the pending-fold block; the LAB switches.  Every kernel template is instantiated in exactly
+// one unit - the one that launches it.
+#pragma once
+#include "launch.h"
+#include "colsum.h"
+#include <algorithm>
+
+namespace t4k {
+// ---- conv_few.hip: thread-per-pixel vector kernels for few channels
+// forward / dX with Cin <= 4 and Cout <= 32 (K 3 or 5): true when the shape is served, *G / *NG = channels per group / groups
+bool conv_few_ok(int K, int Cin, int Cout, int *G, int *NG);
+template <bool BWD>
+void launch_conv_few(int K, hipStream_t hs, const float *X, float *Y, float *Y2, float *XC, const float *F, const float *B,
+                     int N, int Hx, int Wx, int Cin, int Hy, int Wy, int Cout, int C0f, int G, int NG);
+// the dF fold a dX launch may carry in its first `nfold` workgroups (nfold == 0: nothing pending); see k_conv_dx_and_fold
+struct FoldArgs { const float *part; float *DF, *DB; int nslice, ndf, ntot, nfold; };
+// dX of an image-input layer (C1 <= 4, filter within the LDS stage): k_conv_dx_wide or k_conv_dx_few, either carries `fa`
+bool conv_dx_few_ok(int K, int C1, int C0);
+void launch_conv_dx_few(int K, int S, int P, hipStream_t hs, const float *DO, float *DX, float *DX2, const float *F,
+                        int N, int H0, int W0, int C0, int H1, int W1, int C1, FoldArgs fa);
+
+// ---- conv_big.hip: LDS-staged MFMA GEMM tiling for many channels
+bool conv_big_ok(int Cin, int Cout);
+// forward (BWD = false) or dX (BWD = true); X / Cin are the gathered tensor, Y / Cout the produced one.  bn_part: where k_convbig8 may leave the
+// per-channel sums of Y as chunk partials (*bn_chunks > 0 says it did)
+template <bool BWD>
+void launch_conv_big(int K, int S, int P, hipStream_t hs, const float *X, float *Y, float *Y2, const float *F, const float *B,
+                     int N, int Hx, int Wx, int Cin, int Hy, int Wy, int Cout, int C0f, float *bn_part = nullptr, size_t bn_part_floats = 0, int *bn_chunks = nullptr);
+// dF partial slabs [slice][C1*K*K][C0]; returns the number of slices written (0: workspace too small)
+int launch_conv_big_df(int K, int S, int P, hipStream_t hs, const float *I, const float *DO, float *part, size_t part_floats,
+                       int N, int H1, int W1, int C1, int H0, int W0, int C0);
+
+// ---- conv_img.hip: image-input layers (3x3, stride 1, padding 1).  Each returns true when the layer was launched there
+bool conv_thin_fwd(const float *I, float *ICOPY, float *O, const float *F, const float *B, int N, int H, int W, int C1, int C0, hipStream_t hs,
+                   float *bn_part = nullptr, size_t bn_part_floats = 0, int *bn_chunks = nullptr);
+bool conv_thin_df(const float *I, const float *DO, float *part, size_t part_bytes, int N, int H, int W, int C1, int C0, int *nslice, hipStream_t hs);
+bool conv_img_block_fwd(const float *I, float *ICOPY, float *O, const float *F, const float *B, const t4k_poolblock *blk,
+                        int N, int H, int W, int C1, int C0, hipStream_t hs);
+
+// ---- reduce.hip: batch-norm forward from the chunk partials a conv epilogue left
+int bn_stats_for(const float *I, float *stat, int N, int HW, int C, const float *part, int nchunk, t4k_stream_t s);
+int bn_fwd_from_parts(const float *I, float *O, float *XH, const float *W, const float *B, float *stat, long NHW, int C, const float *part, int nchunk, hipStream_t hs);
+}
+
+using namespace t4k;
+
+namespace {
+
+constexpr int LDS_FILTER_FLOATS = 8192;          // 32 KiB filter slice per workgroup
+
+// The LAB switches of the convolution units, read once per unit (release builds: the defaults, no environment read).  Each is an ablation of one
+// rung of the dispatch; the measured reason for its default is given here or at the condition that uses it.
+struct ConvLab {
+    // the entry points (conv.hip)
+    int block      = T4K_LAB_ENV("T4K_CONV_BLOCK", 1);            // t4k_conv2d_block_fwd: the element-wise run in the conv epilogue
+    int big        = T4K_LAB_ENV("T4K_CONV_BIG", 1);              // many channels on the LDS-staged kernels of conv_big.hip
+    int few        = T4K_LAB_ENV("T4K_CONV_FEW", 1);              // few channels on the vector kernels of conv_few.hip
+    int ksplit     = T4K_LAB_ENV("T4K_CONV_KSPLIT", 1);           // gather kernel: two waves per tile on small layers
+    int bn_rider   = T4K_LAB_ENV("T4K_CONV_BN_RIDER", 1);         // 0: t4k_conv2d_bn_fwd / _bn_block_fwd are always the separate calls
+    // enough slices that ~2000 waves are in flight (each wave then issues only a few batches of loads) without
+    // inflating the partial slab the fold has to read: 512 workgroups in total across the (tap, c0) tiles
+    int df_wg      = std::max(1, T4K_LAB_ENV("T4K_CONV_DF_WG", 512));
+    // conv_few.hip
+    int dx_wide    = T4K_LAB_ENV("T4K_DX_WIDE", 1);               // C0 / 4 lanes per pixel for the image-input dX with 32 / 64 / 128 output channels
+    int dx_wide_wpc = T4K_LAB_ENV("T4K_DX_WIDE_WPC", 8);          // its workgroups per CU: the weights are loaded once per workgroup
+    // conv_big.hip, forward / dX
+    int big8       = T4K_LAB_ENV("T4K_CONVBIG8", 1);              // the 8-wave LDS-DMA kernel (k_convbig8)
+    int big8_bk32  = T4K_LAB_ENV("T4K_CONVBIG8_BK32", 1);         // 32-channel stages, two workgroups per CU: 0 off, 1 from two tiles per CU, 2 always
+    int big8_nt    = T4K_LAB_ENV("T4K_CONVBIG8_NT", 0);           // non-temporal output stores
+    int wide_mul   = T4K_LAB_ENV("T4K_CONVBIG_WIDE_MUL", 1);      // k_convbig: 128-wide tiles from this many workgroups per CU
+    // conv_big.hip, dF
+    int df_wpc     = std::max(1, T4K_LAB_ENV("T4K_DF_WGS_PER_CU", 3));   // k_convbig_df: workgroups per CU in total
+    int df_xcd     = T4K_LAB_ENV("T4K_DF_XCD", 1);                // slice counts in multiples of 8: a pixel slice stays on one XCD's L2
+    // 0 off, 1 (default) 64-pixel stages and one workgroup per CU, 2 32-pixel stages and two per CU, 3 / 4: the same with two or four taps of
+    // 64 / 32 channels per tile too - they lose: 9 taps fill 10 / 12 tap slots and the fold reads 51 slices (64 -> 128 @ 16x16: 96.3 + 24 us of fold against 89 + 12)
+    int dfw        = T4K_LAB_ENV("T4K_CONVBIG_DFW", 1);
+    int df8        = T4K_LAB_ENV("T4K_CONVBIG_DF8", 64);          // 0: the 4-wave register-staged kernel; 32 / 64 / 128: pixels per stage of the 8-wave LDS-DMA kernel
+    int df8_wpc    = T4K_LAB_ENV("T4K_CONVBIG_DF8_WPC", 0);       // 0: as many workgroups per CU as the LDS holds, at most 3
+    int df8_nst    = T4K_LAB_ENV("T4K_CONVBIG_DF8_NST", (df8 >= 64 ? 2 : 4));   // stage buffers
+    int df8_tp2    = T4K_LAB_ENV("T4K_CONVBIG_DF8_TP2", 1);       // two taps per 64-row tile when C1 == 32
+    int df8_dbg    = T4K_LAB_ENV("T4K_CONVBIG_DF8_DBG", 0);
+    // conv_img.hip
+    int thin       = T4K_LAB_ENV("T4K_CONV_THIN", 1);             // k_conv_thin_fwd
+    int thin_wg    = std::max(1, T4K_LAB_ENV("T4K_CONV_THIN_WG", 512));      // a wave walks ntile / (4 wg) tiles with its filter in registers
+    int thin_nt    = T4K_LAB_ENV("T4K_CONV_THIN_NT", 1);          // non-temporal output stores
+    int thin_df    = T4K_LAB_ENV("T4K_CONV_THIN_DF", 1);          // k_conv_thin_df
+    int thin_df_wg = std::max(1, T4K_LAB_ENV("T4K_CONV_THIN_DF_WG", 512));
+    int img        = T4K_LAB_ENV("T4K_CONV_IMG", 1);              // k_conv_img_block
+    int img_nt     = T4K_LAB_ENV("T4K_CONV_IMG_NT", 1);           // non-temporal stores of its full-size outputs
+};
+inline const ConvLab &conv_lab() { static const ConvLab v; return v; }
+
+}

@@ -12,11 +12,7 @@
 //             dB[co] += sum dO[..., co]                                                           -> column sum
 // The conv kernels want the virtual conv's filter as T4(C0,K,K,C1) (input channel major): a transposed copy of F is made per call
 // (C1*K*K*C0 elements, one small launch), with the taps flipped where the kernel applies the reference's flip itself (quirk a-11).
-#include "t4k_common.h"
-
-using namespace t4k;
-
-namespace t4k { int colsum_add(const float *X, float *OUT, long rows, int E, hipStream_t hs); }
+#include "conv_types.h"
 
 namespace {
 

@@ -1,12 +1,12 @@
 // gemm_types.h - what the GEMM translation units share (gemm.hip, linear.hip): the kernels' parameter blocks, the
-// host functions that cross units, and the three launch helpers every launcher of these kernels goes through.
+// host functions that cross units, and with_layout (launch_lds / with_flags: launch.h).
 // The kernels live in headers beside their host files (gemm_tile.h, gemm_l32.h, gemm_head_bwd.h) or in the one unit that launches them; every kernel template is
 // instantiated in exactly one unit - the one that launches it.
 #pragma once
-#include "t4k_common.h"
+#include "launch.h"
+#include "colsum.h"
 #include <stdlib.h>
 #include <mutex>
-#include <type_traits>
 
 namespace t4k {
 // mask-multiply backward of the element-wise run in front of a linear layer, applied to dX where it is produced:
@@ -21,7 +21,6 @@ struct ColSum { const float *X; float *out; int rows, E; bool done; };
 int gemm_launch(const float *A, const float *B, float *O, const float *bias, float alpha, float beta,
                 int tA, int tB, int M, int N, int K, int C, t4k_stream_t s, const ActEpi *epi = nullptr, bool *epi_done = nullptr,
                 ColSum *cs = nullptr, XFold *defer = nullptr, FoldRider *rider = nullptr);
-int colsum_add(const float *X, float *OUT, long rows, int E, hipStream_t hs);
 // linear_small.hip: classifier-head sized layers on the vector ALUs, one launch each way
 bool linear_small_ok(int E0, int E1);
 int  linear_small_fwd(const float *X, const float *W, const float *B, float *Y, float *P, int N, int E0, int E1, hipStream_t hs, const XFold *xf = nullptr,
@@ -57,22 +56,6 @@ struct GemmP {
     const float *Z = nullptr;          // 4 KiB of zeros (State::d_zero): source of LDS-DMA lanes past the K range / the matrix edge (DMA variants of the 32x32 kernels)
 };
 
-// Launch of a kernel with dynamic LDS: the kernel's limit is raised the first time it is launched, and again only when a later launch
-// asks for more (k_head_bwd_l32's request depends on the shapes).  Counted like every launch (T4K_LAUNCH).
-template <auto Kern> size_t &lds_granted() { static size_t bytes = 0; return bytes; }      // one per kernel, whatever the call site passes
-template <auto Kern, typename... Args>
-void launch_lds(dim3 grid, dim3 block, size_t lds, hipStream_t s, const Args &...args) {
-    size_t &granted = lds_granted<Kern>();
-    if (lds > granted) { (void)hipFuncSetAttribute(reinterpret_cast<const void *>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); granted = lds; }
-    T4K_LAUNCH(Kern, grid, block, lds, s, args...);
-}
-// run-time flags -> template arguments: f(std::bool_constant<flag>{}...), one instantiation of f per combination
-template <typename F> void with_flags(F &&f) { f(); }
-template <typename F, typename... Bs>
-void with_flags(F &&f, bool b, Bs... more) {
-    if (b) with_flags([&](auto... cs) { f(std::true_type{}, cs...); }, more...);
-    else   with_flags([&](auto... cs) { f(std::false_type{}, cs...); }, more...);
-}
 // (tA, tB) -> the kernels' <AKC, BKC>: an operand's K axis is contiguous in memory when A is not transposed / when B is
 template <typename F, typename... Bs>
 void with_layout(int tA, int tB, F &&f, Bs... more) { with_flags(f, !tA, tB != 0, more...); }

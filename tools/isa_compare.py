@@ -2,7 +2,7 @@
 """Compare the gfx950 code of two builds kernel by kernel.
 
   hipcc <the Makefile's CXXFLAGS> --cuda-device-only -S unit.hip -o dir/unit.s      (every unit that holds a kernel, both trees)
-  tools/isa_compare.py BEFORE_DIR AFTER_DIR [--brief] [--allow REGEX] [--rename 'OLD NAME=NEW NAME'] > report.txt
+  tools/isa_compare.py BEFORE_DIR AFTER_DIR [--brief] [--allow REGEX] [--gone REGEX] [--rename 'OLD NAME=NEW NAME'] > report.txt
 
 A kernel's text is everything from its label to .end_amdhsa_kernel (instructions and the descriptor block); block labels are renumbered per
 kernel, the kernel's own symbol is masked and comments are dropped, so only code can differ.  Kernels are matched by demangled name with
@@ -10,7 +10,7 @@ namespaces dropped (a parameter type that moves between namespaces renames the s
 changed.  A kernel that differs is "offsets only" when every differing line is the same instruction with another immediate (a kernarg offset in
 a scalar load or in the s_add_u32 / s_addc_u32 that forms a kernarg address) or the kernarg size.  Exit status 1 when the kernel sets differ,
 when a kernel differs that --allow does not name, or when an allowed one grew in registers, scratch or instructions or changed its LDS size.
---brief prints differing kernels only.
+--gone names kernels removed on purpose: each is listed as GONE and does not fail the run.  --brief prints differing kernels only.
 """
 import glob, os, re, shutil, subprocess, sys
 
@@ -43,7 +43,7 @@ def offsets_only(ba, bb):
 
 def main():
     opt = lambda o: [sys.argv[i + 1] for i, a in enumerate(sys.argv) if a == o]
-    allow, brief = opt("--allow"), "--brief" in sys.argv
+    allow, gone, brief = opt("--allow"), opt("--gone"), "--brief" in sys.argv
     A, B = kernels(sys.argv[1]), kernels(sys.argv[2])
     for pair in opt("--rename"):
         old, new = pair.split("=")
@@ -51,7 +51,9 @@ def main():
     bad = n_same = 0
     fmt = lambda r: "vgpr %d acc %d sgpr %d scratch %d lds %d instr %d" % tuple(r[k] for k in RES + ("instructions",))
     print("kernels before: %d   after: %d   per unit after: %s" % (len(A), len(B), ", ".join("%s %d" % (u, sum(1 for v in B.values() if v[0] == u)) for u in sorted({v[0] for v in B.values()}))))
-    for n in sorted(set(A) - set(B)): print("ONLY BEFORE  " + n); bad += 1
+    for n in sorted(set(A) - set(B)):
+        if any(re.search(p, n) for p in gone): print("GONE         " + n)
+        else: print("ONLY BEFORE  " + n); bad += 1
     for n in sorted(set(B) - set(A)): print("ONLY AFTER   " + n); bad += 1
     for n in sorted(set(A) & set(B)):
         (fa, ba, ra), (fb, bb, rb) = A[n], B[n]
