@@ -147,6 +147,7 @@ struct Tensor : Obj {
     static Tensor &ten_bcast(int op, Tensor &A, Tensor &B, Tensor &O);   // NumPy broadcasting over N, H, W, C (beyond ten_op)
     enum { AX_SUM = 0, AX_AVG, AX_STD, AX_NORM };
     static Tensor &reduce_axes(int word, Tensor &T, int mask);          // sum / avg / std / norm along the masked axes (N = 8, H = 4, W = 2, C = 1), keepdims
+    static void softmax_axes(Tensor &T, int mask);                      // in place: every group along the masked axes becomes exp(x - max) / sum exp(x - max)
     static Tensor &mm(Tensor &A, Tensor &B, Tensor &O, bool inc = false, bool tA = false, bool tB = false);
     static Tensor &bmm(Tensor &A, Tensor &B, Tensor &O, uint32_t M, uint32_t K, uint32_t P);   // NumPy @ over N and C (beyond _tdot)
     static Tensor &gemm(int variant, Tensor &A, Tensor &B, Tensor &O, DU alpha, DU beta);

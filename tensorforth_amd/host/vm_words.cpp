@@ -358,6 +358,15 @@ void VM::init_tensor() {
 
 // ---------------------------------------------------------------- nn vocabulary helpers (netvm.cpp:20-286)
 void VM::nnop(int op) {
+    // beyond the reference ( T m -- T ): a scalar axis mask on top of a tensor makes `softmax` a softmax of every group along the masked
+    // axes, N = 8, H = 4, W = 2, C = 1, in place; the reference prints its "no param needed!" for this operand set
+    if (op == T4K_L_SOFTMAX && !IS_OBJ(tos_) && SP() >= 1 && is_t(SS(-1))) {
+        const DU m = POP();
+        const int mask = (m >= 1.0f && m <= 15.0f) ? (int)m : 0;
+        if (!mask || (DU)mask != m) { pstr("softmax: axes 1..15?\n"); return; }
+        Tensor::softmax_axes(TTOS(), mask);
+        return;
+    }
     if (TOS1T()) {                                       // tensor ops (destructive)
         Tensor &t = TTOS();
         switch (op) {
