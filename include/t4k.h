@@ -284,6 +284,10 @@ int t4k_det_batched(float *A, int *piv_dev, int K, int batch, float *det_dev, in
 int t4k_rand_init(uint64_t seed);
 /* d[i] = scale * (bias + u_i), u uniform (0,1] or N(0,1) (util.cu:58-70) */
 int t4k_rand(float *d, long n, int opt, float bias, float scale, t4k_stream_t s);
+/* The stream position is kept in whole Philox counters of 4 elements.  t4k_rand_set_offset(off) rounds `off` (in elements) DOWN to a
+ * multiple of 4 - the remainder is dropped, not remembered - and t4k_rand_offset() always returns a multiple of 4: the position set, plus
+ * 4 * ceil(n / 4) for every draw of n elements since (times `world` for a sample-keyed draw of a shard, below).  Offsets are 64-bit and
+ * wrap mod 2^64; the counter's high word and the seed's high word are both part of the stream (element 2^34 is counter 2^32). */
 uint64_t t4k_rand_offset(void);                    /* current stream offset (for checkpoint/tests) */
 int t4k_rand_set_offset(uint64_t off);
 uint64_t t4k_rand_seed(void);                      /* the seed of the stream (a host that embeds several VMs saves / restores (seed, offset) per VM) */

@@ -65,7 +65,7 @@ float fork_reduce_sum(long n, F term) {
 }
 
 /* ---- Philox4x32-10 (Salmon et al. SC'11), counter = element_index/4, key = seed ---- */
-uint64_t g_seed = 0, g_off = 0;
+uint64_t g_seed = 0, g_ctr = 0;   /* position in whole counters of 4 elements, 64-bit as the product's (csrc/t4k_common.h State::rng_ctr) */
 inline void philox4x32_10(uint64_t ctr, uint64_t key, uint32_t out[4]) {
     uint32_t c0 = (uint32_t)ctr, c1 = (uint32_t)(ctr >> 32), c2 = 0, c3 = 0;
     uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
@@ -362,11 +362,11 @@ int t4o_logdet(const float *LU, int K, float *logdet, int *sign) {
 /* t4_rand_init / t4_rand src/util.cu:28-70: x = scale*(bias+u).  The cuRAND XORWOW
  * stream is not reproduced (the reference seeds from time(), src/sys.cpp:37); the
  * oracle and the HIP backend share the Philox4x32-10 definition instead. */
-int      t4o_rand_init(uint64_t seed) { g_seed = seed; g_off = 0; return OK; }
-uint64_t t4o_rand_offset(void)        { return g_off; }
-int      t4o_rand_set_offset(uint64_t off) { g_off = off; return OK; }
+int      t4o_rand_init(uint64_t seed) { g_seed = seed; g_ctr = 0; return OK; }
+uint64_t t4o_rand_offset(void)        { return g_ctr * 4; }
+int      t4o_rand_set_offset(uint64_t off) { g_ctr = off / 4; return OK; }   /* include/t4k.h: rounded down to a whole counter (4 elements) */
 int t4o_rand(float *d, long n, int opt, float bias, float scale) {
-    const uint64_t base = g_off / 4;                   /* g_off is kept a multiple of 4 */
+    const uint64_t base = g_ctr;
     for (long q = 0; q * 4 < n; q++) {
         uint32_t r[4];
         philox4x32_10(base + (uint64_t)q, g_seed, r);
@@ -380,7 +380,7 @@ int t4o_rand(float *d, long n, int opt, float bias, float scale) {
         } else for (int k = 0; k < 4; k++) v[k] = u01(r[k]);
         for (int k = 0; k < 4; k++) { long i = q * 4 + k; if (i < n) d[i] = scale * (bias + v[k]); }
     }
-    g_off += (uint64_t)((n + 3) / 4) * 4;
+    g_ctr += (uint64_t)((n + 3) / 4);
     return OK;
 }
 
@@ -394,10 +394,10 @@ int t4o_rand_set_shard(int rank, int world) {
 uint64_t t4o_rand_seed(void) { return g_seed; }
 int t4o_rand_shard_world(void) { return g_shard_world; }
 int t4o_dropout_mask(float *mask, long n) {
-    const uint64_t nq = (uint64_t)((n + 3) / 4), off0 = g_off;
-    g_off = off0 + (uint64_t)g_shard_rank * nq * 4;
+    const uint64_t nq = (uint64_t)((n + 3) / 4), ctr0 = g_ctr;
+    g_ctr = ctr0 + (uint64_t)g_shard_rank * nq;
     int rc = t4o_rand(mask, n, 0, 0.0f, 1.0f);
-    g_off = off0 + (uint64_t)g_shard_world * nq * 4;
+    g_ctr = ctr0 + (uint64_t)g_shard_world * nq;
     return rc;
 }
 
