@@ -1,7 +1,7 @@
 // bcast.hip - NumPy-style broadcast arithmetic and the batched transpose of the rank-4 words.  Both are
 // HBM-bound streaming kernels: one launch per call, no allocation, no synchronisation.  No reference definition: the
 // reference's k_tt_op (src/t4math.cu:222) takes two flat tensors of one size, its k_transpose (:150) one sample.
-#include "t4k_common.h"
+#include "launch.h"
 
 using namespace t4k;
 
@@ -31,12 +31,6 @@ struct BcastPlan {
     unsigned ext[3];
     unsigned nc, rpb, shift;      // one of nc / rpb is 1
 };
-
-// x = q * d + rem; the 32-bit divide whenever x fits (every tensor below 16 GiB)
-__device__ __forceinline__ void divmod(long x, unsigned d, long &q, unsigned &rem) {
-    if (x < 0xffffffffL) { const unsigned v = (unsigned)x, t = v / d; rem = v - t * d; q = (long)t; }
-    else { const long t = x / (long)d; rem = (unsigned)(x - t * (long)d); q = t; }
-}
 
 template <int OP, bool VEC>
 __global__ void __launch_bounds__(BLK) k_tt_bcast(const float *A, const float *B, float *O, const BcastPlan p) {
@@ -98,8 +92,6 @@ inline bool run_vec_ok(long inner, const long outer[3]) {
 
 extern "C" {
 
-#define BC_CASE(OP) case OP: if (vec) T4K_LAUNCH((k_tt_bcast<OP, true>), dim3(g), dim3(BLK), 0, S(s), A, B, O, p); \
-                             else     T4K_LAUNCH((k_tt_bcast<OP, false>), dim3(g), dim3(BLK), 0, S(s), A, B, O, p); break
 int t4k_tt_op_bcast(int op, const float *A, const float *B, float *O, const int dim[4], const long sA[4], const long sB[4], t4k_stream_t s) {
     T4K_REQUIRE_INIT();
     if (!A || !B || !O || !dim || !sA || !sB) return fail(T4K_ERR_ARG, "t4k_tt_op_bcast: null");
@@ -134,7 +126,9 @@ int t4k_tt_op_bcast(int op, const float *A, const float *B, float *O, const int 
     p.nc = (unsigned)((p.U + BLK - 1) / BLK);                             // 256-lane chunks per run (1 below that)
     p.nitem = ((p.R + p.rpb - 1) / p.rpb) * p.nc;
     const int g = grid_for(p.nitem * BLK);
-    switch (op) { BC_CASE(T4K_ADD); BC_CASE(T4K_SUB); BC_CASE(T4K_MUL); BC_CASE(T4K_DIV); }
+    pick<T4K_ADD, T4K_SUB, T4K_MUL, T4K_DIV>(op, [&](auto o) { with_flags([&](auto v) {
+        T4K_LAUNCH((k_tt_bcast<o.value, v.value>), dim3(g), dim3(BLK), 0, S(s), A, B, O, p);
+    }, vec); });
     T4K_LAUNCH_CHECK(); return T4K_OK;
 }
 

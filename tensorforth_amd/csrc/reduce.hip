@@ -12,19 +12,7 @@ namespace {
 
 constexpr int RED_MAX_PARTS = 1024;
 
-enum { R_SUM = 0, R_NVAR, R_MAX, R_MIN, R_BCE };
-
-template <int OP> __device__ __forceinline__ float r_init() {
-    return OP == R_MAX ? -FLT_MAX : (OP == R_MIN ? FLT_MAX : 0.0f);
-}
-template <int OP> __device__ __forceinline__ float r_comb(float a, float b) {
-    return OP == R_MAX ? fmaxf(a, b) : (OP == R_MIN ? fminf(a, b) : a + b);
-}
-template <int OP> __device__ __forceinline__ float r_term(float x, float y, float avg) {
-    if (OP == R_NVAR) { float d = x - avg; return d * d; }
-    if (OP == R_BCE)  return y * __logf(x + DU_EPS) + (1.0f - y) * __logf(1.0f - x + DU_EPS);  // x = O, y = T
-    return x;
-}
+// r_init / r_comb / r_term and the R_* operations: t4k_common.h
 template <int OP> __device__ __forceinline__ float wave_comb_all(float v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v = r_comb<OP>(v, __shfl_xor(v, off, 64));

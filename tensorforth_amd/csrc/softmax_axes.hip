@@ -3,27 +3,14 @@
 // (reduce.hip: max shift, __expf, fp32 sum, one fp32 division per element), fixed trees, no floating-point atomics: the same bits on
 // every run.  No reference definition: the reference's only softmax is the layer's row form (_fsoftmax forward.cu:222-243) and the
 // whole-tensor word (netvm.cpp:36-39).
-#include "t4k_common.h"
-#include <float.h>
-#include <type_traits>
+#include "axes.h"
 
 using namespace t4k;
 
 namespace {
 
-// x = q * d + rem; the 32-bit divide whenever x fits.  Used once per workgroup iteration or once per group, never per element.
-__device__ __forceinline__ void divmod(long x, unsigned d, long &q, unsigned &rem) {
-    if (x < 0xffffffffL) { const unsigned v = (unsigned)x, t = v / d; rem = v - t * d; q = (long)t; }
-    else { const long t = x / (long)d; rem = (unsigned)(x - t * (long)d); q = t; }
-}
-
-// the planner's constants: the first two and MAX_SPLIT / SPLIT_UNITS are k_red_row's (reduce_axes.hip), the third is this unit's
-constexpr long TARGET_LANES = 64L * 4 * 256 * 2;   // two waves on every SIMD of 256 CUs: below this a group gets more lanes
-constexpr long TARGET_ITEMS = 1024;                // workgroups a split aims for: four on every CU
-constexpr int  NV           = 8;                   // loads (floats, or float4s on the vector path) a lane keeps in registers: the register-resident
+constexpr int NV = 8;                              // loads (floats, or float4s on the vector path) a lane keeps in registers: the register-resident
                                                    // regime holds a lane's whole share in NV of them, the other regimes walk theirs NV at a time
-constexpr long SPLIT_UNITS  = 8;                   // loads a lane keeps at least when a group is split across workgroups
-constexpr long MAX_SPLIT    = 4096;
 
 // what a launch does.  REG: a lane's share of the group stays in registers (read once, written once).  ONLINE: pass 1 keeps a running
 // (max, sum), pass 2 reads again and writes.  PART: pass 1 over one part of a group, the pair left in the workspace.  NORM: pass 2 with
@@ -42,18 +29,7 @@ template <> struct Val<false> {
     static __device__ __forceinline__ void st(float *p, const float (&d)[1]) { *p = d[0]; }
 };
 
-// ---- row family: the innermost merged group is reduced.  Group o is r1 runs (sr1 apart) of r0 contiguous floats starting at
-// base(o) = o * sk0, or (o / k0) * sk1 + (o % k0) * sk0 when a second kept group lies outside the runs.  1 << shift lanes share a group
-// (shift 0..5: several groups per wave, 6: a wave per group, 8: a workgroup per group), 1 << su of them side by side along a run and
-// the rest over the runs; a lane walks its units (a float, or a float4 on the vector path) run by run with two counters, no division.
-// S > 1 (PART / NORM): the units of a run (split_u) or the runs are dealt to S workgroups of `per` each.
-struct RowPlan {
-    long nout, U, r1;             // groups, units per run, runs per group
-    long sk0, sr1, sk1, per, nitem;
-    unsigned k0, shift, su, S;
-    int four, split_u;
-};
-
+// ---- row family (RowPlan, axes.h); a lane walks its units (a float, or a float4 on the vector path) run by run.  S > 1: PART / NORM.
 template <bool MAX> __device__ __forceinline__ float row_fold(float v, unsigned G, unsigned shift, float *sm) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) { const float t = __shfl_xor(v, off, 64); if ((unsigned)off < G) v = MAX ? fmaxf(v, t) : v + t; }
@@ -91,8 +67,7 @@ __global__ void __launch_bounds__(BLK) k_smax_row(const float *X, float *O, floa
         const long u0 = ua + lu, r0 = ra + lr;
         if (!live || u0 >= ub) rb = ra;                                     // nothing for this lane
         const float *xb = X + base; float *ob = O + base;
-        // the walk: unit u of run r, then Gu further along the run, at its end the lane's first unit of the run Gr further
-#define ROW_STEP(r, u) do { u += Gu; if (u >= ub) { u = u0; r += Gr; } } while (0)
+        // the walk (walk_step): unit u of run r, then Gu further along the run, at its end the lane's first unit of the run Gr further
         float m = -FLT_MAX, sum = 0.0f;
         if (MODE == M_REG) {
             float v[NV][V]; int cnt = 0;
@@ -103,7 +78,7 @@ __global__ void __launch_bounds__(BLK) k_smax_row(const float *X, float *O, floa
                     Val<VEC>::ld(xb + r * p.sr1 + u * V, v[i]); cnt = i + 1;
 #pragma unroll
                     for (int q = 0; q < V; q++) m = fmaxf(m, v[i][q]);
-                    ROW_STEP(r, u);
+                    walk_step(r, u, u0, ub, Gu, Gr);
                 }
             }
             m = row_fold<true>(m, G, p.shift, sm);
@@ -126,7 +101,7 @@ __global__ void __launch_bounds__(BLK) k_smax_row(const float *X, float *O, floa
 #pragma unroll
                     for (int q = 0; q < V; q++) v[i][q] = v[i][q] / sum;
                     Val<VEC>::st(ob + r * p.sr1 + u * V, v[i]);
-                    ROW_STEP(r, u);
+                    walk_step(r, u, u0, ub, Gu, Gr);
                 }
             }
             continue;
@@ -141,7 +116,7 @@ __global__ void __launch_bounds__(BLK) k_smax_row(const float *X, float *O, floa
                         Val<VEC>::ld(xb + r * p.sr1 + u * V, v[i]); cnt = i + 1;
 #pragma unroll
                         for (int q = 0; q < V; q++) cm = fmaxf(cm, v[i][q]);
-                        ROW_STEP(r, u);
+                        walk_step(r, u, u0, ub, Gu, Gr);
                     }
                 }
                 const float mn = fmaxf(m, cm);
@@ -171,7 +146,7 @@ __global__ void __launch_bounds__(BLK) k_smax_row(const float *X, float *O, floa
                 long rs = r, us = u;
 #pragma unroll
                 for (int i = 0; i < NV; i++) {
-                    if (r < rb) { Val<VEC>::ld(xb + r * p.sr1 + u * V, v[i]); cnt = i + 1; ROW_STEP(r, u); }
+                    if (r < rb) { Val<VEC>::ld(xb + r * p.sr1 + u * V, v[i]); cnt = i + 1; walk_step(r, u, u0, ub, Gu, Gr); }
                 }
 #pragma unroll
                 for (int i = 0; i < NV; i++) {
@@ -179,26 +154,15 @@ __global__ void __launch_bounds__(BLK) k_smax_row(const float *X, float *O, floa
 #pragma unroll
                         for (int q = 0; q < V; q++) v[i][q] = __expf(v[i][q] - m) / sum;
                         Val<VEC>::st(ob + rs * p.sr1 + us * V, v[i]);
-                        ROW_STEP(rs, us);
+                        walk_step(rs, us, u0, ub, Gu, Gr);
                     }
                 }
             }
         }
-#undef ROW_STEP
     }
 }
 
-// ---- column family: the innermost merged group (k0 floats) is kept.  A workgroup iteration takes one tile of TX = 1 << sx lanes along
-// k0 (one column a lane, four on the vector path: every load of a wave is a contiguous run) of one outer kept index; its 256 >> sx row
-// groups deal the reduced rows (r0 of them sr0 apart, inside r1 of them sr1 apart) among themselves.  Max and sum fold inside the wave by
-// xor shuffles over the lane bits above sx, the four waves through LDS.  S > 1 (PART / NORM): the rows (or the outer reduced extent,
-// split_r1) are dealt to S workgroups.
-struct ColPlan {
-    long k0, r0, r1, sr0, sk1, sr1, per, nitem, nout;
-    unsigned sx, ntile, S;
-    int split_r1;
-};
-
+// ---- column family (ColPlan, axes.h); max and sum fold over the row groups.  S > 1: PART / NORM.
 // every lane leaves with the fold of its own columns over all row groups
 template <bool MAX, int V> __device__ __forceinline__ void col_fold(float (&a)[V], unsigned TX, unsigned tx, float (*sm)[64 * V]) {
     const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -242,8 +206,7 @@ __global__ void __launch_bounds__(BLK) k_smax_col(const float *X, float *O, floa
         if (!live || r0 >= rb) jb = ja;                                     // nothing for this lane
         const long off = ik1 * p.sk1 + (live ? col : 0);
         const float *xb = X + off; float *ob = O + off;
-        // the walk: row r of outer index j, then TY rows further, at the end the lane's first row of the next outer index
-#define COL_STEP(j, r) do { r += TY; if (r >= rb) { r = r0; j++; } } while (0)
+        // the walk (walk_step): row r of outer index j, then TY rows further, at the end the lane's first row of the next outer index
         float m[V], sum[V];
 #pragma unroll
         for (int q = 0; q < V; q++) { m[q] = -FLT_MAX; sum[q] = 0.0f; }
@@ -256,7 +219,7 @@ __global__ void __launch_bounds__(BLK) k_smax_col(const float *X, float *O, floa
                     Val<VEC>::ld(xb + j * p.sr1 + r * p.sr0, v[i]); cnt = i + 1;
 #pragma unroll
                     for (int q = 0; q < V; q++) m[q] = fmaxf(m[q], v[i][q]);
-                    COL_STEP(j, r);
+                    walk_step(j, r, r0, rb, TY, 1u);
                 }
             }
             col_fold<true, V>(m, TX, tx, sm);
@@ -275,7 +238,7 @@ __global__ void __launch_bounds__(BLK) k_smax_col(const float *X, float *O, floa
 #pragma unroll
                     for (int q = 0; q < V; q++) v[i][q] = v[i][q] / sum[q];
                     Val<VEC>::st(ob + j * p.sr1 + r * p.sr0, v[i]);
-                    COL_STEP(j, r);
+                    walk_step(j, r, r0, rb, TY, 1u);
                 }
             }
             continue;
@@ -292,7 +255,7 @@ __global__ void __launch_bounds__(BLK) k_smax_col(const float *X, float *O, floa
                         Val<VEC>::ld(xb + j * p.sr1 + r * p.sr0, v[i]); cnt = i + 1;
 #pragma unroll
                         for (int q = 0; q < V; q++) cm[q] = fmaxf(cm[q], v[i][q]);
-                        COL_STEP(j, r);
+                        walk_step(j, r, r0, rb, TY, 1u);
                     }
                 }
 #pragma unroll
@@ -330,7 +293,7 @@ __global__ void __launch_bounds__(BLK) k_smax_col(const float *X, float *O, floa
                 long js = j, rs = r;
 #pragma unroll
                 for (int i = 0; i < NV; i++) {
-                    if (j < jb) { Val<VEC>::ld(xb + j * p.sr1 + r * p.sr0, v[i]); cnt = i + 1; COL_STEP(j, r); }
+                    if (j < jb) { Val<VEC>::ld(xb + j * p.sr1 + r * p.sr0, v[i]); cnt = i + 1; walk_step(j, r, r0, rb, TY, 1u); }
                 }
 #pragma unroll
                 for (int i = 0; i < NV; i++) {
@@ -338,12 +301,11 @@ __global__ void __launch_bounds__(BLK) k_smax_col(const float *X, float *O, floa
 #pragma unroll
                         for (int q = 0; q < V; q++) v[i][q] = __expf(v[i][q] - m[q]) / sum[q];
                         Val<VEC>::st(ob + js * p.sr1 + rs * p.sr0, v[i]);
-                        COL_STEP(js, rs);
+                        walk_step(js, rs, r0, rb, TY, 1u);
                     }
                 }
             }
         }
-#undef COL_STEP
     }
 }
 
@@ -365,16 +327,6 @@ __global__ void __launch_bounds__(BLK) k_smax_merge(const float *__restrict__ Wk
     }
 }
 
-inline unsigned log2_ceil(long x, unsigned cap) { unsigned k = 0; while (k < cap && (1L << k) < x) k++; return k; }
-inline long ceil_div(long a, long b) { return (a + b - 1) / b; }
-// how many workgroups share one group: enough for TARGET_ITEMS, never leaving a lane fewer than SPLIT_UNITS loads, never more pairs
-// (S per group and the merged one) than the stream's workspace holds
-inline long split_for(long items, long max_by_work, long nout) {
-    long S = std::min(std::min(ceil_div(TARGET_ITEMS, items), max_by_work), MAX_SPLIT);
-    S = std::min(S, (long)(st().ws_bytes / sizeof(float)) / (2 * nout) - 1);
-    return S < 2 ? 1 : S;
-}
-
 // what the planner decided, for the launcher and for t4k_softmax_axes_plan
 struct Plan {
     bool col, vec;
@@ -383,121 +335,67 @@ struct Plan {
     RowPlan row; ColPlan cl;
 };
 
-void plan_row(Plan &P, long nout, long r0, long r1, long k0, bool four, bool vec) {
-    RowPlan &p = P.row; p = RowPlan{};
-    P.col = false; P.vec = vec;
-    p.nout = nout; p.U = vec ? r0 >> 2 : r0; p.r1 = r1; p.k0 = (unsigned)k0; p.four = four;
-    p.sk0 = r0; p.sr1 = r0 * k0; p.sk1 = r0 * k0 * r1;
-    const long T = p.U * r1;                                                 // loads behind one group
-    p.shift = log2_ceil(ceil_div(T, NV), 8);
-    const unsigned cap = log2_ceil(T, 8);
-    while (p.shift < cap && (nout << p.shift) < TARGET_LANES) p.shift++;
-    if (p.shift == 7) p.shift = (nout << 6) >= TARGET_LANES ? 6 : 8;         // a wave or a workgroup: nothing between
-    auto slots = [&](long ext_u) {
+// a split costs a workspace of S pairs per group and the merged pair: two floats per group and part, one part reserved
+void plan_row(Plan &P, const Merged &m, long ws_floats) {
+    RowPlan &p = P.row;
+    row_geometry(p, m, P.vec);
+    p.shift = row_lanes(p.U * p.r1, NV, p.nout);
+    auto slots = [&](long ext_u, long ext_r) {                               // loads of a lane over ext_u units of ext_r runs
         p.su = std::min(p.shift, log2_ceil(ext_u, 8));
-        return ceil_div(ext_u, 1L << p.su) * ceil_div(r1, (1L << p.shift) >> p.su);
+        return ceil_div(ext_u, 1L << p.su) * ceil_div(ext_r, (1L << p.shift) >> p.su);
     };
-    long n = slots(p.U);
-    while (n > NV && p.shift < 8) { p.shift = p.shift >= 6 ? 8 : p.shift + 1; n = slots(p.U); }   // the ceilings left a lane more than NV: more lanes
-    p.S = 1; p.split_u = 0; p.per = 0;
+    long n = slots(p.U, p.r1);
+    while (n > NV && p.shift < 8) { p.shift = p.shift >= 6 ? 8 : p.shift + 1; n = slots(p.U, p.r1); }   // the ceilings left a lane more than NV: more lanes
     P.regime = n <= NV ? 0 : 1;
-    if (P.regime == 1) {                                                     // shift == 8 here
-        const long S = split_for(nout, T / (BLK * SPLIT_UNITS), nout);
-        if (S > 1) {
-            P.regime = 2;
-            p.split_u = p.U >= r1;
-            const long ext = p.split_u ? p.U : r1;
-            p.per = ceil_div(ext, S); p.S = (unsigned)ceil_div(ext, p.per);
-            n = p.split_u ? slots(p.per) : ceil_div(p.U, 1L << p.su) * ceil_div(p.per, (1L << p.shift) >> p.su);
-        }
+    if (P.regime == 1 && row_split(p, 2, 1, ws_floats)) {                    // shift == 8 here
+        P.regime = 2;
+        n = p.split_u ? slots(p.per, p.r1) : slots(p.U, p.per);
     }
     P.chunks = (int)ceil_div(n, NV);
-    p.nitem = ceil_div(nout, BLK >> p.shift) * p.S;
+    p.nitem = ceil_div(p.nout, BLK >> p.shift) * p.S;
 }
 
-void plan_col(Plan &P, long k0, long r0, long k1, long r1, bool vec) {
-    ColPlan &p = P.cl; p = ColPlan{};
-    P.col = true; P.vec = vec;
-    p.k0 = k0; p.r0 = r0; p.r1 = r1; p.sr0 = k0; p.sk1 = k0 * r0; p.sr1 = k0 * r0 * k1; p.nout = k0 * k1;
-    const long Uk = vec ? k0 >> 2 : k0;
-    p.sx = log2_ceil(Uk, 6);
+void plan_col(Plan &P, const Merged &m, long ws_floats) {
+    ColPlan &p = P.cl;
+    col_geometry(p, m, P.vec);
     const long TY = BLK >> p.sx;
-    p.ntile = (unsigned)ceil_div(Uk, 1L << p.sx);
-    const long items = k1 * p.ntile;
-    p.S = 1; p.split_r1 = 0; p.per = 0;
-    long n = ceil_div(r0, TY) * r1;
+    long n = ceil_div(p.r0, TY) * p.r1;
     P.regime = n <= NV ? 0 : 1;
-    if (P.regime == 1 && items < TARGET_ITEMS) {
-        const bool by_r1 = r1 > r0;
-        const long S = split_for(items, by_r1 ? r1 / 4 : r0 / (TY * SPLIT_UNITS), p.nout);
-        if (S > 1) {
-            P.regime = 2;
-            p.split_r1 = by_r1;
-            const long ext = by_r1 ? r1 : r0;
-            p.per = ceil_div(ext, S); p.S = (unsigned)ceil_div(ext, p.per);
-            n = by_r1 ? ceil_div(r0, TY) * p.per : ceil_div(p.per, TY) * r1;
-        }
+    if (P.regime == 1 && col_split(p, 2, 1, ws_floats)) {
+        P.regime = 2;
+        n = p.split_r1 ? ceil_div(p.r0, TY) * p.per : ceil_div(p.per, TY) * p.r1;
     }
     P.chunks = (int)ceil_div(n, NV);
-    p.nitem = items * p.S;
 }
 
-// axes of extent 1 drop out, neighbours that are both kept or both reduced merge: at most four alternating groups (as t4k_reduce_axes)
 int make_plan(Plan &P, const int dim[4], int mask, bool aligned, const char *who) {
-    long e[5]; bool red[5]; int n = 0; bool any = false;
-    for (int i = 0; i < 4; i++) {
-        if (dim[i] == 1) continue;
-        const bool r = (mask & (8 >> i)) != 0;
-        any = any || r;
-        if (n && red[n - 1] == r) e[n - 1] *= dim[i];
-        else { e[n] = dim[i]; red[n] = r; n++; }
-    }
-    if (!any) { e[n] = 1; red[n] = true; n++; }                              // only axes of extent 1 are masked: every element is its own group
-    if (red[n - 1]) {
-        const long r0 = e[n - 1], k0 = n >= 2 ? e[n - 2] : 1, r1 = n >= 3 ? e[n - 3] : 1, k1 = n >= 4 ? e[n - 4] : 1;
-        if (k0 > 0xffffffffL) return fail(T4K_ERR_ARG, "%s: merged extent too large", who);
-        plan_row(P, k0 * k1, r0, r1, k0, n == 4, aligned && (r0 & 3) == 0);  // every run starts on a multiple of r0 elements
-    } else {
-        const long k0 = e[n - 1], r0 = e[n - 2], k1 = n >= 3 ? e[n - 3] : 1, r1 = n >= 4 ? e[n - 4] : 1;
-        plan_col(P, k0, r0, k1, r1, aligned && (k0 & 3) == 0);               // every row starts on a multiple of k0 elements
-    }
-    return T4K_OK;
-}
-
-int check_args(const float *src, float *dst, const int dim[4], int mask, bool pointers, const char *who) {
-    if ((pointers && (!src || !dst)) || !dim) return fail(T4K_ERR_ARG, "%s: null", who);
-    if (mask < 1 || mask > 15) return fail(T4K_ERR_ARG, "%s: mask %d outside 1..15", who, mask);
-    long total = 1;
-    for (int i = 0; i < 4; i++) {
-        if (dim[i] < 1) return fail(T4K_ERR_ARG, "%s: extent %d", who, dim[i]);
-        if (total > (1L << 40) / dim[i]) return fail(T4K_ERR_ARG, "%s: more than 2^40 elements", who);
-        total *= dim[i];
-    }
-    if (pointers && src != dst && src < dst + total && dst < src + total) return fail(T4K_ERR_ARG, "%s: dst overlaps src", who);
+    Merged m;
+    const int rc = merge_axes(dim, mask, who, m); if (rc != T4K_OK) return rc;
+    const long ws_floats = (long)(st().ws_bytes / sizeof(float));
+    P.col = m.col;
+    P.vec = aligned && ((m.col ? m.k0 : m.r0) & 3) == 0;                     // every row starts on a multiple of k0 elements, every run on one of r0
+    if (m.col) plan_col(P, m, ws_floats); else plan_row(P, m, ws_floats);
     return T4K_OK;
 }
 
 template <int MODE, typename PlanT>
-void launch(bool col, bool vec, const float *X, float *O, float *Wk, const PlanT &p, hipStream_t hs) {
+void launch(bool vec, const float *X, float *O, float *Wk, const PlanT &p, hipStream_t hs) {
     const int g = (int)std::min(p.nitem, (long)MAX_WG);
-    if constexpr (std::is_same<PlanT, ColPlan>::value) {
-        if (vec) T4K_LAUNCH((k_smax_col<MODE, true>), dim3(g), dim3(BLK), 0, hs, X, O, Wk, p);
-        else     T4K_LAUNCH((k_smax_col<MODE, false>), dim3(g), dim3(BLK), 0, hs, X, O, Wk, p);
-    } else {
-        if (vec) T4K_LAUNCH((k_smax_row<MODE, true>), dim3(g), dim3(BLK), 0, hs, X, O, Wk, p);
-        else     T4K_LAUNCH((k_smax_row<MODE, false>), dim3(g), dim3(BLK), 0, hs, X, O, Wk, p);
-    }
+    with_flags([&](auto v) {
+        if constexpr (std::is_same<PlanT, ColPlan>::value) T4K_LAUNCH((k_smax_col<MODE, v.value>), dim3(g), dim3(BLK), 0, hs, X, O, Wk, p);
+        else                                               T4K_LAUNCH((k_smax_row<MODE, v.value>), dim3(g), dim3(BLK), 0, hs, X, O, Wk, p);
+    }, vec);
 }
 template <typename PlanT>
 void run(const Plan &P, const PlanT &p, long nout, long os, long ps, const float *X, float *O, hipStream_t hs) {
-    if (P.regime == 0) { launch<M_REG>(P.col, P.vec, X, O, nullptr, p, hs); return; }
-    if (P.regime == 1) { launch<M_ONLINE>(P.col, P.vec, X, O, nullptr, p, hs); return; }
+    if (P.regime == 0) { launch<M_REG>(P.vec, X, O, nullptr, p, hs); return; }
+    if (P.regime == 1) { launch<M_ONLINE>(P.vec, X, O, nullptr, p, hs); return; }
     float *part = ws_for(hs), *fin = part + 2 * nout * (long)p.S;            // S pairs per group, then the merged pair of every group
-    launch<M_PART>(P.col, P.vec, X, O, part, p, hs);
+    launch<M_PART>(P.vec, X, O, part, p, hs);
     const unsigned g = log2_ceil(p.S, 6);
     const int grid = (int)std::min(ceil_div(nout, BLK >> g), (long)MAX_WG);
     T4K_LAUNCH(k_smax_merge, dim3(grid), dim3(BLK), 0, hs, part, fin, nout, p.S, os, ps, g);
-    launch<M_NORM>(P.col, P.vec, X, O, fin, p, hs);
+    launch<M_NORM>(P.vec, X, O, fin, p, hs);
 }
 
 } // namespace
@@ -506,8 +404,10 @@ extern "C" {
 
 int t4k_softmax_axes(const float *src, float *dst, const int dim[4], int mask, t4k_stream_t s) {
     T4K_REQUIRE_INIT();
-    int rc = check_args(src, dst, dim, mask, true, "t4k_softmax_axes"); if (rc != T4K_OK) return rc;
-    Plan P;
+    if (!src || !dst) return fail(T4K_ERR_ARG, "t4k_softmax_axes: null");
+    long total; Plan P;
+    int rc = check_axes(dim, mask, "t4k_softmax_axes", &total); if (rc != T4K_OK) return rc;
+    if (src != dst && src < dst + total && dst < src + total) return fail(T4K_ERR_ARG, "t4k_softmax_axes: dst overlaps src");
     rc = make_plan(P, dim, mask, aligned16(src) && aligned16(dst), "t4k_softmax_axes"); if (rc != T4K_OK) return rc;
     if (P.col) run(P, P.cl, P.cl.nout, 1, P.cl.nout, src, dst, S(s));        // pairs laid out [S, groups]
     else       run(P, P.row, P.row.nout, (long)P.row.S, 1, src, dst, S(s));  // a row of S pairs per group
@@ -517,8 +417,8 @@ int t4k_softmax_axes(const float *src, float *dst, const int dim[4], int mask, t
 int t4k_softmax_axes_plan(const int dim[4], int mask, int aligned, int out[6]) {
     T4K_REQUIRE_INIT();
     if (!out) return fail(T4K_ERR_ARG, "t4k_softmax_axes_plan: null");
-    int rc = check_args(nullptr, nullptr, dim, mask, false, "t4k_softmax_axes_plan"); if (rc != T4K_OK) return rc;
-    Plan P;
+    long total; Plan P;
+    int rc = check_axes(dim, mask, "t4k_softmax_axes_plan", &total); if (rc != T4K_OK) return rc;
     rc = make_plan(P, dim, mask, aligned != 0, "t4k_softmax_axes_plan"); if (rc != T4K_OK) return rc;
     out[0] = P.col ? 1 : 0; out[1] = P.regime; out[2] = P.vec ? 1 : 0;
     out[3] = P.col ? (int)P.cl.sx : (int)P.row.shift;

@@ -1,6 +1,7 @@
 // t4k_common.h - shared internals of libt4hip.so (gfx950 only; wave = 64 lanes).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <float.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -163,6 +164,20 @@ __device__ __forceinline__ float wave_min_all(float v) {
     for (int off = 32; off > 0; off >>= 1) v = fminf(v, __shfl_xor(v, off, 64));
     return v;
 }
+// the reductions of reduce.hip and reduce_axes.hip: a lane starts from r_init, takes r_term of every element (x; y = the target of the
+// binary cross-entropy, avg = the centre the n*variance subtracts) and joins partial results with r_comb
+enum { R_SUM = 0, R_NVAR, R_MAX, R_MIN, R_BCE };
+template <int OP> __device__ __forceinline__ float r_init() {
+    return OP == R_MAX ? -FLT_MAX : (OP == R_MIN ? FLT_MAX : 0.0f);
+}
+template <int OP> __device__ __forceinline__ float r_comb(float a, float b) {
+    return OP == R_MAX ? fmaxf(a, b) : (OP == R_MIN ? fminf(a, b) : a + b);
+}
+template <int OP> __device__ __forceinline__ float r_term(float x, float y, float avg) {
+    if (OP == R_NVAR) { float d = x - avg; return d * d; }
+    if (OP == R_BCE)  return y * __logf(x + DU_EPS) + (1.0f - y) * __logf(1.0f - x + DU_EPS);  // x = O, y = T
+    return x;
+}
 // block-wide sum for BLK=256 (4 waves); result valid in every thread
 __device__ __forceinline__ float block_sum(float v, float *smem4) {
     v = wave_sum_all(v);
@@ -188,6 +203,12 @@ __device__ __forceinline__ void split3(long p, int W, int H, int &j, int &i, int
 __device__ __forceinline__ void split2(long p, int C, int &c, long &rest) {
     if (p < 0x7fffffffL) { const unsigned q = (unsigned)p, t = q / (unsigned)C; c = (int)(q - t * (unsigned)C); rest = (long)t; }
     else { const long t = p / C; c = (int)(p - t * C); rest = t; }
+}
+// x = q * d + rem for any d below 2^32, the 32-bit divide whenever x fits (every tensor below 16 GiB).  For a division per workgroup
+// iteration or per output, never per element.
+__device__ __forceinline__ void divmod(long x, unsigned d, long &q, unsigned &rem) {
+    if (x < 0xffffffffL) { const unsigned v = (unsigned)x, t = v / d; rem = v - t * d; q = (long)t; }
+    else { const long t = x / (long)d; rem = (unsigned)(x - t * (long)d); q = t; }
 }
 
 // Philox4x32-10; counter = element_index/4, key = seed (same definition as the oracle)

@@ -322,37 +322,49 @@ Tensor &Tensor::ten_bcast(int op, Tensor &A, Tensor &B, Tensor &O) {
     if (Tb) Store::get().free(*Tb);
     return O;
 }
+// The walk of the two fallbacks below, over a C-ABI without the axis entries (the CPU oracle): T is viewed as (N,H,W,C); for every index of
+// the unmasked axes, in output order, the elements along the masked axes (one group) are gathered into a temporary row with t4k_copy - the
+// trailing masked axes are one contiguous copy - and f(row, elements, group index) runs; with `back` the row is then copied to where it came from.
+template <typename F>
+static void for_each_group(Tensor &T, int mask, bool back, F f) {
+    long e[4]; nhwc_of(T, e);
+    bool red[4]; long str[4], d = 1, cnt = 1;
+    for (int i = 3; i >= 0; i--) { red[i] = (mask & (8 >> i)) != 0; str[i] = d; d *= e[i]; if (red[i]) cnt *= e[i]; }
+    int tail = 4; long run = 1;                          // the trailing masked axes are one contiguous run
+    while (tail > 0 && (red[tail - 1] || e[tail - 1] == 1)) { run *= e[tail - 1]; tail--; }
+    Tensor &tmp = Store::get().tensor((uint64_t)cnt);
+    long k[4], r[4], o = 0, Rn[4];                       // k: the group's index, r: the masked axes' (both 0 where the other walks)
+    const long K[4] = { red[0] ? 1 : e[0], red[1] ? 1 : e[1], red[2] ? 1 : e[2], red[3] ? 1 : e[3] };
+    for (int i = 0; i < 4; i++) Rn[i] = (i < tail && red[i]) ? e[i] : 1;
+    for (k[0] = 0; k[0] < K[0]; k[0]++) for (k[1] = 0; k[1] < K[1]; k[1]++) for (k[2] = 0; k[2] < K[2]; k[2]++) for (k[3] = 0; k[3] < K[3]; k[3]++, o++)
+        for (int pass = 0; pass < (back ? 2 : 1); pass++) {   // gather, f, scatter
+            long at = 0;
+            for (r[0] = 0; r[0] < Rn[0]; r[0]++) for (r[1] = 0; r[1] < Rn[1]; r[1]++) for (r[2] = 0; r[2] < Rn[2]; r[2]++) for (r[3] = 0; r[3] < Rn[3]; r[3]++, at += run) {
+                long off = 0;
+                for (int i = 0; i < 4; i++) off += (k[i] + r[i]) * str[i];
+                if (pass) chk(t4k_copy(tmp.data + at, T.data + off, run, stream()), "copy");
+                else      chk(t4k_copy(T.data + off, tmp.data + at, run, stream()), "copy");
+            }
+            if (!pass) f(tmp.data, cnt, o);
+        }
+    Store::get().free(tmp);
+}
 // Axis reductions (beyond the reference, whose sum / avg / std / norm fold a whole tensor: tensor.cu:224-250): T is viewed
 // as (N,H,W,C) - a matrix (1,H,W,1), a vector the column (1,K,1,1) - and R has T's rank with every masked axis at extent 1.  One
 // t4k_reduce_axes launch (two for few outputs behind long reductions) plus the element-wise sqrt / division of the word: a count
 // that no extent changes, and no scalar is read back.  The symbol is referenced weakly: over a C-ABI without it (the CPU oracle)
-// every output element gathers what it folds into a temporary with t4k_copy and takes one t4k_reduce written straight to its place.
+// every output element gathers what it folds (for_each_group) and takes one t4k_reduce written straight to its place.
 #pragma weak t4k_reduce_axes
 static void reduce_into(int red_op, Tensor &T, int mask, Tensor *center, Tensor &R) {
-    long e[4]; nhwc_of(T, e);
     if (t4k_reduce_axes) {
+        long e[4]; nhwc_of(T, e);
         const int dim[4] = { (int)e[0], (int)e[1], (int)e[2], (int)e[3] };
         chk(t4k_reduce_axes(red_op, T.data, R.data, dim, mask, center ? center->data : nullptr, stream()), "reduce_axes");
         return;
     }
-    bool red[4]; long str[4], d = 1, cnt = 1;
-    for (int i = 3; i >= 0; i--) { red[i] = (mask & (8 >> i)) != 0; str[i] = d; d *= e[i]; if (red[i]) cnt *= e[i]; }
-    int tail = 4; long run = 1;                          // the trailing reduced axes are one contiguous run
-    while (tail > 0 && (red[tail - 1] || e[tail - 1] == 1)) { run *= e[tail - 1]; tail--; }
-    Tensor &tmp = Store::get().tensor((uint64_t)cnt);
-    long k[4], r[4], o = 0;                              // k: the output's index, r: the reduced axes' (both 0 where the other walks)
-    const long K[4] = { red[0] ? 1 : e[0], red[1] ? 1 : e[1], red[2] ? 1 : e[2], red[3] ? 1 : e[3] };
-    for (k[0] = 0; k[0] < K[0]; k[0]++) for (k[1] = 0; k[1] < K[1]; k[1]++) for (k[2] = 0; k[2] < K[2]; k[2]++) for (k[3] = 0; k[3] < K[3]; k[3]++, o++) {
-        long Rn[4], at = 0;
-        for (int i = 0; i < 4; i++) Rn[i] = (i < tail && red[i]) ? e[i] : 1;
-        for (r[0] = 0; r[0] < Rn[0]; r[0]++) for (r[1] = 0; r[1] < Rn[1]; r[1]++) for (r[2] = 0; r[2] < Rn[2]; r[2]++) for (r[3] = 0; r[3] < Rn[3]; r[3]++, at += run) {
-            long off = 0;
-            for (int i = 0; i < 4; i++) off += (k[i] + r[i]) * str[i];
-            chk(t4k_copy(T.data + off, tmp.data + at, run, stream()), "copy");
-        }
-        chk(t4k_reduce(red_op, tmp.data, cnt, center ? center->get((uint64_t)o) : 0.0f, R.data + o, stream()), "reduce");
-    }
-    Store::get().free(tmp);
+    for_each_group(T, mask, false, [&](float *row, long cnt, long o) {
+        chk(t4k_reduce(red_op, row, cnt, center ? center->get((uint64_t)o) : 0.0f, R.data + o, stream()), "reduce");
+    });
 }
 Tensor &Tensor::reduce_axes(int word, Tensor &T, int mask) {
     long e[4], cnt = 1; nhwc_of(T, e);
@@ -378,37 +390,17 @@ Tensor &Tensor::reduce_axes(int word, Tensor &T, int mask) {
 // Axis softmax (beyond the reference, whose `softmax` word treats the whole tensor as one distribution: netvm.cpp:36-39):
 // T, viewed as (N,H,W,C) like the axis reductions above, is rewritten in place - for every index of the unmasked axes the elements along
 // the masked axes become exp(x - max) / sum exp(x - max).  One t4k_softmax_axes call, nothing read back.  The symbol is referenced
-// weakly: over a C-ABI without it (the CPU oracle) every group is gathered into a temporary row with t4k_copy (the trailing masked axes
-// are one contiguous copy), taken through t4k_softmax(tmp, tmp, 1, len) and copied back.
+// weakly: over a C-ABI without it (the CPU oracle) every group is gathered into a temporary row (for_each_group), taken through
+// t4k_softmax(row, row, 1, len) and copied back.
 #pragma weak t4k_softmax_axes
 void Tensor::softmax_axes(Tensor &T, int mask) {
-    long e[4]; nhwc_of(T, e);
     if (t4k_softmax_axes) {
+        long e[4]; nhwc_of(T, e);
         const int dim[4] = { (int)e[0], (int)e[1], (int)e[2], (int)e[3] };
         chk(t4k_softmax_axes(T.data, T.data, dim, mask, stream()), "softmax_axes");
         return;
     }
-    bool red[4]; long str[4], d = 1, cnt = 1;
-    for (int i = 3; i >= 0; i--) { red[i] = (mask & (8 >> i)) != 0; str[i] = d; d *= e[i]; if (red[i]) cnt *= e[i]; }
-    int tail = 4; long run = 1;                          // the trailing masked axes are one contiguous run
-    while (tail > 0 && (red[tail - 1] || e[tail - 1] == 1)) { run *= e[tail - 1]; tail--; }
-    Tensor &tmp = Store::get().tensor((uint64_t)cnt);
-    long k[4], r[4];                                     // k: the group's index, r: the masked axes' (both 0 where the other walks)
-    const long K[4] = { red[0] ? 1 : e[0], red[1] ? 1 : e[1], red[2] ? 1 : e[2], red[3] ? 1 : e[3] };
-    long Rn[4];
-    for (int i = 0; i < 4; i++) Rn[i] = (i < tail && red[i]) ? e[i] : 1;
-    for (k[0] = 0; k[0] < K[0]; k[0]++) for (k[1] = 0; k[1] < K[1]; k[1]++) for (k[2] = 0; k[2] < K[2]; k[2]++) for (k[3] = 0; k[3] < K[3]; k[3]++)
-        for (int back = 0; back < 2; back++) {           // gather, softmax, scatter
-            long at = 0;
-            for (r[0] = 0; r[0] < Rn[0]; r[0]++) for (r[1] = 0; r[1] < Rn[1]; r[1]++) for (r[2] = 0; r[2] < Rn[2]; r[2]++) for (r[3] = 0; r[3] < Rn[3]; r[3]++, at += run) {
-                long off = 0;
-                for (int i = 0; i < 4; i++) off += (k[i] + r[i]) * str[i];
-                if (back) chk(t4k_copy(tmp.data + at, T.data + off, run, stream()), "copy");
-                else      chk(t4k_copy(T.data + off, tmp.data + at, run, stream()), "copy");
-            }
-            if (!back) chk(t4k_softmax(tmp.data, tmp.data, 1, (int)cnt, stream()), "softmax");
-        }
-    Store::get().free(tmp);
+    for_each_group(T, mask, true, [&](float *row, long cnt, long) { chk(t4k_softmax(row, row, 1, (int)cnt, stream()), "softmax"); });
 }
 Tensor &Tensor::mm(Tensor &A, Tensor &B, Tensor &O, bool inc, bool tA, bool tB) {   // Tensor::mm/gemm3 tensor.cu:73-77,161-180
     const uint32_t H = tA ? A.W() : A.H(), W = tB ? B.H() : B.W();
