@@ -406,7 +406,10 @@ int t4k_linear_fwd(const float *X, const float *W, const float *B, float *Y,
  * Absent stages have layer == T4K_L_NONE (KS must be 1 when there is no pooling stage).  The post stage may also be a dropout layer
  * (`leakyrelu dropout`, `maxpool dropout`) when the pre stage is not one: it draws the slice t4k_dropout_mask would draw for post_mask.  Every tensor the
  * separate layers write (_factivate forward.cu:200-209, _fpool :211-227, flatten copy :96) is written with
- * identical values; a dropout pre-stage draws the Philox slice t4k_rand would have drawn for its mask. */
+ * identical values; a dropout pre-stage draws the Philox slice t4k_rand would have drawn for its mask.
+ * H0 x W0 is the pooled grid.  On a ceil grid the edge windows are clipped as t4k_pool clips them (max / min over the cells that exist, avg still
+ * divides by KS^2).  On a floor grid over an extent that is no multiple of KS some rows / columns belong to no window: the pool stage leaves them alone
+ * both ways (the backward keeps the forward values there, as t4k_dpool does), the stages in front of the pool cover their whole tensors. */
 typedef struct t4k_poolblock {
     int    pre_layer;  float pre_alpha;  float *pre_mask;  float *pre_out;
     int    pool_layer; int KS;           float *pool_out;

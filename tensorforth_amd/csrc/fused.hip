@@ -40,8 +40,29 @@ template <int VW> __device__ __forceinline__ void vstore(float *p, const Vec<VW>
     else              *p = r.v[0];
 }
 
-// BN: the run is preceded by the apply half of a batch-norm layer (statistics already finalised in bnS: [0, C) 1 / sigma, [C, 2C) mean): every element of X
-// is read ONCE, x-hat and the batch-norm output are written as k_bn_apply writes them (same expressions), and the run goes on from the value in registers.
+// The element-wise head of the run at element a (channel c, VW channels): the batch-norm apply (BN) and the pre stage, stored as the separate layers store
+// them; returns the value the pool reads.  BN: the run is preceded by the apply half of a batch-norm layer (statistics already finalised in bnS: [0, C) 1 / sigma,
+// [C, 2C) mean): every element of X is read ONCE, x-hat and the batch-norm output are written as k_bn_apply writes them (same expressions), and the run goes on
+// from the value in registers.
+template <int VW, bool BN>
+__device__ __forceinline__ Vec<VW> head_cell(const PB &p, long a, int c, bool draw, uint64_t base, uint64_t seed) {
+    Vec<VW> e = vload<VW>(p.X + a);
+    if (BN) {
+        Vec<VW> xh;
+#pragma unroll
+        for (int q = 0; q < VW; q++) { xh.v[q] = (e.v[q] - p.bnS[p.C + c + q]) * p.bnS[c + q]; e.v[q] = xh.v[q] * p.bnW[c + q] + p.bnB[c + q]; }
+        vstore<VW>(p.XH + a, xh); vstore<VW>(p.BO + a, e);
+    }
+    if (p.pre) {
+        Vec<VW> o, f;
+        uint32_t r[4] = {0, 0, 0, 0};
+        if (draw) philox4x32_10(base + (uint64_t)(a >> 2), seed, r);   // a .. a+VW-1 sit in one counter block
+#pragma unroll
+        for (int q = 0; q < VW; q++) act_rt(p.pre, e.v[q], draw ? u01(r[(a + q) & 3]) : 0.f, p.a_pre, o.v[q], f.v[q]);
+        vstore<VW>(p.Fpre + a, f); vstore<VW>(p.P + a, o); e = o;
+    }
+    return e;
+}
 template <int KS, int VW, bool BN = false>
 __global__ void __launch_bounds__(BLK) k_poolblock_fwd(PB p) {
     const int CV = p.C / VW;
@@ -62,21 +83,7 @@ __global__ void __launch_bounds__(BLK) k_poolblock_fwd(PB p) {
                 const int gi = i0 * KS + y, gj = j0 * KS + x;
                 if (gi >= p.H1 || gj >= p.W1) continue;
                 const long a = (((long)n * p.H1 + gi) * p.W1 + gj) * p.C + c;
-                Vec<VW> e = vload<VW>(p.X + a);
-                if (BN) {
-                    Vec<VW> xh;
-#pragma unroll
-                    for (int q = 0; q < VW; q++) { xh.v[q] = (e.v[q] - p.bnS[p.C + c + q]) * p.bnS[c + q]; e.v[q] = xh.v[q] * p.bnW[c + q] + p.bnB[c + q]; }
-                    vstore<VW>(p.XH + a, xh); vstore<VW>(p.BO + a, e);
-                }
-                if (p.pre) {
-                    Vec<VW> o, f;
-                    uint32_t r[4] = {0, 0, 0, 0};
-                    if (draw) philox4x32_10(base + (uint64_t)(a >> 2), seed, r);   // a .. a+VW-1 sit in one counter block
-#pragma unroll
-                    for (int q = 0; q < VW; q++) act_rt(p.pre, e.v[q], draw ? u01(r[(a + q) & 3]) : 0.f, p.a_pre, o.v[q], f.v[q]);
-                    vstore<VW>(p.Fpre + a, f); vstore<VW>(p.P + a, o); e = o;
-                }
+                const Vec<VW> e = head_cell<VW, BN>(p, a, c, draw, base, seed);
 #pragma unroll
                 for (int q = 0; q < VW; q++) {
                     if (p.pool == T4K_L_MAXPOOL)      acc.v[q] = first ? e.v[q] : fmaxf(e.v[q], acc.v[q]);
@@ -179,6 +186,39 @@ __global__ void __launch_bounds__(BLK) k_poolblock_bwd(PBB p) {
     }
 }
 
+// A floor grid on an extent that is no multiple of KS leaves rows / columns of the H1 x W1 tensor that no window visits.  The pool and its scatter leave those
+// cells alone; the element-wise stages in front own EVERY element of their tensors, as the separate layers do.  The host never builds such a run (it fuses a
+// pool only where KS divides the extent), so these cells get a small launch of their own beside the run's and the run's kernels stay as they are.
+inline bool unvisited_cells(int KS, int H1, int W1, int H0, int W0) { return KS > 1 && (H0 * KS < H1 || W0 * KS < W1); }
+// forward: the head of the run on the unvisited cells; launched BEFORE k_poolblock_fwd, which moves a captured dropout stream on when it ends
+template <int VW, bool BN>
+__global__ void __launch_bounds__(BLK) k_poolblock_fwd_rest(PB p, int Hv, int Wv) {
+    const int CV = p.C / VW;
+    const long cells = (long)p.N * p.H1 * p.W1 * CV;
+    uint64_t base = 0, seed = 0;
+    const bool draw = p.pre == T4K_L_DROPOUT;
+    if (draw) rng_begin(p.rng, base, seed);
+    for (long z = (long)blockIdx.x * blockDim.x + threadIdx.x; z < cells; z += (long)gridDim.x * blockDim.x) {
+        int c, gj, gi, n; long t; split2(z, CV, c, t); c *= VW; split3(t, p.W1, p.H1, gj, gi, n);
+        if (gi < Hv && gj < Wv) continue;
+        head_cell<VW, BN>(p, z * VW, c, draw, base, seed);
+    }
+}
+// backward: the pre stage's mask multiply there - the pool input buffer still holds its forward values
+template <int VW>
+__global__ void __launch_bounds__(BLK) k_poolblock_bwd_rest(PBB p, int Hv, int Wv) {
+    const int CV = p.C / VW;
+    const long cells = (long)p.N * p.H1 * p.W1 * CV;
+    for (long z = (long)blockIdx.x * blockDim.x + threadIdx.x; z < cells; z += (long)gridDim.x * blockDim.x) {
+        int c, gj, gi, n; long t; split2(z, CV, c, t); split3(t, p.W1, p.H1, gj, gi, n);
+        if (gi < Hv && gj < Wv) continue;
+        Vec<VW> d = vload<VW>(p.Pb + z * VW); const Vec<VW> f = vload<VW>(p.Fpre + z * VW);
+#pragma unroll
+        for (int q = 0; q < VW; q++) d.v[q] *= f.v[q];
+        vstore<VW>(p.Xb + z * VW, d);
+    }
+}
+
 bool is_act(int l)  { return l == T4K_L_RELU || l == T4K_L_TANH || l == T4K_L_SIGMOID || l == T4K_L_SELU || l == T4K_L_LEAKYRL || l == T4K_L_ELU || l == T4K_L_DROPOUT; }
 bool is_pool(int l) { return l == T4K_L_AVGPOOL || l == T4K_L_MAXPOOL || l == T4K_L_MINPOOL; }
 
@@ -230,6 +270,14 @@ static int poolblock_fwd_impl(const float *X, const t4k_poolblock *b, int N, int
     const long nthr = total / VW;
     const int bs = (nthr < (long)BLK * 2 * st().cu_count) ? 64 : BLK;      // small runs: one-wave workgroups reach every CU
     const dim3 grid((unsigned)std::min<long>((nthr + bs - 1) / bs, 8192)), blk(bs);
+    if ((XH || b->pre_layer) && unvisited_cells(b->KS, H1, W1, H0, W0)) {
+        const dim3 rgrid((unsigned)grid_for((long)N * H1 * W1 * C / VW));
+#define PBR_(BN_) do { if (VW == 4) T4K_LAUNCH((k_poolblock_fwd_rest<4, BN_>), rgrid, dim3(BLK), 0, S(s), p, H0 * b->KS, W0 * b->KS); \
+                       else if (VW == 2) T4K_LAUNCH((k_poolblock_fwd_rest<2, BN_>), rgrid, dim3(BLK), 0, S(s), p, H0 * b->KS, W0 * b->KS); \
+                       else T4K_LAUNCH((k_poolblock_fwd_rest<1, BN_>), rgrid, dim3(BLK), 0, S(s), p, H0 * b->KS, W0 * b->KS); } while (0)
+        if (XH) PBR_(true); else PBR_(false);
+#undef PBR_
+    }
 #define PBF_(KS_, BN_) do { if (VW == 4) T4K_LAUNCH((k_poolblock_fwd<KS_, 4, BN_>), grid, blk, 0, S(s), p); \
                             else if (VW == 2) T4K_LAUNCH((k_poolblock_fwd<KS_, 2, BN_>), grid, blk, 0, S(s), p); \
                             else T4K_LAUNCH((k_poolblock_fwd<KS_, 1, BN_>), grid, blk, 0, S(s), p); } while (0)
@@ -255,7 +303,7 @@ int t4k_poolblock_bwd(const float *DY, float *X, const t4k_poolblock *b, int N, 
     if (!DY || !X) return fail(T4K_ERR_ARG, "t4k_poolblock_bwd: null tensor");
     const long total = (long)N * H0 * W0 * C; if (total <= 0) return T4K_OK;
     PBB p;
-    p.DY = DY; p.Rb = b->copy_out ? (b->post_layer ? b->post_out : (b->pool_layer ? b->pool_out : b->pre_out)) : nullptr;
+    p.DY = DY; p.Rb = b->copy_out ? (b->post_layer ? b->post_out : (b->pool_layer ? b->pool_out : (b->pre_layer ? b->pre_out : X))) : nullptr;   // flatten-only run: the copy's input IS X
     p.Qb = b->pool_layer ? b->pool_out : (b->pre_layer ? b->pre_out : X);   // buffer the post activation read its input from
     p.Pb = b->pre_layer ? b->pre_out : X;                         // pool input buffer (forward values -> dX in place)
     p.Xb = X; p.Fpre = b->pre_mask; p.Fpost = b->post_mask;
@@ -270,6 +318,12 @@ int t4k_poolblock_bwd(const float *DY, float *X, const t4k_poolblock *b, int N, 
                        else T4K_LAUNCH((k_poolblock_bwd<KS_, 1>), grid, blk, 0, S(s), p); } while (0)
     switch (b->KS) { case 1: PBB_(1); break; case 2: PBB_(2); break; default: PBB_(3); break; }
 #undef PBB_
+    if (b->pre_layer && unvisited_cells(b->KS, H1, W1, H0, W0)) {
+        const dim3 rgrid((unsigned)grid_for((long)N * H1 * W1 * C / VW));
+        if (VW == 4) T4K_LAUNCH((k_poolblock_bwd_rest<4>), rgrid, dim3(BLK), 0, S(s), p, H0 * b->KS, W0 * b->KS);
+        else if (VW == 2) T4K_LAUNCH((k_poolblock_bwd_rest<2>), rgrid, dim3(BLK), 0, S(s), p, H0 * b->KS, W0 * b->KS);
+        else T4K_LAUNCH((k_poolblock_bwd_rest<1>), rgrid, dim3(BLK), 0, S(s), p, H0 * b->KS, W0 * b->KS);
+    }
     T4K_LAUNCH_CHECK(); return T4K_OK;
 }
 

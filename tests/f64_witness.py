@@ -212,32 +212,68 @@ def act_from(kind, x, alpha, mask):
     return act(kind, x, alpha)[0]
 
 
-def pool(kind, x, KS=2):
-    """2x2 (KSxKS) pool of NHWC x: max / min exact, avg = sum of KS^2 terms (KS^2 - 1 roundings) / KS^2 (exact for KS = 2)"""
-    x = f64(x); N, H, Wd, C = x.shape; H0, W0 = H // KS, Wd // KS
-    t = x[:, :H0 * KS, :W0 * KS].reshape(N, H0, KS, W0, KS, C)
+def _windows(x, KS, H0, W0):
+    """the pool windows of NHWC x on an H0 x W0 grid in scan order, [N, H0, W0, C, KS * KS], and which of their cells exist,
+    [1, H0, W0, 1, KS * KS]: a ceil grid (H0 = ceil(H / KS)) clips its edge windows at the tensor's border, as k_pool does"""
+    N, H, Wd, C = x.shape; Hp, Wp = H0 * KS, W0 * KS
+    assert 0 < H0 <= -(-H // KS) and 0 < W0 <= -(-Wd // KS), "a window without a cell"
+    xp = np.zeros((N, max(Hp, H), max(Wp, Wd), C)); xp[:, :H, :Wd] = x
+    ok = np.zeros((max(Hp, H), max(Wp, Wd)), bool); ok[:H, :Wd] = True
+    t = xp[:, :Hp, :Wp].reshape(N, H0, KS, W0, KS, C).transpose(0, 1, 3, 5, 2, 4).reshape(N, H0, W0, C, KS * KS)
+    m = ok[:Hp, :Wp].reshape(H0, KS, W0, KS).transpose(0, 2, 1, 3).reshape(1, H0, W0, 1, KS * KS)
+    return t, m
+
+
+def _unwindow(o, KS, H, Wd):
+    """inverse of _windows: [N, H0, W0, C, KS * KS] back onto the H x Wd grid (cells no window holds: 0)"""
+    N, H0, W0, C, _ = o.shape; Hp, Wp = H0 * KS, W0 * KS
+    out = np.zeros((N, max(Hp, H), max(Wp, Wd), C), o.dtype)
+    out[:, :Hp, :Wp] = o.reshape(N, H0, W0, C, KS, KS).transpose(0, 1, 4, 2, 5, 3).reshape(N, Hp, Wp, C)
+    return out[:, :H, :Wd]
+
+
+def pool(kind, x, KS=2, H0=None, W0=None):
+    """KSxKS pool of NHWC x on an H0 x W0 grid (default: the floor grid H // KS): max / min exact, over the cells that exist; avg = sum of
+    the existing cells (KS^2 - 1 roundings) / KS^2 - ALWAYS KS^2, also in a clipped edge window, as k_pool divides (exact for KS = 2).
+    usample = avg: the up-sample layer's backward is k_pool's L_USAMPLE case, which shares the L_AVGPOOL arithmetic (division included)."""
+    x = f64(x); N, H, Wd, C = x.shape
+    H0 = H // KS if H0 is None else H0; W0 = Wd // KS if W0 is None else W0
+    t, m = _windows(x, KS, H0, W0)
     if kind == "max":
-        return W(t.max((2, 4)), 0.0, 0)
+        return W(np.where(m, t, -np.inf).max(-1), 0.0, 0)
     if kind == "min":
-        return W(t.min((2, 4)), 0.0, 0)
-    if kind == "avg":
-        return W(t.mean((2, 4)), np.abs(t).mean((2, 4)), KS * KS, 1.0)
+        return W(np.where(m, t, np.inf).min(-1), 0.0, 0)
+    if kind in ("avg", "usample"):
+        return W((t * m).sum(-1) / (KS * KS), (np.abs(t) * m).sum(-1) / (KS * KS), KS * KS, 1.0)
     raise ValueError(kind)
 
 
-def dpool(kind, dy, x, KS=2):
-    """k_dpool: avg spreads dy / KS^2 to every cell (exact for KS = 2); max / min route dy to the FIRST extreme cell of the window in scan
-    order, every other cell 0.  x = the pool's forward input (its stored values decide the routing)."""
-    dy = f64(dy); x = f64(x); N, H, Wd, C = x.shape; H0, W0 = H // KS, Wd // KS
-    out = np.zeros_like(x)
-    if kind == "avg":
-        out[:, :H0 * KS, :W0 * KS] = np.repeat(np.repeat(dy / (KS * KS), KS, 1), KS, 2)
-        return W(out, 0.0, 0)
-    t = x[:, :H0 * KS, :W0 * KS].reshape(N, H0, KS, W0, KS, C).transpose(0, 1, 3, 5, 2, 4).reshape(N, H0, W0, C, KS * KS)
-    k = (t.argmax(-1) if kind == "max" else t.argmin(-1))      # argmax / argmin return the first extreme: the reference's strict compare
-    o = np.zeros((N, H0, W0, C, KS * KS)); np.put_along_axis(o, k[..., None], dy[..., None], -1)
-    out[:, :H0 * KS, :W0 * KS] = o.reshape(N, H0, W0, C, KS, KS).transpose(0, 1, 4, 2, 5, 3).reshape(N, H0 * KS, W0 * KS, C)
-    return W(out, 0.0, 0)
+def dpool(kind, dy, x, KS=2, H0=None, W0=None, keep=None):
+    """k_dpool on an H0 x W0 grid (default: the floor grid): avg spreads dy / KS^2 to every cell of the window (exact for KS = 2, one rounding for KS = 3), usample
+    spreads dy undivided; max / min route dy to the FIRST extreme cell of the window in row-major scan order, every other cell of the window
+    0.  x = the pool's forward input (its stored values decide the routing).  Every cell some window holds is written and no other: the
+    witness carries that as `.written` ([N, H, W, C] bool).  The kernels work in place on the forward buffer, so the cells NO window visits
+    (the last rows / columns of a floor grid on a non-multiple extent) keep what the buffer held - pass it as `keep` to have the witness say
+    so; without it those cells are 0 (the callers with H % KS == 0 never see the difference)."""
+    dy = f64(dy); x = f64(x); N, H, Wd, C = x.shape
+    H0 = H // KS if H0 is None else H0; W0 = Wd // KS if W0 is None else W0
+    dy = dy.reshape(N, H0, W0, C)
+    t, m = _windows(x, KS, H0, W0)
+    if kind in ("avg", "usample"):
+        o = np.broadcast_to((dy / (KS * KS) if kind == "avg" else dy)[..., None], t.shape) * m
+    elif kind in ("max", "min"):
+        k = np.where(m, t, -np.inf).argmax(-1) if kind == "max" else np.where(m, t, np.inf).argmin(-1)   # the first extreme: the reference's strict compare
+        o = np.zeros(t.shape); np.put_along_axis(o, k[..., None], dy[..., None], -1)
+    else:
+        raise ValueError(kind)
+    written = _unwindow(np.ascontiguousarray(np.broadcast_to(m, t.shape)), KS, H, Wd)
+    out = _unwindow(o, KS, H, Wd)
+    if keep is not None:
+        out = np.where(written, out, f64(keep).reshape(x.shape))
+    # avg at KS = 3: dy / 9 is one rounding (the division by 4 of KS = 2 is exact, as is every routing)
+    w = W(out, np.abs(out) * written, 1, 1.0) if kind == "avg" and KS * KS & (KS * KS - 1) else W(out, 0.0, 0)
+    w.written = written
+    return w
 
 
 def mul(g, m):

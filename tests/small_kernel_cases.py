@@ -34,6 +34,9 @@ OPT_CHUNKED_SIZES = (1, 1023, 1024, 1025, 3000)
 OPT_MULTI_SIZES = (7, 70001, 1024, 65537)
 LINALG_K = (1, 2, 5, 255, 256, 257, 300)
 LINALG_KINDS = ("dominant", "permuted", "cond1e4")
+RUN_MAX_GRID = 8192                         # fused.hip: t4k_poolblock_fwd / _bwd cap their grid here
+RUN_WAVE64_BELOW = BLK * 2                  # ... and take 64-thread workgroups below BLK * 2 threads per CU (512 x cu_count threads)
+RUN_CU = 256                                # the MI355X's CU count: the table below is sized for it
 DCONV_SHAPES = ((6, 4, 4, 12, 8), (2, 7, 7, 3, 4), (4, 8, 8, 64, 32), (3, 16, 16, 8, 1), (2, 5, 5, 32, 64), (2, 5, 8, 6, 3), (1, 9, 6, 16, 3))   # N, H1, W1, C1, C0
 
 
@@ -93,3 +96,73 @@ def softmax_rows(rng, N, C):
     if N > 3:
         Z[3] = -80.0
     return Z
+
+
+# ----------------------------------------------------------------------------- pool and fused element-wise runs (pool.hip, fused.hip)
+def ceil_div(a, b):
+    return -(-a // b)
+
+
+def run_vw(C, *ptrs):
+    """fused.hip vec_width: the widest of 4 / 2 / 1 channels per thread that divides C with EVERY tensor's base address a multiple of
+    4 * VW bytes (t4k_poolblock_bwd falls straight to 1 for a misaligned DY, the BN form for XH / O: see run_vw_bwd / run_vw_bn)"""
+    for vw in (4, 2):
+        if C % vw == 0 and all(q % (4 * vw) == 0 for q in ptrs):
+            return vw
+    return 1
+
+
+def run_vw_tail(vw, *ptrs):
+    """the second step of the backward (DY) and of the BN form (XH, O): a misaligned one of these drops the run to scalar at once"""
+    return vw if all(q % (4 * vw) == 0 for q in ptrs) else 1
+
+
+def run_plan(nthr, cu=RUN_CU):
+    """(workgroup size, grid, grid-stride trips of the longest thread, threads at work in the last trip) of a fused run of nthr threads"""
+    bs = 64 if nthr < RUN_WAVE64_BELOW * cu else BLK
+    grid = min(ceil_div(nthr, bs), RUN_MAX_GRID)
+    trips = ceil_div(nthr, grid * bs)
+    return bs, grid, trips, nthr - (trips - 1) * grid * bs
+
+
+def run_label(nthr, cu=RUN_CU):
+    bs, grid, trips, _ = run_plan(nthr, cu)
+    return "wave64" if bs == 64 and trips == 1 else "wg256" if bs == BLK and trips == 1 else "wg256_wrap" if bs == BLK else "wave64_wrap"
+
+
+def pool_plan(n):
+    """(grid, trips, threads at work in the last trip) of k_pool / k_dpool over n outputs: grid_for(n)"""
+    grid = min(ceil_div(n, BLK), MAX_WG)
+    trips = ceil_div(n, grid * BLK)
+    return grid, trips, n - (trips - 1) * grid * BLK
+
+
+class RunCase:
+    """one fused run: N images, pooled grid H0 x W0 (input grid H0 * KS x W0 * KS), C channels; `plan` / `vw` = what it is meant to hit"""
+
+    def __init__(self, plan, vw, N, H0, W0, C, KS, pool, why):
+        self.plan, self.vw, self.N, self.H0, self.W0, self.C, self.KS, self.pool, self.why = plan, vw, N, H0, W0, C, KS, pool, why
+        self.H1, self.W1 = H0 * KS, W0 * KS
+        self.nthr = N * H0 * W0 * C // vw
+        self.id = "%s-vw%d-N%d-%dx%d-C%d-KS%d" % (plan, vw, N, H0, W0, C, KS)
+
+
+RUN_CASES = (
+    RunCase("wave64", 4, 8, 32, 32, 60, 2, "max", "last 64-thread plan: 122 880 threads"),
+    RunCase("wg256", 4, 8, 32, 32, 64, 2, "max", "first 256-thread plan: 131 072 threads"),
+    RunCase("wave64", 2, 8, 32, 32, 30, 2, "max", "the same boundary at two channels per thread: 122 880"),
+    RunCase("wg256", 2, 8, 32, 32, 34, 2, "max", "... 139 264"),
+    RunCase("wave64", 1, 8, 32, 32, 15, 2, "max", "the same boundary at one channel per thread: 122 880"),
+    RunCase("wg256", 1, 8, 32, 32, 17, 2, "max", "... 139 264"),
+    RunCase("wg256_wrap", 1, 4, 64, 64, 129, 2, "max", "second grid-stride trip, ragged: 2 113 536 threads, 16 384 of them in trip two"),
+    RunCase("wg256_wrap", 1, 8, 64, 64, 65, 1, None, "the same without a pool: 2 129 920 threads, 32 768 in trip two"),
+)
+RUN_WRAP_THREADS = RUN_MAX_GRID * BLK       # 2 097 152: a run strides above
+
+# plain k_pool / k_dpool past MAX_WG workgroups with a clipped last window: N, H1, W1, C, KS (ceil grid)
+POOL_WRAP_CASES = ((3, 75, 75, 123, 2), (3, 113, 113, 123, 3))       # 3 x 38 x 38 x 123 = 532 836 outputs > 524 288 (8 548 in trip two)
+
+# the narrow-vector fallbacks at C = 8: a tensor that sits `off` bytes into its allocation -> the width the run must take
+RUN_TENSORS = ("X", "pre_mask", "pre_out", "pool_out", "post_mask", "post_out", "copy_out")
+RUN_MISALIGNED = tuple(("misaligned_%s" % t, t, off, vw) for t in RUN_TENSORS for off, vw in ((4, 1), (8, 2))) + \
+    tuple(("misaligned_%s" % t, t, off, 1) for t in ("DY", "XH", "O") for off in (4, 8))      # the second step drops to scalar, never to 2

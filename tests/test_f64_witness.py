@@ -510,3 +510,109 @@ def test_transposed_conv_witness(oracle, o, N, H1, W1, C1, C0):
         wt.check("dconv dX", DX, wdx); wt.check("dconv dF", DF, wdf); wt.check("dconv dB", DB, wdb)
     assert not passes(DF - DF0, wdf), "dF not accumulated"
     assert not passes(np.ascontiguousarray(DF[:, ::-1, ::-1, :]), wdf), "taps flipped"
+
+
+# ============================================================================= pools on clipped grids and the fused-run case table (tests/test_gpu_pool_runs_sweep.py)
+POOL_L = {"max": "L_MAXPOOL", "min": "L_MINPOOL", "avg": "L_AVGPOOL", "usample": "L_USAMPLE"}
+
+
+def _oracle_pool(oracle, o, kind, x, KS, H0, W0):
+    N, H, Wd, C = x.shape; q = np.zeros((N, H0, W0, C), np.float32)
+    assert o.t4o_pool(getattr(oracle, POOL_L[kind]), oracle.P(x), oracle.P(q), N, H, Wd, H0, W0, C, KS) == 0
+    return q
+
+
+def _oracle_dpool(oracle, o, kind, x, dy, KS, H0, W0):
+    N, H, Wd, C = x.shape; g = x.copy()
+    assert o.t4o_dpool(getattr(oracle, POOL_L[kind]), oracle.P(g), oracle.P(dy), N, H, Wd, H0, W0, C, KS) == 0
+    return g
+
+
+def _tied(rng, shape):
+    """integers in {-2 .. 2}: almost every window holds its extreme more than once"""
+    return rng.integers(-2, 3, shape).astype(np.float32)
+
+
+@pytest.mark.parametrize("kind", ["max", "min", "avg", "usample"])
+@pytest.mark.parametrize("KS", [2, 3])
+@pytest.mark.parametrize("H,Wd", [(7, 5), (8, 7)])
+def test_pool_witness_on_clipped_grids_holds_the_oracle_and_fails_the_defects(oracle, o, kind, KS, H, Wd):
+    rng = np.random.default_rng(70 + H * 10 + KS)
+    N, C = 2, 3; H0, W0 = -(-H // KS), -(-Wd // KS)                           # the ceil grid: the last window of a row / column is clipped
+    assert H0 * KS > H or W0 * KS > Wd
+    for x in (rng.standard_normal((N, H, Wd, C)).astype(np.float32), _tied(rng, (N, H, Wd, C))):
+        dy = (rng.integers(1, 4, (N, H0, W0, C)) * rng.choice((-1, 1), (N, H0, W0, C))).astype(np.float32)      # never 0: a misrouted dy always shows
+        q = _oracle_pool(oracle, o, kind, x, KS, H0, W0); w = wt.pool(kind, x, KS, H0, W0)
+        wt.check("pool %s" % kind, q, w)
+        g = _oracle_dpool(oracle, o, kind, x, dy, KS, H0, W0); wd = wt.dpool(kind, dy, x, KS, H0, W0, keep=x)
+        wt.check("dpool %s" % kind, g, wd)
+        assert wd.written.all()                                               # a ceil grid visits every cell
+        t, m = wt._windows(x.astype(np.float64), KS, H0, W0); cells = m.sum(-1)
+        if kind in ("avg", "usample"):
+            bad = ((t * m).sum(-1) / cells).astype(np.float32)               # divided by the cells that exist instead of KS^2
+            assert not passes(bad, w), "avg over the cell count"
+            assert passes(bad[:, :H // KS, :Wd // KS], wt.W(w.exact[:, :H // KS, :Wd // KS], w.mag[:, :H // KS, :Wd // KS], w.n, w.c))   # ... which only the clipped windows show
+        else:
+            key = np.where(m, t, -np.inf if kind == "max" else np.inf)
+            ext = key.max(-1, keepdims=True) if kind == "max" else key.min(-1, keepdims=True)
+            last = (KS * KS - 1) - np.argmax((key == ext)[..., ::-1], -1)     # the LAST extreme of the window
+            o_ = np.zeros(t.shape); np.put_along_axis(o_, last[..., None], dy.astype(np.float64)[..., None], -1)
+            bad = wt._unwindow(o_, KS, H, Wd)
+            if (key == ext).sum(-1).max() > 1:
+                assert not passes(bad, wd), "tie routed to the last extreme"
+            # a visited cell outside the arg-extreme keeps its forward value instead of 0
+            idx = np.argwhere((wd.exact == 0) & (x != 0))
+            assert len(idx); bad = g.copy(); bad[tuple(idx[0])] = x[tuple(idx[0])]
+            assert not passes(bad, wd), "cell outside the arg-extreme not zeroed"
+        # the cells of the clipped windows left holding their forward values (a kernel that skips partial windows)
+        full = wt._unwindow(np.ascontiguousarray(np.broadcast_to((cells == KS * KS)[..., None], t.shape)), KS, H, Wd)
+        bad = np.where(full, g, x)
+        assert not passes(bad, wd), "clipped cells left at their forward value"
+
+
+@pytest.mark.parametrize("kind", ["max", "min", "avg", "usample"])
+def test_pool_witness_floor_grid_keeps_the_unvisited_cells(oracle, o, kind):
+    """7 x 7 at KS = 2 on the floor grid 3 x 3: row 6 and column 6 belong to no window; k_dpool works in place, so they keep the forward value"""
+    rng = np.random.default_rng(75)
+    N, H, C, KS, H0 = 2, 7, 3, 2, 3
+    x = rng.standard_normal((N, H, H, C)).astype(np.float32); dy = rng.standard_normal((N, H0, H0, C)).astype(np.float32)
+    wt.check("pool", _oracle_pool(oracle, o, kind, x, KS, H0, H0), wt.pool(kind, x, KS))            # the default grid IS the floor grid
+    g = _oracle_dpool(oracle, o, kind, x, dy, KS, H0, H0)
+    w = wt.dpool(kind, dy, x, KS, keep=x)
+    wt.check("dpool", g, w)
+    assert not w.written[:, 6].any() and not w.written[:, :, 6].any() and w.written[:, :6, :6].all()
+    assert np.array_equal(g[:, 6], x[:, 6]) and np.array_equal(g[:, :, 6], x[:, :, 6])
+    w0 = wt.dpool(kind, dy, x, KS)                                           # without `keep` the witness says 0 there (the earlier callers' view)
+    assert not w0.exact[:, 6].any() and np.array_equal(w0.exact[:, :6, :6], w.exact[:, :6, :6])
+    assert not passes(g, w0)
+
+
+def test_fused_run_case_table_lands_on_its_plans_at_256_cus():
+    """every case of tests/small_kernel_cases.py reaches the launch plan and the vector width its label names on a 256-CU device; every
+    label is reached; the boundary cases sit on either side of 512 x 256 threads and the wrap cases leave a ragged second trip"""
+    seen = set()
+    for c in sk.RUN_CASES:
+        assert sk.run_vw(c.C) == c.vw and c.nthr * c.vw == c.N * c.H0 * c.W0 * c.C, c.id
+        assert sk.run_label(c.nthr, 256) == c.plan, (c.id, sk.run_plan(c.nthr, 256))
+        bs, grid, trips, tail = sk.run_plan(c.nthr, 256)
+        if c.plan == "wave64":
+            assert bs == 64 and 131072 - 8192 <= c.nthr < 131072 and grid == c.nthr // 64, c.id       # just below the switch
+        elif c.plan == "wg256":
+            assert bs == 256 and 131072 <= c.nthr <= 131072 + 8192 and grid == c.nthr // 256, c.id  # at / just above it
+        else:
+            assert bs == 256 and grid == sk.RUN_MAX_GRID and trips == 2 and 0 < tail < grid * bs // 32, (c.id, tail)
+        seen.add(c.plan); seen.add("vw%d" % c.vw)
+    assert seen == {"wave64", "wg256", "wg256_wrap", "vw4", "vw2", "vw1"}
+    assert {(c.plan, c.vw) for c in sk.RUN_CASES} >= {(pl, vw) for pl in ("wave64", "wg256") for vw in (4, 2, 1)}
+    for N, H1, W1, C, KS in sk.POOL_WRAP_CASES:
+        H0, W0 = sk.ceil_div(H1, KS), sk.ceil_div(W1, KS); n = N * H0 * W0 * C
+        grid, trips, tail = sk.pool_plan(n)
+        assert grid == sk.MAX_WG and trips == 2 and 0 < tail < grid * sk.BLK and n > sk.GRID1_STRIDE_N
+        assert H0 * KS > H1 and W0 * KS > W1                                  # a clipped last window in both directions
+    base = 1 << 20                                                          # any 16-byte aligned address
+    for label, tensor, off, vw in sk.RUN_MISALIGNED:
+        ptrs = {t: base for t in sk.RUN_TENSORS + ("DY", "XH", "O")}; ptrs[tensor] += off
+        got = sk.run_vw_tail(sk.run_vw(8, *(ptrs[t] for t in sk.RUN_TENSORS)), *(ptrs[t] for t in ("DY", "XH", "O")))
+        assert got == vw and label == "misaligned_" + tensor, (label, off, got)
+    assert {t for _, t, _, _ in sk.RUN_MISALIGNED} == set(sk.RUN_TENSORS) | {"DY", "XH", "O"}
+    assert sk.run_vw(8, base) == 4 and sk.run_vw(6, base) == 2 and sk.run_vw(5, base) == 1 and sk.run_vw(8, base + 8) == 2 and sk.run_vw(6, base + 4) == 1
