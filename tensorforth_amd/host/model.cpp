@@ -188,18 +188,23 @@ void Model::finalize() {                                // gradient slab: SURVEY
     if (tab_dev) { t4k_free(tab_dev); tab_dev = nullptr; }                  // parameter table holds the old pointers
     if (use_side && !side_) chk(t4k_stream_create(&side_), "side stream");
     plan_runs();
-    stack_end_.clear();
+    stack_end_.assign(layer.size(), -1);                // op index of a conv stack's last op -> its first op (the conv layer); all -1 under switches with which no step takes a stack (stacks_on)
+    for (int k = 0; use_fusion && use_stack && !side_ && k + 1 < (int)layer.size(); ) {
+        t4k_conv_stage stg[3]; int ops = 0;
+        const int ns = at(k).grad_fn == T4K_L_CONV ? stack_at(k, stg, ops) : 0;
+        if (ns >= 2 || (ns == 1 && stack_single_)) { stack_end_[k + ops - 1] = k; k += ops; } else k++;
+    }
     t4k_sync(stream());
 }
 // Fused element-wise runs: [dropout|activation] [pool] [activation] [flatten] -> one launch each way (csrc/fused.hip).
 // Only mask-multiply activations qualify (sigmoid is pass-through in the reference's backprop, backprop.cu:129-131).
-static bool is_eltwise(int f) { return f == T4K_L_RELU || f == T4K_L_TANH || f == T4K_L_SIGMOID || f == T4K_L_SELU || f == T4K_L_LEAKYRL || f == T4K_L_ELU || f == T4K_L_DROPOUT; }
+static bool is_mact(int f) { return f == T4K_L_RELU || f == T4K_L_TANH || f == T4K_L_SELU || f == T4K_L_LEAKYRL || f == T4K_L_ELU; }
+static bool is_pool(int f) { return f == T4K_L_AVGPOOL || f == T4K_L_MAXPOOL || f == T4K_L_MINPOOL; }
+static bool is_eltwise(int f) { return is_mact(f) || f == T4K_L_SIGMOID || f == T4K_L_DROPOUT; }
 void Model::plan_runs() {
     const int L = (int)layer.size() - 1;                // number of ops
-    run_of_.assign(layer.size(), -1); runs_.clear();
+    run_of_.assign(layer.size(), -1); run_at_.assign(layer.size(), -1); runs_.clear();
     if (!use_fusion) return;
-    auto is_mact = [](int f) { return f == T4K_L_RELU || f == T4K_L_TANH || f == T4K_L_SELU || f == T4K_L_LEAKYRL || f == T4K_L_ELU; };
-    auto is_pool = [](int f) { return f == T4K_L_AVGPOOL || f == T4K_L_MAXPOOL || f == T4K_L_MINPOOL; };
     for (int i = 0; i < L; ) {
         int j = i, pre = -1, pool = -1, post = -1, flat = -1;
         if (j < L && (is_mact(at(j).grad_fn) || at(j).grad_fn == T4K_L_DROPOUT)) pre = j++;
@@ -215,7 +220,9 @@ void Model::plan_runs() {
         if (pool >= 0) { b.pool_layer = at(pool).grad_fn; b.KS = at(pool).stride[0]; b.pool_out = at(pool + 1).data; }
         if (post >= 0) { b.post_layer = at(post).grad_fn; b.post_alpha = at(post).xparm; b.post_mask = at(post).grad[4]->data; b.post_out = at(post + 1).data; }
         if (flat >= 0) b.copy_out = at(flat + 1).data;
-        run_of_[i] = (int)runs_.size(); runs_.push_back(r);
+        Tensor &pin = at(pool >= 0 ? pool : i), &pout = pool >= 0 ? at(pool + 1) : pin;
+        r.N = at(i).N(); r.H1 = pin.H(); r.W1 = pin.W(); r.H0 = pout.H(); r.W0 = pout.W(); r.C = pin.C();
+        run_of_[i] = (int)runs_.size(); std::fill(run_at_.begin() + i, run_at_.begin() + j, run_of_[i]); runs_.push_back(r);
         i = j;
     }
 }
@@ -312,6 +319,34 @@ static void dp_bn_mode(bool train) {
     static const bool want = env_flag("T4_DP_SYNC_BN", true);
     if (t4k_comm_world() > 0) t4k_comm_sync_batchnorm(train && want);
 }
+// the classifier head [linear + activation] + [linear + softmax] at layer j, behind a conv stack (t4k_conv_stack_head_fwd)
+bool Model::fill_stack_head(int j, Tensor &input, t4k_stack_head &hd) {
+    Tensor &l1 = at(j), &y1 = at(j + 1), &act = at(j + 2), &y2 = at(j + 3), &prob = at(j + 4);
+    memset(&hd, 0, sizeof(hd));
+    hd.W1 = l1.grad[0]->data; hd.B1 = l1.grad[1]->data; hd.Y1 = y1.data;
+    hd.mid_layer = y1.grad_fn; hd.mid_alpha = y1.xparm; hd.mid_mask = y1.grad[4]->data; hd.mid_out = act.data;
+    hd.W2 = act.grad[0]->data; hd.B2 = act.grad[1]->data; hd.Y2 = y2.data; hd.P = prob.data;
+    hd.E1 = (int)l1.HWC(); hd.E0a = (int)y1.HWC(); hd.E0b = (int)y2.HWC();
+    // a dataset batch: the one-hot rows and the hit flags of Model::onehot(Dataset&) + hit (forward.cu:57-60) ride in the same launch
+    if (input.type != T_DATASET || j + 5 != (int)layer.size() || capturing_ || use_graphs) return false;
+    Dataset &ds = (Dataset &)input;
+    const uint32_t E = (uint32_t)prob.HWC();
+    if (!ds.label || ds.batch_sz < 1 || (uint32_t)ds.batch_sz > prob.N()) return false;
+    if (!hot) hot = &T4(prob.N(), 1, E, 1);
+    if ((uint32_t)ds.batch_sz < prob.N()) hot->zeros();     // short last batch: the rows past it stay zero and count nothing
+    if (!hit_flags_ || hit_flags_n_ < (int)prob.N()) {
+        if (hit_flags_) { t4k_sync(stream()); t4k_host_free(hit_flags_); t4k_free(hit_flags_dev_); }
+        void *pp; chk(t4k_host_alloc(&pp, prob.N()), "nn#hit flags"); hit_flags_ = (unsigned char *)pp; hit_flags_n_ = (int)prob.N();
+        chk(t4k_malloc(&pp, prob.N()), "nn#hit flags"); hit_flags_dev_ = (unsigned char *)pp;
+    }
+    // where the flags go: a loop that reads `nn.hit` every batch (the reference's demos, t4_30e.4th:68-76) gets them in pinned host memory -
+    // its device sync makes them readable, no copy; a loop that does not keeps them on the device, where the store does not hold the
+    // kernel's end behind a PCIe round trip, and the rare `nn.hit` copies them out
+    hit_flags_on_dev_ = !hit_read_;
+    hit_read_ = false;
+    hd.label = ds.label; hd.hot = hot->data; hd.hit_flag = hit_flags_on_dev_ ? hit_flags_dev_ : hit_flags_; hd.n_label = ds.batch_sz;
+    return true;
+}
 void Model::run_forward(Tensor &input) {
     hit_flags_pending_ = false;
     clear_dx0_marks();                                   // this pass overwrites layer 0: a skipped dX of the previous backward is gone for good
@@ -325,12 +360,13 @@ void Model::run_forward(Tensor &input) {
     auto lin_kind = [&](int i) -> int {
         if (!(i + 2 < L) || at(i).grad_fn != T4K_L_LINEAR) return 0;
         const int rn = run_of_[i + 1];
-        if (rn >= 0 && runs_[rn].count >= 2) return (!runs_[rn].blk.pool_layer && !runs_[rn].blk.copy_out) ? 3 : 0;
+        if (rn >= 0 && runs_[rn].count >= 2) return runs_[rn].masks_only() ? 3 : 0;
         if (!is_eltwise(at(i + 1).grad_fn)) return 0;
         return (at(i + 2).grad_fn == T4K_L_LINEAR && i + 4 < L && at(i + 3).grad_fn == T4K_L_SOFTMAX) ? 1 : 2;
     };
     const bool copy_in_lin = fused && input.data != n0.data && lin_kind(0) >= 2;   // a first linear layer's fold launch carries the layer-0 copy
-    if (!copy_in_conv && !copy_in_lin) lazy_copy(input.data, n0);
+    float *cp = (copy_in_conv || copy_in_lin) ? n0.data : nullptr;   // where op 0's own launch leaves the copy (null behind op 0)
+    if (!cp) lazy_copy(input.data, n0);
     bool masks = false;
     if (concurrent())                                   // side stream: draw every dropout mask up front, in layer order
         for (int i = 0; i + 1 < L; i++)
@@ -341,7 +377,7 @@ void Model::run_forward(Tensor &input) {
     tl_ = trace_ms();
     stack_fresh_.assign(layer.size(), 0);                // which conv stacks this forward ran through t4k_conv_stack_fwd (their saved state is current)
     const float *x = input.data;
-    for (int i = 0; i + 1 < L; i++) {
+    for (int i = 0; i + 1 < L; i++, cp = nullptr) {
         Tensor &in = at(i), &out = at(i + 1);
         if (trace && *trace) {                          // forward.cu:44-58: time since the previous layer's line, the layer, its input's sum per sample and channel
             const double tt = trace_ms();
@@ -352,15 +388,13 @@ void Model::run_forward(Tensor &input) {
         if (masks && in.grad_fn == T4K_L_DROPOUT) { join(); masks = false; }
         if (fused && run_of_[i] >= 0) {                 // one launch for the whole element-wise run
             const Run &r = runs_[run_of_[i]];
-            Tensor &lastt = at(i + r.count), &pin = (r.blk.pool_layer ? at(i + (r.blk.pre_layer ? 1 : 0)) : in);
-            chk(t4k_poolblock_fwd(x, &r.blk, in.N(), pin.H(), pin.W(), r.blk.pool_layer ? at(i + (r.blk.pre_layer ? 2 : 1)).H() : pin.H(),
-                                  r.blk.pool_layer ? at(i + (r.blk.pre_layer ? 2 : 1)).W() : pin.W(), pin.C(), stream()), "nn#frun");
-            x = lastt.data; i += r.count - 1;
+            chk(t4k_poolblock_fwd(x, &r.blk, r.N, r.H1, r.W1, r.H0, r.W0, r.C, stream()), "nn#frun");
+            x = at(i + r.count).data; i += r.count - 1;
             continue;
         }
         if (fused && in.grad_fn == T4K_L_LINEAR && lin_kind(i) == 3) {   // linear + an element-wise run of two (`leakyrelu dropout`): everything rides in the GEMM's fold launch
             const Run &r = runs_[run_of_[i + 1]];
-            chk(t4k_linear_block_fwd(x, (i == 0 && copy_in_lin) ? n0.data : nullptr, in.grad[0]->data, in.grad[1]->data, out.data, &r.blk,
+            chk(t4k_linear_block_fwd(x, cp, in.grad[0]->data, in.grad[1]->data, out.data, &r.blk,
                                      out.N(), (int)out.HWC(), (int)in.HWC(), stream()), "nn#flinear+run");
             x = at(i + 1 + r.count).data; i += r.count;
             continue;
@@ -376,10 +410,10 @@ void Model::run_forward(Tensor &input) {
                 x = prob.data; i += 3;
                 continue;
             }
-            if (i == 0 && copy_in_lin) {                // the copy of the batch into layer 0 goes with the same launch
+            if (cp) {                                   // the copy of the batch into layer 0 goes with the same launch
                 t4k_poolblock b1; memset(&b1, 0, sizeof(b1)); b1.KS = 1;
                 b1.pre_layer = out.grad_fn; b1.pre_alpha = out.xparm; b1.pre_mask = out.grad[4]->data; b1.pre_out = act.data;
-                chk(t4k_linear_block_fwd(x, n0.data, in.grad[0]->data, in.grad[1]->data, out.data, &b1, out.N(), (int)out.HWC(), (int)in.HWC(), stream()), "nn#flinear+act");
+                chk(t4k_linear_block_fwd(x, cp, in.grad[0]->data, in.grad[1]->data, out.data, &b1, out.N(), (int)out.HWC(), (int)in.HWC(), stream()), "nn#flinear+act");
             } else
                 chk(t4k_linear_act_fwd(x, in.grad[0]->data, in.grad[1]->data, out.data, out.grad_fn, out.xparm, out.grad[4]->data, act.data,
                                        out.N(), (int)out.HWC(), (int)in.HWC(), stream()), "nn#flinear+act");
@@ -392,85 +426,41 @@ void Model::run_forward(Tensor &input) {
             x = prob.data; i++;
             continue;
         }
-        if (fused && use_stack && in.grad_fn == T4K_L_CONV) {   // [conv + run] x n, one workgroup per image, activations in LDS: ONE launch
+        if (fused && in.grad_fn == T4K_L_CONV) {        // a conv layer and what rides in its launch: the widest group first
             t4k_conv_stage stg[3]; int ops = 0;
-            const int ns = stack_at(i, stg, ops);
-            if (ns >= 2 || (ns == 1 && stack_single_)) {
-                const int j = i + ops;                  // the layer behind the stack: a classifier head [linear + activation] + [linear + softmax]?
-                if (use_stack_head && j + 1 < L && lin_kind(j) == 1) {   // then the whole forward pass is ONE launch
-                    Tensor &l1 = at(j), &y1 = at(j + 1), &act = at(j + 2), &y2 = at(j + 3), &prob = at(j + 4);
-                    t4k_stack_head hd; memset(&hd, 0, sizeof(hd));
-                    hd.W1 = l1.grad[0]->data; hd.B1 = l1.grad[1]->data; hd.Y1 = y1.data;
-                    hd.mid_layer = y1.grad_fn; hd.mid_alpha = y1.xparm; hd.mid_mask = y1.grad[4]->data; hd.mid_out = act.data;
-                    hd.W2 = act.grad[0]->data; hd.B2 = act.grad[1]->data; hd.Y2 = y2.data; hd.P = prob.data;
-                    hd.E1 = (int)l1.HWC(); hd.E0a = (int)y1.HWC(); hd.E0b = (int)y2.HWC();
-                    // a dataset batch: the one-hot rows and the hit flags of Model::onehot(Dataset&) + hit (forward.cu:57-60) ride in the same launch
-                    bool rider = false;
-                    if (input.type == T_DATASET && j + 4 == L - 1 && !capturing_ && !use_graphs) {
-                        Dataset &ds = (Dataset &)input;
-                        const uint32_t E = (uint32_t)prob.HWC();
-                        if (ds.label && ds.batch_sz >= 1 && (uint32_t)ds.batch_sz <= prob.N()) {
-                            if (!hot) hot = &T4(prob.N(), 1, E, 1);
-                            if ((uint32_t)ds.batch_sz < prob.N()) hot->zeros();     // short last batch: the rows past it stay zero and count nothing
-                            if (!hit_flags_ || hit_flags_n_ < (int)prob.N()) {
-                                if (hit_flags_) { t4k_sync(stream()); t4k_host_free(hit_flags_); t4k_free(hit_flags_dev_); }
-                                void *pp; chk(t4k_host_alloc(&pp, prob.N()), "nn#hit flags"); hit_flags_ = (unsigned char *)pp; hit_flags_n_ = (int)prob.N();
-                                chk(t4k_malloc(&pp, prob.N()), "nn#hit flags"); hit_flags_dev_ = (unsigned char *)pp;
-                            }
-                            // where the flags go: a loop that reads `nn.hit` every batch (the reference's demos, t4_30e.4th:68-76) gets them in pinned host memory -
-                            // its device sync makes them readable, no copy; a loop that does not keeps them on the device, where the store does not hold the
-                            // kernel's end behind a PCIe round trip, and the rare `nn.hit` copies them out
-                            hit_flags_on_dev_ = !hit_read_;
-                            hit_read_ = false;
-                            hd.label = ds.label; hd.hot = hot->data; hd.hit_flag = hit_flags_on_dev_ ? hit_flags_dev_ : hit_flags_; hd.n_label = ds.batch_sz; rider = true;
-                        }
-                    }
-                    if (t4k_conv_stack_head_ok(stg, ns, in.N(), &hd)) {
-                        chk(t4k_conv_stack_head_fwd(x, (i == 0 && copy_in_conv) ? n0.data : nullptr, stg, ns, in.N(), &hd, stream()), "nn#fstack+head");
-                        if (rider) { hit_flags_pending_ = true; hit_pending_ = false; }
-                        stack_fresh_[i] = 1;
-                        x = prob.data; i = j + 3;
-                        continue;
-                    }
-                }
-                chk(t4k_conv_stack_fwd(x, (i == 0 && copy_in_conv) ? n0.data : nullptr, stg, ns, in.N(), stream()), "nn#fstack");
-                stack_fresh_[i] = 1;
-                x = at(i + ops).data; i += ops - 1;
-                continue;
+            const int ns = use_stack ? stack_at(i, stg, ops) : 0;
+            const int j = i + ops;                      // the layer behind the stack: a classifier head [linear + activation] + [linear + softmax]?
+            const bool stack = ns >= 2 || (ns == 1 && stack_single_);
+            t4k_stack_head hd;
+            const bool head = stack && use_stack_head && j + 1 < L && lin_kind(j) == 1, rider = head && fill_stack_head(j, input, hd);
+            const Run *r1 = (i + 2 < L && run_of_[i + 1] >= 0) ? &runs_[run_of_[i + 1]] : nullptr;       // the element-wise run behind the conv, behind conv + batch-norm
+            const Run *r2 = (i + 3 < L && out.grad_fn == T4K_L_BATCHNM && run_of_[i + 2] >= 0) ? &runs_[run_of_[i + 2]] : nullptr;
+            float *F = in.grad[0]->data, *B = in.grad[1]->data;
+            const int N = out.N(), H1 = in.H(), W1 = in.W(), C1 = in.C(), H0 = out.H(), W0 = out.W(), C0 = out.C(), K = in.grad[0]->H(), S = in.stride[0], P = in.stride[2];
+            int last = -1;                              // the last op the launch covers
+            if (head && t4k_conv_stack_head_ok(stg, ns, N, &hd)) {     // [conv + run] x n + head, one workgroup per image, activations in LDS: the whole forward pass is ONE launch
+                chk(t4k_conv_stack_head_fwd(x, cp, stg, ns, N, &hd, stream()), "nn#fstack+head");
+                if (rider) { hit_flags_pending_ = true; hit_pending_ = false; }
+                stack_fresh_[i] = 1; last = j + 3;
+            } else if (stack) {                         // [conv + run] x n
+                chk(t4k_conv_stack_fwd(x, cp, stg, ns, N, stream()), "nn#fstack");
+                stack_fresh_[i] = 1; last = j - 1;
+            } else if (r1 && r1->blk.pool_layer && r1->blk.KS == 2) {   // conv + the run behind it: the run rides in the conv epilogue
+                chk(t4k_conv2d_block_fwd(x, cp, out.data, F, B, &r1->blk, N, H1, W1, C1, H0, W0, C0, K, S, P, stream()), "nn#fconv+run");
+                last = i + r1->count;
+            } else if (r2) {                            // conv + batch-norm + the run behind them: the conv output is read once (statistics from the conv's epilogue, batch-norm apply inside the run's launch)
+                chk(t4k_conv2d_bn_block_fwd(x, cp, out.data, F, B, N, H1, W1, C1, H0, W0, C0, K, S, P, at(i + 2).data, out.grad[4]->data, out.grad[0]->data, out.grad[1]->data,
+                                            out.mtum[4]->data, &r2->blk, r2->H0, r2->W0, stream()), "nn#fconv+batchnorm+run");
+                last = i + 1 + r2->count;
+            } else if (i + 2 < L && out.grad_fn == T4K_L_BATCHNM) {   // conv + batch-norm: the statistics ride in the conv's epilogue where its kernel carries them
+                chk(t4k_conv2d_bn_fwd(x, cp, out.data, F, B, N, H1, W1, C1, H0, W0, C0, K, S, P, at(i + 2).data, out.grad[4]->data, out.grad[0]->data, out.grad[1]->data,
+                                      out.mtum[4]->data, stream()), "nn#fconv+batchnorm");
+                last = i + 1;
+            } else if (cp) {                            // the conv alone, with the layer-0 copy
+                chk(t4k_conv2d_fwd2(x, cp, out.data, F, B, N, H1, W1, C1, H0, W0, C0, K, S, P, stream()), "nn#fconv");
+                last = i;
             }
-        }
-        if (fused && in.grad_fn == T4K_L_CONV && i + 2 < L && run_of_[i + 1] >= 0 && runs_[run_of_[i + 1]].blk.pool_layer &&
-            runs_[run_of_[i + 1]].blk.KS == 2) {        // conv + the element-wise run behind it: the run rides in the conv epilogue
-            const Run &r = runs_[run_of_[i + 1]];
-            chk(t4k_conv2d_block_fwd(x, (i == 0 && copy_in_conv) ? n0.data : nullptr, out.data, in.grad[0]->data, in.grad[1]->data, &r.blk,
-                                     out.N(), in.H(), in.W(), in.C(), out.H(), out.W(), out.C(), in.grad[0]->H(), in.stride[0], in.stride[2], stream()), "nn#fconv+run");
-            x = at(i + 1 + r.count).data; i += r.count;
-            continue;
-        }
-        if (fused && in.grad_fn == T4K_L_CONV && i + 3 < L && out.grad_fn == T4K_L_BATCHNM && run_of_[i + 2] >= 0) {   // conv + batch-norm + the element-wise run behind them: the conv
-            const int i2 = i + 2;                          // output is read once (statistics from the conv's epilogue, batch-norm apply inside the run's launch)
-            const Run &r = runs_[run_of_[i2]];
-            Tensor &o2 = at(i2), &pin = (r.blk.pool_layer ? at(i2 + (r.blk.pre_layer ? 1 : 0)) : o2);
-            const int Hq = r.blk.pool_layer ? at(i2 + (r.blk.pre_layer ? 2 : 1)).H() : pin.H(), Wq = r.blk.pool_layer ? at(i2 + (r.blk.pre_layer ? 2 : 1)).W() : pin.W();
-            chk(t4k_conv2d_bn_block_fwd(x, (i == 0 && copy_in_conv) ? n0.data : nullptr, out.data, in.grad[0]->data, in.grad[1]->data, out.N(), in.H(), in.W(), in.C(),
-                                        out.H(), out.W(), out.C(), in.grad[0]->H(), in.stride[0], in.stride[2],
-                                        o2.data, out.grad[4]->data, out.grad[0]->data, out.grad[1]->data, out.mtum[4]->data, &r.blk, Hq, Wq, stream()), "nn#fconv+batchnorm+run");
-            x = at(i2 + r.count).data; i = i2 + r.count - 1;
-            continue;
-        }
-        if (fused && in.grad_fn == T4K_L_CONV && i + 2 < L && out.grad_fn == T4K_L_BATCHNM) {   // conv + batch-norm: the statistics ride in the conv's epilogue where its kernel carries them
-            Tensor &o2 = at(i + 2);
-            chk(t4k_conv2d_bn_fwd(x, (i == 0 && copy_in_conv) ? n0.data : nullptr, out.data, in.grad[0]->data, in.grad[1]->data, out.N(), in.H(), in.W(), in.C(),
-                                  out.H(), out.W(), out.C(), in.grad[0]->H(), in.stride[0], in.stride[2],
-                                  o2.data, out.grad[4]->data, out.grad[0]->data, out.grad[1]->data, out.mtum[4]->data, stream()), "nn#fconv+batchnorm");
-            x = o2.data; i += 1;
-            continue;
-        }
-        if (i == 0 && copy_in_conv) {
-            chk(t4k_conv2d_fwd2(x, n0.data, out.data, in.grad[0]->data, in.grad[1]->data, out.N(), in.H(), in.W(), in.C(),
-                                out.H(), out.W(), out.C(), in.grad[0]->H(), in.stride[0], in.stride[2], stream()), "nn#fconv");
-            x = out.data;
-            continue;
+            if (last >= 0) { i = last; x = at(i + 1).data; continue; }
         }
         x = fstep(in, out, x);
         if (trace && *trace && out.has_nan()) {
@@ -733,10 +723,11 @@ void Model::run_backward(Tensor &tgt) {
     const bool fused = use_fusion && !(trace && *trace) && !concurrent();
     int skip = 0;                                       // layers already handled by the prep launch
     const float *dy0 = nullptr;                         // ... and where they left the gradient (default: the output tensor)
+    const float *tg = nullptr;                          // `out -= target` still pending: the last linear layer's backward launch performs it
     NLOG("Model::bprep input(onehot) numel=%ld OK {\n", (long)tgt.numel);     // _bprep backprop.cu:84-106 (under trace nothing is fused: the loss derivative is a launch of its own)
     switch (at(-2).grad_fn) {
     case T4K_L_SIGMOID: case T4K_L_SOFTMAX: case T4K_L_LOGSMAX:
-        if (fused && layer.size() > 3 && at(-3).grad_fn == T4K_L_LINEAR) { prep_tgt_ = &tgt; skip = 1; break; }   // rides in the linear backward launch
+        if (fused && layer.size() > 3 && at(-3).grad_fn == T4K_L_LINEAR) { tg = tgt.data; skip = 1; break; }   // rides in the linear backward launch
         if (fused && layer.size() > 2) {                // out -= target, and the pass-through `in = out` of the last layer, in one launch
             chk(t4k_tt_op2(T4K_SUB, out.data, tgt.data, out.data, at(-2).data, (long)out.numel, s), "bprep"); skip = 1; break;
         }
@@ -744,9 +735,7 @@ void Model::run_backward(Tensor &tgt) {
     case T4K_L_LINEAR:
         chk(t4k_tt_op(T4K_SUB, out.data, tgt.data, out.data, (long)out.numel, s), "bprep"); break;
     default: {
-        const int lf = at(-2).grad_fn;                  // last op
-        const bool mact = lf == T4K_L_RELU || lf == T4K_L_TANH || lf == T4K_L_SELU || lf == T4K_L_LEAKYRL || lf == T4K_L_ELU;
-        if (fused && mact && layer.size() > 2 && run_of_[(int)layer.size() - 2] < 0 && at(-2).numel == out.numel) {   // copy + the activation's mask multiply, one launch
+        if (fused && is_mact(at(-2).grad_fn) && layer.size() > 2 && run_of_[(int)layer.size() - 2] < 0 && at(-2).numel == out.numel) {   // copy + the activation's mask multiply, one launch
             chk(t4k_copy_mask(tgt.data, at(-2).grad[4]->data, out.data, at(-2).data, (long)out.numel, s), "bprep+bactivate"); skip = 1; dy0 = at(-2).data; break;
         }
         chk(t4k_copy(tgt.data, out.data, (long)out.numel, s), "bprep"); break;
@@ -757,6 +746,7 @@ void Model::run_backward(Tensor &tgt) {
     NLOG("\nModel::backprop starts trace=%d train=%d {", *trace, (int)train);
     tl_ = trace_ms();
     const float *dy = dy0 ? dy0 : out.data;             // where the gradient w.r.t. the current layer's output lives
+    const bool stacks = stacks_on();
     for (int i = (int)layer.size() - 2 - skip, j = skip; i >= 0; i--, j++) {
         Tensor &in = at(i), &o = at(i + 1);
         if (trace && *trace) {                          // backprop.cu:40-58
@@ -765,62 +755,53 @@ void Model::run_backward(Tensor &tgt) {
                    in.N(), in.H(), in.W(), in.C(), in.xparm, o.sum() / o.N() / o.C(), o.N(), o.H(), o.W(), o.C());
             tl_ = tt;
         }
-        if (fused && use_stack && j > 0) {              // does a sample-resident conv stack END at op i?  [conv + run] x n backward in ONE launch (+ the partial fold)
-            if (stack_end_.empty()) {                   // op index of a stack's last op -> its first op (conv layer), built once per finalize
-                stack_end_.assign(layer.size(), -1);
-                for (int k = 0; k + 1 < (int)layer.size(); ) {
-                    t4k_conv_stage stg[3]; int ops = 0;
-                    const int ns = at(k).grad_fn == T4K_L_CONV ? stack_at(k, stg, ops) : 0;
-                    if (ns >= 2 || (ns == 1 && stack_single_)) { stack_end_[k + ops - 1] = k; k += ops; } else k++;
+        const int k0 = stacks && j > 0 ? stack_end_[i] : -1;
+        if (k0 >= 0) {                                  // a sample-resident conv stack ENDS at op i: [conv + run] x n backward in ONE launch (+ the partial fold)
+            t4k_conv_stage stg[3]; int ops = 0;
+            const int ns = stack_at(k0, stg, ops);
+            const int bflags = (train ? 1 : 0) | ((k0 < (int)stack_fresh_.size() && stack_fresh_[k0]) ? 0 : 2) | ((use_opt_fold && !grad_hook && !capturing_) ? 4 : 0) | ((use_lazy_dx0 && k0 == 0 && !capturing_ && !use_graphs) ? 8 : 0);
+            // (asked first, quietly: without the forward's saved state the whole-image kernel runs, and its windows may not fit the LDS - the per-layer kernels then)
+            if (ns > 0 && k0 + ops - 1 == i && t4k_conv_stack_bwd_ok(stg, ns, at(k0).N(), bflags, s) && chk(t4k_conv_stack_bwd(dy, stg, ns, at(k0).N(), bflags, s), "nn#bstack") == T4K_OK) {
+                if (k0 == 0 && use_lazy_dx0 && t4k_conv_stack_dx0_pending(stg[0].O)) {
+                    dx0_stale_ = true; at(0).stale_owner = this; if (at(0).grad[4]) at(0).grad[4]->stale_owner = this;
                 }
-            }
-            if (stack_end_[i] >= 0) {
-                const int k0 = stack_end_[i];
-                t4k_conv_stage stg[3]; int ops = 0;
-                const int ns = stack_at(k0, stg, ops);
-                const int bflags = (train ? 1 : 0) | ((k0 < (int)stack_fresh_.size() && stack_fresh_[k0]) ? 0 : 2) | ((use_opt_fold && !grad_hook && !capturing_) ? 4 : 0) | ((use_lazy_dx0 && k0 == 0 && !capturing_ && !use_graphs) ? 8 : 0);
-                // (asked first, quietly: without the forward's saved state the whole-image kernel runs, and its windows may not fit the LDS - the per-layer kernels then)
-                if (ns > 0 && k0 + ops - 1 == i && t4k_conv_stack_bwd_ok(stg, ns, at(k0).N(), bflags, s) && chk(t4k_conv_stack_bwd(dy, stg, ns, at(k0).N(), bflags, s), "nn#bstack") == T4K_OK) {
-                    if (k0 == 0 && use_lazy_dx0 && t4k_conv_stack_dx0_pending(stg[0].O)) {
-                        dx0_stale_ = true; at(0).stale_owner = this; if (at(0).grad[4]) at(0).grad[4]->stale_owner = this;
-                    }
-                    for (int k = i; k >= k0; k--) if (at(k).grad_fn == T4K_L_CONV) grads_ready(k, at(k));      // slab segments complete, last layer first
-                    dy = at(k0).data; j += i - k0; i = k0;
-                    continue;
-                }
-            }
-        }
-        if (fused && j > 0) {                           // does a fused run END at op i?
-            int rf = -1;
-            for (int k = i; k >= 0 && k > i - 4; k--) if (run_of_[k] >= 0 && k + runs_[run_of_[k]].count - 1 == i) { rf = k; break; }
-            if (rf >= 0) {
-                const Run &r = runs_[run_of_[rf]];
-                Tensor &fin = at(rf), &pin = (r.blk.pool_layer ? at(rf + (r.blk.pre_layer ? 1 : 0)) : fin);
-                const int ho = r.blk.pool_layer ? at(rf + (r.blk.pre_layer ? 2 : 1)).H() : pin.H(), wo = r.blk.pool_layer ? at(rf + (r.blk.pre_layer ? 2 : 1)).W() : pin.W();
-                chk(t4k_poolblock_bwd(dy, fin.data, &r.blk, fin.N(), pin.H(), pin.W(), ho, wo, pin.C(), s), "nn#brun");
-                dy = fin.data; j += i - rf; i = rf;
+                for (int k = i; k >= k0; k--) if (at(k).grad_fn == T4K_L_CONV) grads_ready(k, at(k));      // slab segments complete, last layer first
+                dy = at(k0).data; j += i - k0; i = k0;
                 continue;
             }
         }
-        dy = bstep(i, in, o, dy, j == 0);
-        if (skip_next_) {                               // bstep also ran the backward of op i-1 (a lone mask-multiply layer)
-            skip_next_ = false;
-            grads_ready(i, in);
-            if (also_ready_ >= 0) { grads_ready(also_ready_, at(also_ready_)); also_ready_ = -1; }   // a second layer's gradients came out of the same launch
-            const int k = skip_cnt_; skip_cnt_ = 1;
-            dy = at(i - k).data; i -= k; j += k;
+        const Run *r = fused && j > 0 && run_at_[i] >= 0 ? &runs_[run_at_[i]] : nullptr;
+        if (r && r->first + r->count - 1 == i) {        // a fused run ENDS at op i
+            Tensor &fin = at(r->first);
+            chk(t4k_poolblock_bwd(dy, fin.data, &r->blk, r->N, r->H1, r->W1, r->H0, r->W0, r->C, s), "nn#brun");
+            dy = fin.data; j += i - r->first; i = r->first;
             continue;
         }
+        const Back b = bstep(i, in, o, dy, j == 0, tg);
+        tg = nullptr;
         grads_ready(i, in);
+        if (b.also >= 0) grads_ready(b.also, at(b.also));   // a second layer's gradients came out of the same launch
+        dy = b.dy; i -= b.covered; j += b.covered;      // the launch also ran the backward of `covered` ops in front (fused plans only: nothing to trace there)
         if (trace && *trace && in.has_nan()) { hprintf("nn#backprop Nan %s\n", LAYER_NAME[in.grad_fn]); TSHOW(in, false); TSHOW(o, false); err = true; break; }
         if (trace && *trace > 1) TSHOW(in, true);       // `2 trace`: every layer's dX (backprop.cu:67)
     }
     join();
 }
+// The first layer's dX is read by no training loop: its backward runs dF | dB (dW | dB) only when some layer tensor holds dY - that tensor, layer 0
+// and the weights carry the mark, and the first word that resolves one of them has dX0 produced (materialize_dx0).  false: no holder, dX0 is stored now.
+bool Model::offer_dx0(const float *dy, bool conv) {
+    Tensor &in = at(0), *holder = nullptr;
+    for (int k = 1; k < (int)layer.size() && !holder; k++) if (at(k).data == dy) holder = &at(k);
+    if (!holder) return false;
+    dx0_stale_ = true; dx0_lin_ = true; w0_saved_ = false; dx0_dy_ = dy; dx0_dy_t_ = holder;
+    in.stale_owner = this; in.grad[0]->stale_owner = this; holder->stale_owner = this;
+    if (conv) { dx0_conv_ = true; in.grad[4]->stale_owner = this; }
+    return true;
+}
 // one layer backward (_bstep backprop.cu:111-140): reads dY at `dy`, leaves dX in in.data (the reference's
 // in-place convention) and returns where the previous layer finds it.  Parameter gradients and the
-// `in = dX` copies run on the side stream.
-const float *Model::bstep(int i, Tensor &in, Tensor &out, const float *dy, bool last) {
+// `in = dX` copies run on the side stream.  `tg`: backprop's `out -= target` is still pending (run_backward).
+Model::Back Model::bstep(int i, Tensor &in, Tensor &out, const float *dy, bool last, const float *tg) {
     const int fn = in.grad_fn;
     t4k_stream_t s = stream();
     switch (fn) {
@@ -828,133 +809,42 @@ const float *Model::bstep(int i, Tensor &in, Tensor &out, const float *dy, bool 
         Tensor &dx = *in.grad[4];
         const int N = in.N(), H1 = in.H(), W1 = in.W(), C1 = in.C(), H0 = out.H(), W0 = out.W(), C0 = out.C();
         const int K = in.grad[0]->H(), S = in.stride[0], P = in.stride[2];
-        if (i == 0 && train && use_lazy_dx0 && use_fusion && !(trace && *trace) && !concurrent() && !capturing_ && !use_graphs && in.grad[2] && in.grad[3]) {
-            // the net's first layer: nobody reads dX0 in a training loop - dF | dB now, dX0 when a word asks (materialize_dx0)
-            Tensor *holder = nullptr;
-            for (int k = 1; k < (int)layer.size() && !holder; k++) if (at(k).data == dy) holder = &at(k);
-            if (holder) {
-                chk(t4k_conv2d_bwd(in.data, dy, nullptr, in.grad[0]->data, in.grad[2]->data, in.grad[3]->data,
-                                   N, H1, W1, C1, H0, W0, C0, K, S, P, 1, s), "nn#bconv dF");
-                dx0_stale_ = true; dx0_lin_ = true; dx0_conv_ = true; w0_saved_ = false; dx0_dy_ = dy; dx0_dy_t_ = holder;
-                in.stale_owner = this; dx.stale_owner = this; in.grad[0]->stale_owner = this; holder->stale_owner = this;
-                return in.data;
-            }
+        if (i == 0 && train && use_lazy_dx0 && use_fusion && !(trace && *trace) && !concurrent() && !capturing_ && !use_graphs && in.grad[2] && in.grad[3] &&
+            offer_dx0(dy, true)) {                      // the net's first layer: dF | dB now, dX0 when a word asks
+            chk(t4k_conv2d_bwd(in.data, dy, nullptr, in.grad[0]->data, in.grad[2]->data, in.grad[3]->data,
+                               N, H1, W1, C1, H0, W0, C0, K, S, P, 1, s), "nn#bconv dF");
+            return { in.data };
         }
         if (!concurrent()) {                            // one stream: dF|dB read x first, then dX lands in the scratch tensor AND over x
             chk(t4k_conv2d_bwd2(in.data, dy, dx.data, in.data, in.grad[0]->data, train ? in.grad[2]->data : nullptr, train ? in.grad[3]->data : nullptr,
                                 N, H1, W1, C1, H0, W0, C0, K, S, P, train, s), "nn#bconv");
-            return in.data;
+            return { in.data };
         }
         if (train) chk(t4k_conv2d_bwd(in.data, dy, nullptr, in.grad[0]->data, in.grad[2]->data, in.grad[3]->data,
                                       N, H1, W1, C1, H0, W0, C0, K, S, P, 1, fork()), "nn#bconv dF");
         chk(t4k_conv2d_bwd(in.data, dy, dx.data, in.grad[0]->data, nullptr, nullptr, N, H1, W1, C1, H0, W0, C0, K, S, P, 0, s), "nn#bconv dX");
         lazy_copy(dx.data, in);                         // x = dX (overwrite), backprop.cu:185 - after dF has consumed x
-        return dx.data;
+        return { dx.data };
     }
     case T4K_L_DCONV: {                                 // backprop.cu:137: the conv forward routine gives dX; dF|dB read x first, then `in = dx`
         Tensor &dx = *in.grad[4];
         chk(t4k_dconv2d_bwd(in.data, dy, dx.data, in.grad[0]->data, train ? in.grad[2]->data : nullptr, train ? in.grad[3]->data : nullptr,
                             in.N(), in.H(), in.W(), in.C(), out.H(), out.W(), out.C(), in.grad[0]->H(), in.stride[0], in.stride[2], train, s), "nn#bdconv");
         chk(t4k_copy(dx.data, in.data, (long)in.numel, s), "nn#bdconv in = dx");
-        return in.data;
+        break;
     }
     case T4K_L_LINEAR: {
-        if (last) { lazy_copy(dy, in); return dy; }     // linear as the last layer: pass dY (backprop.cu:119-121)
-        const int N = in.N(), E0 = (int)out.HWC(), E1 = (int)in.HWC();
+        if (last) { lazy_copy(dy, in); return { dy }; }  // linear as the last layer: pass dY (backprop.cu:119-121)
         Tensor *gx = concurrent() ? gx_[i] : nullptr;
-        if (!gx) {                                      // single stream: reference order (dW reads X, then dX overwrites it)
-            const float *tg = prep_tgt_ ? prep_tgt_->data : nullptr;   // backprop's `out -= target` still pending (run_backward)
-            prep_tgt_ = nullptr;
-            // a lone mask-multiply layer (dropout, relu, ...) right in front of this linear layer: its backward rides along
-            const bool fused = use_fusion && !(trace && *trace);
-            if (fused && i > 0 && run_of_[i - 1] >= 0 && runs_[run_of_[i - 1]].count == 1 && !runs_[run_of_[i - 1]].blk.pool_layer &&
-                runs_[run_of_[i - 1]].blk.pre_layer) {
-                Tensor &prev = at(i - 1);
-                // ... and when the layer in front of THAT is the linear layer behind a conv stack's flatten (the t4_30a/30e classifier), its backward
-                // joins the launch too: every GEMM tile recomputes the rows of dY1 it needs (10 terms each), so nothing waits for the head (t4k_mlp_head_bwd)
-                if (tg && use_head_bwd && train && i >= 3 && at(i - 2).grad_fn == T4K_L_LINEAR && !stack_end_.empty() && stack_end_[i - 3] >= 0 &&
-                    at(i - 2).grad[2] && at(i - 2).grad[3] &&
-                    t4k_mlp_head_bwd_ok(N, (int)at(i - 2).HWC(), E1, E0)) {
-                    Tensor &big = at(i - 2);
-                    chk(t4k_mlp_head_bwd(in.data, in.grad[0]->data, (float *)dy, tg, at(-2).data, prev.grad[4]->data, prev.data, in.grad[2]->data, in.grad[3]->data,
-                                         big.data, big.grad[0]->data, big.grad[2]->data, big.grad[3]->data, N, (int)big.HWC(), E1, E0, s), "nn#bhead+blinear");
-                    skip_next_ = true; skip_cnt_ = 2; also_ready_ = i - 2;
-                    return big.data;
-                }
-                if (tg) chk(t4k_loss_linear_bwd(in.data, in.grad[0]->data, (float *)dy, tg, at(-2).data, in.data, prev.grad[4]->data, prev.data,
-                                            train ? in.grad[2]->data : nullptr, train ? in.grad[3]->data : nullptr, N, E0, E1, train, s), "nn#bprep+blinear+act");
-                else
-                chk(t4k_linear_bwd2(in.data, in.grad[0]->data, dy, in.data, prev.grad[4]->data, prev.data, train ? in.grad[2]->data : nullptr,
-                                    train ? in.grad[3]->data : nullptr, N, E0, E1, train, s), "nn#blinear+act");
-                skip_next_ = true;
-                return in.data;
-            }
-            // a lone activation that multiplies by its derivative mask (relu, tanh, leakyrelu, ... - not a fused run, not the
-            // pass-through sigmoid) in front of a layer too large for the head kernel: the multiply rides in the dX epilogue
-            auto in_run = [&](int op) { for (int k = op; k >= 0 && k > op - 5; k--) if (run_of_[k] >= 0 && k + runs_[run_of_[k]].count - 1 >= op) return true; return false; };
-            if (fused && i > 0 && !tg && !in_run(i - 1)) {
-                const int pf = at(i - 1).grad_fn;
-                if (pf == T4K_L_RELU || pf == T4K_L_TANH || pf == T4K_L_SELU || pf == T4K_L_LEAKYRL || pf == T4K_L_ELU) {
-                    Tensor &prev = at(i - 1);
-                    t4k_poolblock b1; memset(&b1, 0, sizeof(b1)); b1.KS = 1;
-                    b1.pre_layer = pf; b1.pre_alpha = prev.xparm; b1.pre_mask = prev.grad[4]->data; b1.pre_out = in.data;
-                    chk(t4k_linear_block_bwd(in.data, in.grad[0]->data, (float *)dy, nullptr, nullptr, in.data, &b1, prev.data,
-                                             train ? in.grad[2]->data : nullptr, train ? in.grad[3]->data : nullptr, N, E0, E1, train, s), "nn#blinear+act");
-                    skip_next_ = true; skip_cnt_ = 1;
-                    return in.data;
-                }
-            }
-            // a run of two mask-multiply layers (`leakyrelu dropout`) in front: its backward rides along as well
-            if (fused && i > 1 && run_of_[i - 2] >= 0 && runs_[run_of_[i - 2]].count == 2 && !runs_[run_of_[i - 2]].blk.pool_layer &&
-                !runs_[run_of_[i - 2]].blk.copy_out) {
-                const Run &r = runs_[run_of_[i - 2]];
-                // the linear layer in front of that run joins the launch when it is the net's first layer or has such a run of its own in front (the GAN
-                // discriminator: linear, leakyrelu, dropout, linear, leakyrelu, dropout, linear, sigmoid) - t4k_mlp_block_bwd, see t4k_mlp_head_bwd
-                // (measured on the GAN nets, N = 256, 256-wide runs: 28.5 us against 9 + 11.7 us apart - re-reading two 256 KB masks per tile costs more than
-                // reading the finished dY1; opt-in with T4_HEAD_BWD=2)
-                static const bool runs_too = env_long("T4_HEAD_BWD", 1) >= 2;
-                if (tg && use_head_bwd && runs_too && i >= 3 && at(i - 3).grad_fn == T4K_L_LINEAR && (!train || (at(i - 3).grad[2] && at(i - 3).grad[3]))) {
-                    Tensor &big = at(i - 3);
-                    const Run *r1 = nullptr;
-                    if (i >= 5 && run_of_[i - 5] >= 0 && runs_[run_of_[i - 5]].count == 2 && !runs_[run_of_[i - 5]].blk.pool_layer && !runs_[run_of_[i - 5]].blk.copy_out) r1 = &runs_[run_of_[i - 5]];
-                    if ((r1 || i == 3) && t4k_mlp_head_bwd_ok(N, (int)big.HWC(), E1, E0)) {
-                        chk(t4k_mlp_block_bwd(in.data, in.grad[0]->data, (float *)dy, tg, at(-2).data, &r.blk, at(i - 2).data,
-                                              train ? in.grad[2]->data : nullptr, train ? in.grad[3]->data : nullptr,
-                                              big.data, big.grad[0]->data, r1 ? &r1->blk : nullptr, r1 ? at(i - 5).data : nullptr,
-                                              train ? big.grad[2]->data : nullptr, train ? big.grad[3]->data : nullptr, N, (int)big.HWC(), E1, E0, train, s), "nn#bhead+run+blinear");
-                        skip_next_ = true; skip_cnt_ = r1 ? 5 : 3; also_ready_ = i - 3;
-                        return r1 ? at(i - 5).data : big.data;
-                    }
-                }
-                chk(t4k_linear_block_bwd(in.data, in.grad[0]->data, (float *)dy, tg, tg ? at(-2).data : nullptr, in.data, &r.blk, at(i - 2).data,
-                                         train ? in.grad[2]->data : nullptr, train ? in.grad[3]->data : nullptr, N, E0, E1, train, s), "nn#blinear+run");
-                skip_next_ = true; skip_cnt_ = 2;
-                return in.data;
-            }
-            if (tg) chk(t4k_loss_linear_bwd(in.data, in.grad[0]->data, (float *)dy, tg, at(-2).data, in.data, nullptr, nullptr,
-                                        in.grad[2]->data, in.grad[3]->data, N, E0, E1, train, s), "nn#bprep+blinear");
-            else if (i == 0 && train && use_lazy_dx0 && fused && !capturing_ && !use_graphs && in.grad[2] && in.grad[3] && (long)E0 * E1 >= 16384) {
-                // the net's first layer: nobody reads dX0 in a training loop - dW | dB now, dX0 = dY W when a word asks (materialize_dx0)
-                Tensor *holder = nullptr;
-                for (int k = 1; k < (int)layer.size() && !holder; k++) if (at(k).data == dy) holder = &at(k);
-                if (holder) {
-                    chk(t4k_linear_bwd(in.data, in.grad[0]->data, dy, nullptr, in.grad[2]->data, in.grad[3]->data, N, E0, E1, 1, s), "nn#blinear dW");
-                    dx0_stale_ = true; dx0_lin_ = true; w0_saved_ = false; dx0_dy_ = dy; dx0_dy_t_ = holder;
-                    in.stale_owner = this; in.grad[0]->stale_owner = this; holder->stale_owner = this;
-                    return in.data;
-                }
-                chk(t4k_linear_bwd(in.data, in.grad[0]->data, dy, in.data, in.grad[2]->data, in.grad[3]->data, N, E0, E1, train, s), "nn#blinear");
-            }
-            else chk(t4k_linear_bwd(in.data, in.grad[0]->data, dy, in.data, in.grad[2]->data, in.grad[3]->data, N, E0, E1, train, s), "nn#blinear");
-            return in.data;
-        }
+        if (!gx) return blinear(i, in, out, dy, tg);    // single stream: reference order (dW reads X, then dX overwrites it)
+        const int N = in.N(), E0 = (int)out.HWC(), E1 = (int)in.HWC();
         if (train) chk(t4k_linear_bwd(in.data, in.grad[0]->data, dy, nullptr, in.grad[2]->data, in.grad[3]->data, N, E0, E1, 1, fork()), "nn#blinear dW");
         chk(t4k_linear_bwd(in.data, in.grad[0]->data, dy, gx->data, nullptr, nullptr, N, E0, E1, 0, s), "nn#blinear dX");
         lazy_copy(gx->data, in);                        // dX lands in X's buffer (backprop.cu:240) once dW has read X
-        return gx->data;
+        return { gx->data };
     }
     case T4K_L_FLATTEN: case T4K_L_SIGMOID: case T4K_L_SOFTMAX: case T4K_L_LOGSMAX:
-        lazy_copy(dy, in); return dy;                   // pass-through (:122,129-131)
+        lazy_copy(dy, in); return { dy };               // pass-through (:122,129-131)
     case T4K_L_RELU: case T4K_L_TANH: case T4K_L_SELU: case T4K_L_LEAKYRL: case T4K_L_ELU: case T4K_L_DROPOUT:
         chk(t4k_tt_op(T4K_MUL, dy, in.grad[4]->data, in.data, (long)in.numel, s), "nn#bactivate"); break;
     case T4K_L_AVGPOOL: case T4K_L_MAXPOOL: case T4K_L_MINPOOL:
@@ -967,7 +857,67 @@ const float *Model::bstep(int i, Tensor &in, Tensor &out, const float *dy, bool 
         in.map(T4K_SCALE, (DU)(in.stride[0] * in.stride[0])); break;
     default: hprintf("nn#bstep layer=%d not supported\n", fn);
     }
-    return in.data;
+    return { in.data };
+}
+// Linear layer i backward on one stream, and what rides in its launch: the pending `out -= target` (tg) and the backward of the group in front of the
+// layer - mask-multiply layers and, behind a conv stack or in an MLP, the linear layer in front of those.  The cases, widest group first.
+Model::Back Model::blinear(int i, Tensor &in, Tensor &out, const float *dy, const float *tg) {
+    t4k_stream_t s = stream();
+    const int N = in.N(), E0 = (int)out.HWC(), E1 = (int)in.HWC();
+    const bool fused = use_fusion && !(trace && *trace);
+    float *X = in.data, *W = in.grad[0]->data, *dW = train ? in.grad[2]->data : nullptr, *dB = train ? in.grad[3]->data : nullptr, *dY = (float *)dy;
+    float *out2 = tg ? at(-2).data : nullptr;           // the pass-through `in = out` of the last layer goes with `out -= target`
+    auto masks_run = [&](int k, int count) { return fused && k >= 0 && run_of_[k] >= 0 && runs_[run_of_[k]].count == count && runs_[run_of_[k]].masks_only() ? &runs_[run_of_[k]] : nullptr; };
+    // a lone mask-multiply layer (dropout, relu, ...) right in front of this linear layer: its backward rides along
+    if (fused && i > 0 && run_of_[i - 1] >= 0 && runs_[run_of_[i - 1]].count == 1 && !runs_[run_of_[i - 1]].blk.pool_layer && runs_[run_of_[i - 1]].blk.pre_layer) {
+        Tensor &prev = at(i - 1);
+        // ... and when the layer in front of THAT is the linear layer behind a conv stack's flatten (the t4_30a/30e classifier), its backward
+        // joins the launch too: every GEMM tile recomputes the rows of dY1 it needs (10 terms each), so nothing waits for the head (t4k_mlp_head_bwd)
+        if (tg && use_head_bwd && train && i >= 3 && at(i - 2).grad_fn == T4K_L_LINEAR && stacks_on() && stack_end_[i - 3] >= 0 &&
+            at(i - 2).grad[2] && at(i - 2).grad[3] && t4k_mlp_head_bwd_ok(N, (int)at(i - 2).HWC(), E1, E0)) {
+            Tensor &big = at(i - 2);
+            chk(t4k_mlp_head_bwd(X, W, dY, tg, out2, prev.grad[4]->data, prev.data, in.grad[2]->data, in.grad[3]->data,
+                                 big.data, big.grad[0]->data, big.grad[2]->data, big.grad[3]->data, N, (int)big.HWC(), E1, E0, s), "nn#bhead+blinear");
+            return { big.data, 2, i - 2 };
+        }
+        if (tg) chk(t4k_loss_linear_bwd(X, W, dY, tg, out2, X, prev.grad[4]->data, prev.data, dW, dB, N, E0, E1, train, s), "nn#bprep+blinear+act");
+        else    chk(t4k_linear_bwd2(X, W, dy, X, prev.grad[4]->data, prev.data, dW, dB, N, E0, E1, train, s), "nn#blinear+act");
+        return { prev.data, 1 };
+    }
+    // a lone activation that multiplies by its derivative mask (relu, tanh, leakyrelu, ... - not a fused run, not the
+    // pass-through sigmoid) in front of a layer too large for the head kernel: the multiply rides in the dX epilogue
+    if (fused && i > 0 && !tg && run_at_[i - 1] < 0 && is_mact(at(i - 1).grad_fn)) {
+        Tensor &prev = at(i - 1);
+        t4k_poolblock b1; memset(&b1, 0, sizeof(b1)); b1.KS = 1;
+        b1.pre_layer = prev.grad_fn; b1.pre_alpha = prev.xparm; b1.pre_mask = prev.grad[4]->data; b1.pre_out = X;
+        chk(t4k_linear_block_bwd(X, W, dY, nullptr, nullptr, X, &b1, prev.data, dW, dB, N, E0, E1, train, s), "nn#blinear+act");
+        return { prev.data, 1 };
+    }
+    // a run of two mask-multiply layers (`leakyrelu dropout`) in front: its backward rides along as well
+    if (const Run *r = masks_run(i - 2, 2)) {
+        // the linear layer in front of that run joins the launch when it is the net's first layer or has such a run of its own in front (the GAN
+        // discriminator: linear, leakyrelu, dropout, linear, leakyrelu, dropout, linear, sigmoid) - t4k_mlp_block_bwd, see t4k_mlp_head_bwd
+        // (measured on the GAN nets, N = 256, 256-wide runs: 28.5 us against 9 + 11.7 us apart - re-reading two 256 KB masks per tile costs more than
+        // reading the finished dY1; opt-in with T4_HEAD_BWD=2)
+        static const bool runs_too = env_long("T4_HEAD_BWD", 1) >= 2;
+        if (tg && use_head_bwd && runs_too && i >= 3 && at(i - 3).grad_fn == T4K_L_LINEAR && (!train || (at(i - 3).grad[2] && at(i - 3).grad[3]))) {
+            Tensor &big = at(i - 3);
+            const Run *r1 = masks_run(i - 5, 2);
+            if ((r1 || i == 3) && t4k_mlp_head_bwd_ok(N, (int)big.HWC(), E1, E0)) {
+                chk(t4k_mlp_block_bwd(X, W, dY, tg, out2, &r->blk, at(i - 2).data, dW, dB,
+                                      big.data, big.grad[0]->data, r1 ? &r1->blk : nullptr, r1 ? at(i - 5).data : nullptr,
+                                      train ? big.grad[2]->data : nullptr, train ? big.grad[3]->data : nullptr, N, (int)big.HWC(), E1, E0, train, s), "nn#bhead+run+blinear");
+                return { r1 ? at(i - 5).data : big.data, r1 ? 5 : 3, i - 3 };
+            }
+        }
+        chk(t4k_linear_block_bwd(X, W, dY, tg, out2, X, &r->blk, at(i - 2).data, dW, dB, N, E0, E1, train, s), "nn#blinear+run");
+        return { at(i - 2).data, 2 };
+    }
+    if (tg) chk(t4k_loss_linear_bwd(X, W, dY, tg, out2, X, nullptr, nullptr, in.grad[2]->data, in.grad[3]->data, N, E0, E1, train, s), "nn#bprep+blinear");
+    else if (i == 0 && train && use_lazy_dx0 && fused && !capturing_ && !use_graphs && in.grad[2] && in.grad[3] && (long)E0 * E1 >= 16384 && offer_dx0(dy, false))
+        chk(t4k_linear_bwd(X, W, dy, nullptr, in.grad[2]->data, in.grad[3]->data, N, E0, E1, 1, s), "nn#blinear dW");   // the net's first layer: dW | dB now, dX0 = dY W when a word asks
+    else chk(t4k_linear_bwd(X, W, dy, X, in.grad[2]->data, in.grad[3]->data, N, E0, E1, train, s), "nn#blinear");
+    return { X };
 }
 
 // ---------------------------------------------------------------- optimizers

@@ -297,7 +297,9 @@ private:
     Tensor &VEC(uint64_t n);
     void RAND(Tensor &t, DU scale);
     const float *fstep(Tensor &in, Tensor &out, const float *x);
-    const float *bstep(int i, Tensor &in, Tensor &out, const float *dy, bool last);
+    struct Back { const float *dy; int covered = 0, also = -1; };   // a backward launch: where dX lives, how many ops in front of its own it covered, a second layer whose dW | dB it completed (-1: none)
+    Back bstep(int i, Tensor &in, Tensor &out, const float *dy, bool last, const float *tg);
+    Back blinear(int i, Tensor &in, Tensor &out, const float *dy, const float *tg);   // a linear layer and the groups in front that ride in its launch
     void run_forward(Tensor &input);
     void run_backward(Tensor &tgt);
     Model &gradient(const char *nm, Optim op, DU lr, DU b1, DU b2, DU wd);
@@ -315,17 +317,20 @@ private:
     t4k_stream_t side_ = nullptr;
     std::vector<t4k_event_t> ev_; size_t ev_i_ = 0;
     std::vector<Tensor *> gx_;                 // per-layer dX scratch of linear layers
-    struct Run { int first = 0, count = 1; t4k_poolblock blk; };   // fused element-wise run starting at layer `first`
-    std::vector<int> run_of_;                  // layer index -> index into runs_ or -1
+    struct Run {                               // fused element-wise run starting at layer `first`; its pooled stage is [N, H1, W1, C] -> [N, H0, W0, C] (the same without a pool)
+        int first = 0, count = 1, N = 0, H1 = 0, W1 = 0, H0 = 0, W0 = 0, C = 0; t4k_poolblock blk;
+        bool masks_only() const { return !blk.pool_layer && !blk.copy_out; }   // mask-multiply layers only: no pool, no flatten
+    };
+    std::vector<int> run_of_, run_at_;         // layer index -> index into runs_ of the run that STARTS there / that COVERS it, or -1
     std::vector<Run> runs_;
     void plan_runs();
     static bool use_fusion;                    // T4_FUSE=0 keeps one launch per layer
     std::vector<char> stack_fresh_;            // per first-op index: the latest forward took the stack kernel (so what it saved for the backward is current)
-    std::vector<int> stack_end_;              // last op of a conv stack -> its first op (run_backward), rebuilt after finalize
+    std::vector<int> stack_end_;              // last op of a conv stack -> its first op, or -1: what stack_at admits (finalize); a step reads it only under stacks_on()
+    bool stacks_on() const { return use_fusion && use_stack && !(trace && *trace) && !concurrent(); }   // this step takes the conv-stack launches
     double tl_ = 0;                                      // trace levels: clock of the previous layer's line
     bool stack_single_ = true;    // single-stage stacks too (round 3: slower, off; round 4, with the lazy first-layer dX and the fold inside the optimizer: the t4_40a net nn_c 0.0637 -> 0.0459 ms per step at N = 128)
     static bool use_head_bwd;                  // T4_HEAD_BWD=0: head backward and the linear layer in front of it as separate launches
-    int also_ready_ = -1;                      // a second layer whose gradients the last bstep launch produced (run_backward reports it)
     static bool use_stack_head;                // T4_STACK_HEAD=0: conv stack and classifier head as separate launches
     static bool use_stack;                     // T4_STACK=0: no sample-resident conv stacks (csrc/conv_stack.hip)
     static bool use_lazy_dx0;                  // T4_LAZY_DX0=0: a conv stack's backward always computes the first layer's dX (default: on demand, materialize_dx0)
@@ -338,6 +343,8 @@ private:
     Tensor *dx0_dy_t_ = nullptr, *w0_save_ = nullptr;
     bool dp_in_opt_ = false;                   // this optimizer call sums the gradient slab over the ranks itself (one-shot peer exchange, t4k_opt_step_dp)
     void clear_dx0_marks();
+    bool offer_dx0(const float *dy, bool conv);   // per-layer first layer: find the tensor that holds dY, set the marks; false: no holder, dX0 is stored now
+    bool fill_stack_head(int j, Tensor &input, t4k_stack_head &hd);   // the classifier head at layer j for t4k_conv_stack_head_*; true: one-hot rows and hit flags ride along
     static bool use_opt_fold;                  // T4_OPT_FOLD=0: the conv stack's dF | dB partial fold as a launch of its own (default: inside the optimizer launch, t4k_opt_step)
     // sample-resident conv stack starting at layer i: [conv + run] x ns (stages filled for the C-ABI); ops = layers it covers
     int  stack_at(int i, t4k_conv_stage *st, int &ops);
@@ -359,9 +366,6 @@ private:
     void dp_flush();
     void dp_begin_backward();
     void dp_finish();
-    Tensor *prep_tgt_ = nullptr;               // `out -= target` pending: the last linear layer's backward launch performs it
-    int  skip_cnt_ = 1;                        // ... how many ops in front it covered
-    bool skip_next_ = false;                   // set by bstep when it also ran the backward of the op in front
 };
 
 // ---------------------------------------------------------------- printing
