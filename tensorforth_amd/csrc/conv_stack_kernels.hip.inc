@@ -47,9 +47,14 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 
 #define CS_THREADS 512
 #define CS_WAVES 8
+// the banded backward (cs_bwd_b) runs 16 waves: in the middle phase of a stage waves 0 .. 7 take the dF items and waves 8 .. 15 the stage's dX, side by side
+#define CS_BTHREADS 1024
+#define CS_BWAVES 16
 // lab hook (tools/experiments/cs_lab.hip, T4K_STACK_PROF_PTR): s_memtime stamps of wave 0 of every workgroup, 32 per workgroup
 #define CS_STAMP_P(pp, k) do { if ((pp) && threadIdx.x == 0) (pp)[(blockIdx.x * gridDim.y + blockIdx.y) * 32 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
 #define CS_STAMP(k) do { if (p.prof && threadIdx.x == 0) p.prof[(blockIdx.x * gridDim.y + blockIdx.y) * 32 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
+// the same from the first lane of wave 8: begin / end of the dX role of the banded backward (stamps 24 + 2 S, 25 + 2 S)
+#define CS_STAMP_X(k) do { if (p.prof && threadIdx.x == CS_THREADS) p.prof[(blockIdx.x * gridDim.y + blockIdx.y) * 32 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
 
 struct Shape { int H, W, C1, C0, K, pre, pool, post, KS; float a_pre, a_post; int flat; };
 constexpr Shape SH[CS_NS] = { CS_SHAPES };
@@ -154,11 +159,16 @@ template <int CV> __device__ __forceinline__ void lstore(float *p, const float *
 // tiles at once when there are more tiles than waves, and otherwise splits the tile's k steps between two accumulators (added at the end) -
 // two tiles per wave would leave half the waves idle (the 20 -> 10 dX of the LeNet backward: 7 tiles, 4 busy waves, 5.6 k cycles).
 constexpr int conv_mt(int rows, int w) { return (rows * w + 15) / 16; }
-template <int W, int CIN, int COUT, int K, int JPK, int NTK, int NCK, int MTMAX = 1 << 20, int RSIN = 0>
+// WV0 / WVN: the waves that share the tiles (the dX role of the banded backward: waves 8 .. 15 of 16); only those waves may call.
+// PIPE = false (banded backward, whose 1024-thread workgroup may use 128 registers): no double buffer over the filter rows - a row's operands are read in
+// chunks of at most 64 registers, each chunk in front of its MFMAs.  The MFMAs and their order are the same: same sums.
+constexpr int conv_tpw(int ntk, int mtmax, int wvn) { return (ntk == 1 && mtmax > wvn) ? 2 : 1; }
+constexpr bool conv_pipe_fits(int jpk, int ntk, int mtmax, int wvn) { return 2 * (jpk / 4) * (conv_tpw(ntk, mtmax, wvn) + ntk) <= 96; }
+template <int W, int CIN, int COUT, int K, int JPK, int NTK, int NCK, int MTMAX = 1 << 20, int RSIN = 0, int WV0 = 0, int WVN = CS_WAVES, bool PIPE = true>
 __device__ __forceinline__ void conv_mfma(const float *In, const float *Wl, const float *bias, float *Out, int nr) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, kq = lane >> 4;
+    const int lane = threadIdx.x & 63, wave = (threadIdx.x >> 6) - WV0, i = lane & 15, kq = lane >> 4;
     constexpr int RS = RSIN ? RSIN : (W + K - 1) * CIN, STEPS = JPK / 4;     // RSIN: the window's row stride when it is padded (backward windows)
-    constexpr int TPW = (NTK == 1 && MTMAX > CS_WAVES) ? 2 : 1;      // M tiles a wave works on at once
+    constexpr int TPW = conv_tpw(NTK, MTMAX, WVN);                  // M tiles a wave works on at once
     constexpr int QC = (NTK == 1 && TPW == 1) ? 2 : 1;              // accumulators per tile (k steps alternate between them)
     // ROWT (backward windows of rows shorter than a tile, LeNet's 14-wide dX conv): a tile is ONE window row, lanes W .. 15 read on into the row's right
     // border and are not stored.  16 consecutive pixels of a row sit CIN floats apart - with CIN = 20 the lanes (i, kq) cover the 64 banks exactly once -
@@ -169,7 +179,7 @@ __device__ __forceinline__ void conv_mfma(const float *In, const float *Wl, cons
     float bb[NTK];
 #pragma unroll
     for (int n = 0; n < NTK; n++) bb[n] = (bias && n * 16 + i < COUT) ? bias[n * 16 + i] : 0.f;
-    for (int mt0 = wave * TPW; mt0 < MT; mt0 += CS_WAVES * TPW) {
+    for (int mt0 = wave * TPW; mt0 < MT; mt0 += WVN * TPW) {
         const float *a0[TPW];
 #pragma unroll
         for (int t = 0; t < TPW; t++) {
@@ -190,6 +200,40 @@ __device__ __forceinline__ void conv_mfma(const float *In, const float *Wl, cons
         // Software pipeline over the filter rows, pinned with scheduling barriers: the LDS reads of row ky+1 are ISSUED in front of the MFMAs of
         // row ky (left alone, hipcc sinks every read next to its MFMA to save registers and waits lgkmcnt(0) in front of each pair - one exposed
         // LDS round trip per two MFMAs, 24 per tile of the 10 -> 20 layer).  Reads return in order, so the waits become counted.
+        if constexpr (!PIPE) {
+            constexpr int QCH = cmax(1, cmin(STEPS, 64 / (TPW + NTK))), NCH = (STEPS + QCH - 1) / QCH;
+#pragma unroll
+            for (int ky = 0; ky < K; ky++)
+#pragma unroll
+                for (int ch = 0; ch < NCH; ch++) {
+                    float av[TPW][QCH], bv[QCH][NTK];
+#pragma unroll
+                    for (int qq = 0; qq < QCH; qq++) {
+                        const int q = ch * QCH + qq;
+                        if (q < STEPS) {
+#pragma unroll
+                            for (int t = 0; t < TPW; t++) av[t][qq] = a0[t][ky * RS + q * 4];
+#pragma unroll
+                            for (int n = 0; n < NTK; n++) bv[qq][n] = b0[(ky * JPK + q * 4) * NCK + n * 16];
+                        }
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int qq = 0; qq < QCH; qq++) {
+                        const int q = ch * QCH + qq;
+                        if (q < STEPS) {
+#pragma unroll
+                            for (int t = 0; t < TPW; t++)
+#pragma unroll
+                                for (int n = 0; n < NTK; n++) {
+                                    if (QC == 2 && ((ky * STEPS + q) & 1)) acc2[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[t][qq], bv[qq][n], acc2[n], 0, 0, 0);
+                                    else acc[t][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[t][qq], bv[qq][n], acc[t][n], 0, 0, 0);
+                                }
+                        }
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+        } else {
         float av[2][TPW][STEPS], bv[2][STEPS][NTK];
         auto load_row = [&](int buf, int ky) {
 #pragma unroll
@@ -215,6 +259,7 @@ __device__ __forceinline__ void conv_mfma(const float *In, const float *Wl, cons
                         else acc[t][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[ky & 1][t][q], bv[ky & 1][q][n], acc[t][n], 0, 0, 0);
                     }
             __builtin_amdgcn_sched_barrier(0);
+        }
         }
         if (QC == 2) {
 #pragma unroll
@@ -889,7 +934,8 @@ constexpr int dx_size() { int m = 0; for (int s = 0; s < CS_NS; s++) m = cmax(m,
 constexpr int df_units(int s) { return ((SH[s].K * SH[s].K * SH[s].C1 + 15) / 16) * NT(s); }          // (tile of the K*K*C1 taps, tile of c0)
 constexpr int cgcd(int a, int b) { return b == 0 ? a : cgcd(b, a % b); }
 constexpr int df_mgn_(int s) { const int mtt = (SH[s].K * SH[s].K * SH[s].C1 + 15) / 16, mg = cmin(mtt, 3); return (mtt + mg - 1) / mg; }
-constexpr int df_rg(int s) { return cmin(CS_WAVES / cgcd(df_mgn_(s), CS_WAVES), cmax(1, SH[s].W / 2)); }   // pixel-column groups per M-tile block: work items a multiple of the wave count
+constexpr int DF_WAVES = 8;                                                                        // waves that take dF items - in cs_bwd the whole workgroup, in cs_bwd_b its dF role: the slot geometry is the same in both
+constexpr int df_rg(int s) { return cmin(DF_WAVES / cgcd(df_mgn_(s), DF_WAVES), cmax(1, SH[s].W / 2)); }   // pixel-column groups per M-tile block: work items a multiple of the wave count
 constexpr int slot_size() { int m = 0; for (int s = 0; s < CS_NS; s++) { const int mtt = (SH[s].K * SH[s].K * SH[s].C1 + 15) / 16, mg = cmin(mtt, 3); m = cmax(m, df_mgn_(s) * df_rg(s) * mg * NT(s) * 256 + 16 * SH[s].C0); } return pad4(m); }
 constexpr int do_off() { return wb_off(CS_NS - 1) + wb_size(CS_NS - 1); }
 constexpr int xw_off() { return do_off() + do_size(); }
@@ -902,18 +948,20 @@ template <int S> __device__ __forceinline__ int wl_bwd(int e) {       // filter 
     const int c0 = e % C0, t = e / C0, kx = t % K, t2 = t / K, ky = t2 % K, c1 = t2 / K;
     return (ky * JPb(S) + kx * C0 + c0) * NCb(S) + c1;
 }
-template <int S> __device__ __forceinline__ void load_filter_b(const BwdArgs &p, float (&vf)[CS_NS][8]) {
+// NTH = threads of the workgroup, VFQ = filter elements a thread stages (8 x 512 = 4 x 1024 = the largest filter the host admits)
+template <int S, int NTH = CS_THREADS, int VFQ = 8> __device__ __forceinline__ void load_filter_b(const BwdArgs &p, float (&vf)[CS_NS][VFQ]) {
     if constexpr (S < CS_NS) {
+        static_assert(nF(S) <= VFQ * NTH, "filter too large for the register-staged path");
 #pragma unroll
-        for (int q = 0; q < (nF(S) + CS_THREADS - 1) / CS_THREADS; q++) { const int e = threadIdx.x + q * CS_THREADS; vf[S][q] = e < nF(S) ? p.st[S].F[e] : 0.f; }
-        load_filter_b<S + 1>(p, vf);
+        for (int q = 0; q < (nF(S) + NTH - 1) / NTH; q++) { const int e = threadIdx.x + q * NTH; vf[S][q] = e < nF(S) ? p.st[S].F[e] : 0.f; }
+        load_filter_b<S + 1, NTH, VFQ>(p, vf);
     }
 }
-template <int S> __device__ __forceinline__ void put_filter_b(float *L, const float (&vf)[CS_NS][8]) {
+template <int S, int NTH = CS_THREADS, int VFQ = 8> __device__ __forceinline__ void put_filter_b(float *L, const float (&vf)[CS_NS][VFQ]) {
     if constexpr (S < CS_NS) {
 #pragma unroll
-        for (int q = 0; q < (nF(S) + CS_THREADS - 1) / CS_THREADS; q++) { const int e = threadIdx.x + q * CS_THREADS; if (e < nF(S)) L[wb_off(S) + ((SH[S].C1 <= 4 && nF(S) <= 160) ? e : wl_bwd<S>(e))] = vf[S][q]; }   // few input channels, small filter: verbatim (dx_valu)
-        put_filter_b<S + 1>(L, vf);
+        for (int q = 0; q < (nF(S) + NTH - 1) / NTH; q++) { const int e = threadIdx.x + q * NTH; if (e < nF(S)) L[wb_off(S) + ((SH[S].C1 <= 4 && nF(S) <= 160) ? e : wl_bwd<S>(e))] = vf[S][q]; }   // few input channels, small filter: verbatim (dx_valu)
+        put_filter_b<S + 1, NTH, VFQ>(L, vf);
     }
 }
 
@@ -924,7 +972,7 @@ template <int S> __device__ __forceinline__ void put_filter_b(float *L, const fl
 // Pooled rows [ql, qh) are processed (dY in LDS and the dO window start at row ql), rows [pol, poh) are stored.  SAVED: the pool's winning
 // cell comes from the forward's arg-max codes instead of the forward values in the pool's input buffer (banded backward: a neighbouring
 // band overwrites those in place).
-template <int S, bool SAVED>
+template <int S, bool SAVED, int NTH = CS_THREADS>
 __device__ __forceinline__ void run_bwd(const BwdStage &g, const float *dY, bool dy_global, float *dOw, int img, int ql = 0, int qh = H0(S), int pol = 0, int poh = H0(S)) {
     constexpr int W = SH[S].W, C = SH[S].C0, KS = SH[S].KS, K = SH[S].K, PD = K / 2, PRE = SH[S].pre, POOL = SH[S].pool, POST = SH[S].post;
     constexpr int CV = vw_of(C), CQ = C / CV, RSO = RSOw(S), NW = POOL ? 4 : 1;
@@ -934,7 +982,7 @@ __device__ __forceinline__ void run_bwd(const BwdStage &g, const float *dY, bool
     float *Rb = SH[S].flat ? (POST ? g.R : (POOL ? g.Q : (PRE ? g.P : g.O))) : nullptr;     // flatten: in = out
     float *Qb = POOL ? g.Q : (PRE ? g.P : g.O);                                             // the post activation's input buffer
     float *Pb = PRE ? g.P : g.O;                                                            // pool input buffer: forward values -> dX
-    for (int it = threadIdx.x; it < NIT; it += CS_THREADS) {
+    for (int it = threadIdx.x; it < NIT; it += NTH) {
         const int cq = it % CQ, t = it / CQ, j0 = t % W0(S), ir = t / W0(S), i0 = ql + ir, c = cq * CV;
         const int lo = (i0 * W0(S) + j0) * C + c, lloc = (ir * W0(S) + j0) * C + c;
         const long zo = e0 + lo;
@@ -1007,10 +1055,13 @@ constexpr int LAB_SKIP = 0;
 #endif
 constexpr int df_mg(int s) { return cmin((SH[s].K * SH[s].K * SH[s].C1 + 15) / 16, 3); }
 constexpr int df_mgn(int s) { return ((SH[s].K * SH[s].K * SH[s].C1 + 15) / 16 + df_mg(s) - 1) / df_mg(s); }
+// Two parts with a workgroup barrier between them: df_items (waves 0 .. DF_WAVES - 1: the MFMA items into the LDS slots, dB column sums) and
+// df_fold (NTH threads: fold of the slots in a fixed order, partial-row stores).  cs_bwd runs them back to back (df_partial); cs_bwd_b runs the
+// items beside the stage's dX and the fold in the store phase behind the barrier the two share.
 template <int S, int NRMAX>
-__device__ __forceinline__ void df_partial(const float *Xw, const float *dOw, float *slots, float *part, u64 *prof, int nrows = SH[S].H) {
+__device__ __forceinline__ void df_items(const float *Xw, const float *dOw, float *slots, u64 *prof, int nrows = SH[S].H) {
     constexpr int W = SH[S].W, C1 = SH[S].C1, C0 = SH[S].C0, K = SH[S].K, PD = K / 2, KC = K * C1, TAPS = K * KC;
-    constexpr int MTT = (TAPS + 15) / 16, NTK = NT(S), MG = df_mg(S), MGN = df_mgn(S), RG = df_rg(S), BLK = MG * NTK * 256;
+    constexpr int NTK = NT(S), MG = df_mg(S), MGN = df_mgn(S), RG = df_rg(S), BLK = MG * NTK * 256;
     constexpr int RSX = RSXw(S), RSO = RSOw(S), YQ = (NRMAX + 3) / 4;      // row quads: MFMA k = 4 consecutive rows of one pixel column
     constexpr bool ONES = (TAPS & 15) != 0;          // a spare row in the last M tile: fed with 1.0 it yields dB = the column sums of dO for free
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, kq = lane >> 4;
@@ -1020,7 +1071,7 @@ __device__ __forceinline__ void df_partial(const float *Xw, const float *dOw, fl
     int yoff_x[YQ], yoff_o[YQ]; bool rok[YQ];
 #pragma unroll
     for (int yq = 0; yq < YQ; yq++) { const int y = yq * 4 + kq; rok[yq] = y < nrows; const int yc = min(y, nrows - 1); yoff_x[yq] = yc * RSX; yoff_o[yq] = yc * RSO; }
-    for (int item = wave; item < MGN * RG; item += CS_WAVES) {
+    for (int item = wave; item < MGN * RG; item += DF_WAVES) {
         const int mgi = item / RG, rg = item - mgi * RG;
         const float *a0[MG]; bool one[MG];
 #pragma unroll
@@ -1081,11 +1132,17 @@ __device__ __forceinline__ void df_partial(const float *Xw, const float *dOw, fl
         for (int pq = gq; pq < nrows * W; pq += 16) { const int y = pq / W, x = pq - y * W; sacc += dOw[(y + PD) * RSO + (x + PD) * C0 + c]; }
         dbs[gq * C0 + c] = sacc;
     }
-    lds_barrier();
+}
+template <int S, int NTH = CS_THREADS>
+__device__ __forceinline__ void df_fold(const float *slots, float *part, u64 *prof) {
+    constexpr int C1 = SH[S].C1, C0 = SH[S].C0, K = SH[S].K, KC = K * C1, TAPS = K * KC;
+    constexpr int MTT = (TAPS + 15) / 16, NTK = NT(S), MG = df_mg(S), MGN = df_mgn(S), RG = df_rg(S), BLK = MG * NTK * 256;
+    constexpr bool ONES = (TAPS & 15) != 0;
+    const float *dbs = slots + MGN * RG * BLK;
     if (S == CS_NS - 1) CS_STAMP_P(prof, 18);
     // fold the row groups (fixed order) and scatter into the filter's own layout ((c1*K + ky)*K + kx)*C0 + c0, VF consecutive c0 per lane
     constexpr int VF = (C0 & 3) == 0 ? 4 : 1;
-    for (int e4 = threadIdx.x; e4 < ((LAB_SKIP & 128) ? 0 : MGN * BLK / VF); e4 += CS_THREADS) {
+    for (int e4 = threadIdx.x; e4 < ((LAB_SKIP & 128) ? 0 : MGN * BLK / VF); e4 += NTH) {
         const int e = e4 * VF, mgi = e / BLK, r1 = e - mgi * BLK, mn = r1 >> 8, m = mn / NTK, n = mn - m * NTK, rw = (r1 >> 4) & 15, mm = 4 * (rw & 3) + (rw >> 2), nn = r1 & 15;   // block row rw holds D row mm
         const int tap = ((mgi * MG + m) * 16) + mm, c0 = n * 16 + nn;
         if (mgi * MG + m < MTT && tap <= TAPS && c0 < C0 && (tap < TAPS || ONES)) {
@@ -1109,22 +1166,33 @@ __device__ __forceinline__ void df_partial(const float *Xw, const float *dOw, fl
         part[nF(S) + threadIdx.x] = v;
     }
 }
+template <int S, int NRMAX>
+__device__ __forceinline__ void df_partial(const float *Xw, const float *dOw, float *slots, float *part, u64 *prof, int nrows = SH[S].H) {
+    df_items<S, NRMAX>(Xw, dOw, slots, prof, nrows);
+    lds_barrier();
+    df_fold<S>(slots, part, prof);
+}
 
 // dX of a conv layer with FEW input channels (C1 <= 4: the image layer) on the vector ALUs: an MFMA tile would be 1..4 useful columns
 // of 16.  A lane owns one pixel: dX[y, x, c1] = sum over (ky, kx, c0) F[c1, ky, kx, c0] * dO[y+ky-P, x+kx-P, c0] (the reference's un-flipped
 // correlation, nmath.tcu:304-324); the (kx, c0) run of a filter row is contiguous in the dO window, the weights are LDS broadcasts.
-template <int S>
+// T0 / TN: the threads that share the pixels (the dX role of the banded backward: threads 512 .. 1023); only those threads may call.
+// ROWW: the weights are read one filter row at a time inside the pixel loop instead of all K rows once per lane - a third of the registers (the banded
+// backward's 1024-thread workgroup may use 128; its bands are at most a pixel or two per thread, so nothing is read twice that was read once before).
+template <int S, int T0 = 0, int TN = CS_THREADS, bool ROWW = false>
 __device__ __forceinline__ void dx_valu(const float *dOw, const float *Wf, float *dXb, int nrows = SH[S].H) {
     constexpr int H = SH[S].H, W = SH[S].W, C1 = SH[S].C1, C0 = SH[S].C0, K = SH[S].K, KC0 = K * C0, RSO = RSOw(S);
     constexpr bool PAIR = (C0 & 1) == 0;                  // (x * C0) and the row stride are even: 8-byte LDS reads
-    float wv[C1][K][KC0];                                 // the filter, once per lane (the same for all of them: LDS broadcasts)
+    float wv[C1][ROWW ? 1 : K][KC0];                      // the filter, once per lane (the same for all of them: LDS broadcasts)
+    if (!ROWW) {
 #pragma unroll
-    for (int c1 = 0; c1 < C1; c1++)
+        for (int c1 = 0; c1 < C1; c1++)
 #pragma unroll
-        for (int ky = 0; ky < K; ky++)
+            for (int ky = 0; ky < K; ky++)
 #pragma unroll
-            for (int j = 0; j < KC0; j++) wv[c1][ky][j] = Wf[(c1 * K + ky) * KC0 + j];
-    for (int pix = threadIdx.x; pix < nrows * W; pix += CS_THREADS) {
+                for (int j = 0; j < KC0; j++) wv[c1][ky][j] = Wf[(c1 * K + ky) * KC0 + j];
+    }
+    for (int pix = threadIdx.x - T0; pix < nrows * W; pix += TN) {
         const int y = pix / W, x = pix - y * W;
         float acc[C1];
 #pragma unroll
@@ -1132,6 +1200,12 @@ __device__ __forceinline__ void dx_valu(const float *dOw, const float *Wf, float
 #pragma unroll
         for (int ky = 0; ky < K; ky++) {
             const float *d = dOw + (y + ky) * RSO + x * C0;
+            if (ROWW) {
+#pragma unroll
+                for (int c1 = 0; c1 < C1; c1++)
+#pragma unroll
+                    for (int j = 0; j < KC0; j++) wv[c1][0][j] = Wf[(c1 * K + ky) * KC0 + j];
+            }
             float dv[KC0];
             if (PAIR) {
 #pragma unroll
@@ -1143,7 +1217,7 @@ __device__ __forceinline__ void dx_valu(const float *dOw, const float *Wf, float
 #pragma unroll
             for (int j = 0; j < KC0; j++)
 #pragma unroll
-                for (int c1 = 0; c1 < C1; c1++) acc[c1] = fmaf(wv[c1][ky][j], dv[j], acc[c1]);
+                for (int c1 = 0; c1 < C1; c1++) acc[c1] = fmaf(wv[c1][ROWW ? 0 : ky][j], dv[j], acc[c1]);
         }
 #pragma unroll
         for (int c1 = 0; c1 < C1; c1++) dXb[pix * C1 + c1] = acc[c1];
@@ -1237,8 +1311,14 @@ constexpr int bdx_off(int which) { return bxw_off() + bxw_size() + which * bdx_s
 constexpr int bslot_off() { return bdx_off(2); }
 constexpr int bwdb_lds_floats() { return bslot_off() + slot_size(); }
 
+// The workgroup has CS_BWAVES = 16 waves.  The phases whose loops stride by the thread count (window zero fill, run backward, X-window fill, filter
+// staging, the store phase) run on all of them.  The MIDDLE phase of a stage is two independent latency chains - the dF items (LDS round trip -> MFMA burst per
+// item) and the stage's dX (which alone feeds the next stage) - and runs them side by side: waves 0 .. 7 take the dF items exactly as the 8 waves of cs_bwd
+// do (item = wave, wave + 8, ...: same slots, same sums), waves 8 .. 15 the dX.  Lab stamps (thread 0 unless noted), per stage S: 1 + 8 S windows zeroed,
+// 2 + 8 S run backward done, 3 + 8 S roles begin, 4 + 8 S dF items done, 5 + 8 S past the shared barrier, 6 + 8 S fold done, 7 + 8 S dX copied out;
+// from the first lane of wave 8: 24 + 2 S dX role begins, 25 + 2 S dX role done.
 template <int S>
-__device__ __forceinline__ void stage_bwd_b(const BwdArgs &p, float *L, int img, int band, const float *dY, bool dy_global, const float (&vf)[CS_NS][8]) {
+__device__ __forceinline__ void stage_bwd_b(const BwdArgs &p, float *L, int img, int band, const float *dY, bool dy_global, const float (&vf)[CS_NS][4]) {
     if constexpr (S >= 0) {
         const BwdStage &g = p.st[S];
         constexpr int H = SH[S].H, W = SH[S].W, C1 = SH[S].C1, C0 = SH[S].C0, K = SH[S].K, KS = SH[S].KS, PD = K / 2;
@@ -1249,62 +1329,77 @@ __device__ __forceinline__ void stage_bwd_b(const BwdArgs &p, float *L, int img,
         float *dOw = L + bdo_off(), *Xw = L + bxw_off(), *dXb = L + bdx_off(S & 1);
         // the conv input's forward values for the dF rows (own conv rows +- P), from the forward's copy; in flight under the run backward
         const int xr_lo = max(ol - PD, 0), xr_hi = min(oh + PD, H), nxw = (xr_hi - xr_lo) * rowX;
-        constexpr int NXQ = ((bmax_o(S) * KS + K - 1) * rowX + CS_THREADS - 1) / CS_THREADS;
+        constexpr int NXQ = ((bmax_o(S) * KS + K - 1) * rowX + CS_BTHREADS - 1) / CS_BTHREADS;
         float vx[NXQ];
         const float *xg = g.save_x + ((long)img * H + xr_lo) * rowX;
 #pragma unroll
-        for (int q = 0; q < NXQ; q++) { const int e = threadIdx.x + q * CS_THREADS; vx[q] = e < nxw ? xg[e] : 0.f; }
-        if (!(LAB_SKIP & 16)) for (int e = threadIdx.x * 4; e < bdo_size() + bxw_size(); e += CS_THREADS * 4) *reinterpret_cast<float4 *>(dOw + e) = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int q = 0; q < NXQ; q++) { const int e = threadIdx.x + q * CS_BTHREADS; vx[q] = e < nxw ? xg[e] : 0.f; }
+        if (!(LAB_SKIP & 16)) for (int e = threadIdx.x * 4; e < bdo_size() + bxw_size(); e += CS_BTHREADS * 4) *reinterpret_cast<float4 *>(dOw + e) = make_float4(0.f, 0.f, 0.f, 0.f);
         lds_barrier();
         CS_STAMP(1 + 8 * S);
-        if (!(LAB_SKIP & 4)) run_bwd<S, true>(g, dY, dy_global, dOw, img, ql, qh, pol, poh);
+        if (!(LAB_SKIP & 4)) run_bwd<S, true, CS_BTHREADS>(g, dY, dy_global, dOw, img, ql, qh, pol, poh);
         CS_STAMP(2 + 8 * S);
         // round 6: the dX-conv filters (requested in the kernel's first instructions) go to LDS HERE, behind the last stage's run backward: the first
-        // consumer is that stage's dX convolution two barriers further on, and placed at the kernel's start the wait for them was a round trip of its own in
+        // consumer is that stage's dX convolution one barrier further on, and placed at the kernel's start the wait for them was a round trip of its own in
         // front of the run backward's loads (cs_lab: "setup" 2.7 k cycles)
-        if constexpr (S == CS_NS - 1) put_filter_b<0>(L, vf);
+        if constexpr (S == CS_NS - 1) put_filter_b<0, CS_BTHREADS>(L, vf);
 #pragma unroll
         for (int q = 0; q < NXQ; q++) {
-            const int e = threadIdx.x + q * CS_THREADS;
+            const int e = threadIdx.x + q * CS_BTHREADS;
             if (e < nxw && !(LAB_SKIP & 8)) { const int y = e / rowX, r = e - y * rowX; Xw[(y + xr_lo - (ol - PD)) * RSX + PD * C1 + r] = vx[q]; }
         }
         lds_barrier();
-        CS_STAMP(3 + 8 * S);
-        if ((p.train & 1) && !(LAB_SKIP & 1)) df_partial<S, bmax_o(S) * KS>(Xw, dOw + (ol - dq0) * RSO, L + bslot_off(), p.part + ((long)img * CS_BSPLIT + band) * part_row() + part_off(S), p.prof, oh - ol);
-        CS_STAMP(4 + 8 * S);
-        if (S == 0 && (p.train & 2)) return;                     // lazy dX of the first layer (see BwdArgs)
-        if constexpr (C1 <= 4 && nF(S) <= 160) { if (!(LAB_SKIP & 2)) dx_valu<S>(dOw + (xl - dq0) * RSO, L + wb_off(S), dXb, xh - xl); }
-        else if (!(LAB_SKIP & 2)) conv_mfma<W, C0, C1, K, JPb(S), NTb(S), NCb(S), conv_mt(bmax_x(S), W), RSOw(S)>(dOw + (xl - dq0) * RSO, L + wb_off(S), nullptr, dXb, xh - xl);
-        CS_STAMP(5 + 8 * S);
+        // ---- the two roles.  Both only READ the windows (the dF role Xw and dOw, the dX role dOw and the filter) and they WRITE disjoint regions - the slots
+        // and the dX buffer - so neither needs anything from the other and ONE barrier behind both orders everything the store phase and the next stage read.
+        // No branch below contains a barrier: a role with nothing to do (no parameter gradients, the first layer's dX left to t4k_conv_stack_dx0, a lab skip)
+        // falls through to the barrier every wave executes.
+        const bool grads = (p.train & 1) && !(LAB_SKIP & 1), lazy0 = S == 0 && (p.train & 2);
+        float *slots = L + bslot_off();
+        if (threadIdx.x < CS_THREADS) {
+            CS_STAMP(3 + 8 * S);
+            if (grads) df_items<S, bmax_o(S) * KS>(Xw, dOw + (ol - dq0) * RSO, slots, p.prof, oh - ol);
+            CS_STAMP(4 + 8 * S);
+        } else {
+            CS_STAMP_X(24 + 2 * S);
+            if (!lazy0 && !(LAB_SKIP & 2)) {
+                if constexpr (C1 <= 4 && nF(S) <= 160) dx_valu<S, CS_THREADS, CS_THREADS, (nF(S) > 64)>(dOw + (xl - dq0) * RSO, L + wb_off(S), dXb, xh - xl);
+                else conv_mfma<W, C0, C1, K, JPb(S), NTb(S), NCb(S), conv_mt(bmax_x(S), W), RSOw(S), CS_WAVES, CS_WAVES, conv_pipe_fits(JPb(S), NTb(S), conv_mt(bmax_x(S), W), CS_WAVES)>(dOw + (xl - dq0) * RSO, L + wb_off(S), nullptr, dXb, xh - xl);
+            }
+            CS_STAMP_X(25 + 2 * S);
+        }
         lds_barrier();
+        CS_STAMP(5 + 8 * S);
+        // ---- one store phase on all 16 waves: the fold of the slots into this workgroup's partial row (every sum in its fixed order), then the dX copy-out
+        if (grads) df_fold<S, CS_BTHREADS>(slots, p.part + ((long)img * CS_BSPLIT + band) * part_row() + part_off(S), p.prof);
         CS_STAMP(6 + 8 * S);
+        if (lazy0) return;                                       // lazy dX of the first layer (see BwdArgs)
         if (!(LAB_SKIP & 32)) {   // dX, own input rows: the conv input tensor (`in = dx`) and its scratch copy
             const int n = (ih - il) * rowX;
             const float *src = dXb + (il - xl) * rowX;
             float *x = g.X + ((long)img * H + il) * rowX, *x2 = g.DXS ? g.DXS + ((long)img * H + il) * rowX : nullptr;
             if ((rowX & 3) == 0) {
-                for (int e = threadIdx.x * 4; e < n; e += CS_THREADS * 4) {
+                for (int e = threadIdx.x * 4; e < n; e += CS_BTHREADS * 4) {
                     const float4 v = *reinterpret_cast<const float4 *>(src + e);
                     *reinterpret_cast<float4 *>(x + e) = v; if (x2) *reinterpret_cast<float4 *>(x2 + e) = v;
                 }
-            } else for (int e = threadIdx.x; e < n; e += CS_THREADS) { const float v = src[e]; x[e] = v; if (x2) x2[e] = v; }
+            } else for (int e = threadIdx.x; e < n; e += CS_BTHREADS) { const float v = src[e]; x[e] = v; if (x2) x2[e] = v; }
         }
         CS_STAMP(7 + 8 * S);
         stage_bwd_b<S - 1>(p, L, img, band, dXb, false, vf);
     }
 }
 
-extern "C" __global__ void __launch_bounds__(CS_THREADS) cs_bwd_b(const BwdArgs p) {
+extern "C" __global__ void __launch_bounds__(CS_BTHREADS) cs_bwd_b(const BwdArgs p) {
     extern __shared__ __attribute__((aligned(16))) float L[];
     const int img = blockIdx.x, band = blockIdx.y;
     CS_STAMP(0);
-    float vf[CS_NS][8];
-    load_filter_b<0>(p, vf);
-    for (int e = threadIdx.x * 4; e < bdo_off(); e += CS_THREADS * 4) *reinterpret_cast<float4 *>(L + e) = make_float4(0.f, 0.f, 0.f, 0.f);
+    float vf[CS_NS][4];
+    load_filter_b<0, CS_BTHREADS>(p, vf);
+    for (int e = threadIdx.x * 4; e < bdo_off(); e += CS_BTHREADS * 4) *reinterpret_cast<float4 *>(L + e) = make_float4(0.f, 0.f, 0.f, 0.f);
     stage_bwd_b<CS_NS - 1>(p, L, img, band, p.DY, true, vf);     // (the zeroed filter region is fenced by the stage's first barrier; the filters follow its run backward)
     if (p.f0_save && img == 0 && band == 0) {                    // the filter the skipped dX of stage 0 belongs to (the optimizer changes F before anyone asks)
 #pragma unroll
-        for (int q = 0; q < (nF(0) + CS_THREADS - 1) / CS_THREADS; q++) { const int e = threadIdx.x + q * CS_THREADS; if (e < nF(0)) p.f0_save[e] = vf[0][q]; }
+        for (int q = 0; q < (nF(0) + CS_BTHREADS - 1) / CS_BTHREADS; q++) { const int e = threadIdx.x + q * CS_BTHREADS; if (e < nF(0)) p.f0_save[e] = vf[0][q]; }
     }
 }
 #endif // CS_ONLY_FWD

@@ -59,6 +59,20 @@ int main(int argc, char **argv) {
             for (int b = 0; b < N * 4; b++) if (h[b * 32 + k] && h[b * 32]) { const double d = (double)(h[b * 32 + k] - h[b * 32]); sum += d; cnt++; if (d > mx) mx = d; }
             if (cnt) printf("  %2d: avg %8.0f  max %8.0f  (%d workgroups)\n", k, sum / cnt, mx, cnt);
         }
+        // banded backward: the two wave roles of every stage (stamps 3 / 4 + 8 S: dF role, thread 0; 24 / 25 + 2 S: dX role, first lane of wave 8;
+        // 5 + 8 S: thread 0 past the barrier the roles share) - how long each role ran and how long it then stood at the barrier
+        for (int S = 2; bwd && S >= 0; S--) {
+            double df = 0, dx = 0, wf = 0, wx = 0, skew = 0; int cnt = 0;
+            for (int b = 0; b < N * 4; b++) {
+                const unsigned long long *s = &h[(size_t)b * 32];
+                if (!s[3 + 8 * S] || !s[4 + 8 * S] || !s[5 + 8 * S] || !s[24 + 2 * S] || !s[25 + 2 * S]) continue;
+                df += (double)(s[4 + 8 * S] - s[3 + 8 * S]); dx += (double)(s[25 + 2 * S] - s[24 + 2 * S]);
+                wf += (double)(s[5 + 8 * S] - s[4 + 8 * S]); wx += (double)(long long)(s[5 + 8 * S] - s[25 + 2 * S]);
+                skew += (double)(long long)(s[24 + 2 * S] - s[3 + 8 * S]); cnt++;
+            }
+            if (cnt) printf("  stage %d roles: dF %6.0f cycles then %6.0f at the barrier | dX %6.0f cycles then %6.0f at the barrier | dX began %+.0f after dF  (%d workgroups)\n",
+                            S, df / cnt, wf / cnt, dx / cnt, wx / cnt, skew / cnt, cnt);
+        }
     }
     return 0;
 }
