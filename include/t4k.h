@@ -88,6 +88,13 @@ int t4k_sync(t4k_stream_t s);
  * loop with it and prints the MEASURED launches per step (the reference issues one launch + cudaDeviceSynchronize per layer,
  * src/nn/forward.cu:82-113, backprop.cu:111-140; memcpy / memset / collective commands are not kernels and are not counted). */
 unsigned long long t4k_launch_count(void);
+/* The rung of the GEMM dispatch ladder (csrc/gemm.hip gemm_launch) the last product of this process took, as a static string: test hook - the
+ * GEMM sweep asserts it for every shape of its table.  "l32/w8/rst", "pair", "nn_plain", "plain_any", "plain_ragk", "plain128", "plain128/ragk",
+ * "plain128/bk32", "plain256", "glds8<128>", "glds8<64,ragk>", "mfma<128,128,32,vec,full>", "mfma<64,64,64,vec,skew>", "mfma<64,64,32>", "k0"
+ * (K = 0: O = beta O), "none" (M or N = 0); "xN" behind it for N split-K slabs and "+fold" when the fold launch followed them.  Valid until the
+ * next call of this function.  Plain, unsynchronised stores by the launch wrappers of gemm.hip: read it on the thread that issued the product, right
+ * behind the call - a product issued from a second host thread, or a later entry that reaches the same wrappers, overwrites it. */
+const char *t4k_gemm_last_plan(void);
 
 /* Library streams own a private workspace, so independent work (e.g. dW beside dX) may be forked
  * onto them and still be captured into one graph through event edges. */

@@ -518,6 +518,7 @@ void launch_plain_(const PlainP &q, int tmq, int tnq, unsigned gx, hipStream_t s
 }
 void launch_nn_plain(const GemmP &p, dim3 grid, hipStream_t s) {
     PlainP q{ p.A, p.B, p.O, p.M, p.N, p.K, 1.0f, 0.0f, nullptr, nullptr, nullptr };
+    st().gemm_plan = "nn_plain";
     launch_plain_<true, false, false>(q, p.M / 64, p.N / 64, grid.x, s);
 }
 // any layout, alpha / beta / bias: interior tiles, K % 128 == 0, unsplit - or, pair = true, K % 256 == 0 and two workgroups per tile (the caller checks)
@@ -525,6 +526,7 @@ void launch_plain_any(const GemmP &p, dim3 grid, int tA, int tB, hipStream_t s, 
     PlainP q{ p.A, p.B, p.O, p.M, p.N, p.K, p.alpha, p.beta, p.bias, p.sync, p.part };
     q.swap = (gemm_lab().tt_swap && tA && tB) ? 1 : 0;
     const int tmq = p.M / 64, tnq = p.N / 64;
+    st().gemm_plan = ragk ? "plain_ragk" : pair ? "pair" : "plain_any";
     with_layout(tA, tB, [&](auto akc, auto bkc, auto epi) {
         if (ragk)      launch_plain_<akc(), bkc(), epi(), false, true>(q, tmq, tnq, grid.x, s);
         else if (pair) launch_plain_<akc(), bkc(), epi(), true>(q, tmq, tnq, grid.x, s);
@@ -864,6 +866,7 @@ void launch_plain128(const GemmP &p, int tA, int tB, hipStream_t s) {
         auto fill_of = [](long tiles_, long cu_) { return (double)tiles_ / (double)(((tiles_ + cu_ - 1) / cu_) * cu_); };
         if (p256 && p.M % 256 == 0 && p.N % 256 == 0 && p.K % 32 == 0 && p.K >= 64 && (p256 >= 2 || (t256 >= cu && fill_of(t256, cu) * 1.04 > fill_of(t128, cu))) &&
             (long)p.M * p.K < (1L << 30) && (long)p.N * p.K < (1L << 30)) {
+            st().gemm_plan = "plain256";
             with_layout(tA, tB, [&](auto akc, auto bkc, auto e) { launch_plain256_<akc(), bkc(), e()>(q, s); }, epi);
             return;
         }
@@ -873,6 +876,7 @@ void launch_plain128(const GemmP &p, int tA, int tB, hipStream_t s) {
     const int bk32 = gemm_lab().plain128_bk32;
     const long tiles = (long)(p.M / 128) * (p.N / 128);
     const bool two = bk32 && p.K % 32 == 0 && (bk32 >= 2 || tiles >= 2L * st().cu_count);
+    st().gemm_plan = two ? "plain128/bk32" : ragk ? "plain128/ragk" : "plain128";
     with_layout(tA, tB, [&](auto akc, auto bkc, auto e) {
         if (two)       launch_plain128_<akc(), bkc(), e(), false, 32>(q, s);
         else if (ragk) launch_plain128_<akc(), bkc(), e(), true>(q, s);
@@ -884,6 +888,7 @@ void launch_plain128(const GemmP &p, int tA, int tB, hipStream_t s) {
 template <int BK, bool RAGK = false>
 void launch_glds8(const GemmP &p, dim3 grid, int tA, int tB, hipStream_t s) {
     constexpr size_t lds_bytes = (size_t)((BK >= 128) ? 2 : 3) * 128 * BK * sizeof(float);
+    st().gemm_plan = BK >= 128 ? (RAGK ? "glds8<128,ragk>" : "glds8<128>") : (RAGK ? "glds8<64,ragk>" : "glds8<64>");
     with_layout(tA, tB, [&](auto akc, auto bkc) { launch_lds<k_gemm_glds8<BK, akc(), bkc(), false, RAGK>>(grid, dim3(512), lds_bytes, s, p); });
 }
 
@@ -942,6 +947,8 @@ __global__ void __launch_bounds__(BLK) k_gemm_f64(const float *__restrict__ A, c
 
 template <int BM, int BN, int BK, bool VEC, bool SKEW, bool FULL>
 void launch_variant(const GemmP &p, dim3 grid, int tA, int tB, hipStream_t s) {
+    st().gemm_plan = BM == 128 ? (FULL ? "mfma<128,128,32,vec,full>" : VEC ? "mfma<128,128,32,vec,skew>" : "mfma<128,128,32>")
+                   : BK == 32  ? "mfma<64,64,32>" : (FULL ? "mfma<64,64,64,vec,full>" : "mfma<64,64,64,vec,skew>");
     with_layout(tA, tB, [&](auto akc, auto bkc) {
         launch_lds<k_gemm_mfma<BM, BN, BK, akc(), bkc(), VEC, SKEW, FULL>>(grid, dim3(256), (size_t)2 * (BM + BN) * BK * sizeof(float), s, p);
     });
@@ -1007,13 +1014,24 @@ int gemm_launch(const float *A, const float *B, float *O, const float *bias, flo
     if (epi_done) *epi_done = false;
     if (defer) defer->part = nullptr;
     if (!A || !B || !O || M < 0 || N < 0 || K < 0 || C < 1) return fail(T4K_ERR_ARG, "t4k_gemm: bad argument");
-    if (M == 0 || N == 0) return T4K_OK;
+    st().gemm_slabs = 1; st().gemm_fold = false;
+    if (M == 0 || N == 0) { st().gemm_plan = "none"; return T4K_OK; }
     const GemmLab &lab = gemm_lab();
     const int cu = st().cu_count;
     hipStream_t hs = S(s);
     GemmP p;
     p.A = A; p.B = B; p.O = O; p.bias = bias; p.part = ws_for(s);
     p.M = M; p.N = N; p.K = K; p.C = C; p.alpha = alpha; p.beta = beta; p.sync = st().d_sync;
+    if (K == 0) {
+        // an empty product: O = alpha 0 + beta O (+ bias) on the fold kernel with no slab to add.  The ladder below would reach a K-loop kernel, and the lean
+        // ones (k_gemm_nn_plain, which a large plain product takes at K % 128 == 0) issue their first stage's DMA before they look at the stage count:
+        // 64 rows of an operand that has no byte to read
+        const long e = (long)M * N * C;
+        st().gemm_plan = "k0";
+        T4K_LAUNCH(k_splitk_fold, dim3(grid_for(e)), dim3(BLK), 0, hs, p.part, O, e, 0, alpha, beta, bias, N, ActEpi{0, 0.f, nullptr, nullptr, RngArg{0, 0, nullptr}}, FoldRider{});
+        T4K_LAUNCH_CHECK();
+        return T4K_OK;
+    }
 
     // 16-byte loads need: C == 1, aligned bases, contiguous extents divisible by 4
     const int a_contig = tA ? M : K, b_contig = tB ? K : N;
@@ -1056,6 +1074,7 @@ int gemm_launch(const float *A, const float *B, float *O, const float *bias, flo
             // waves per workgroup (= k-groups) and whether a wave walks more than two blocks (RST: blocks 2, 3 wait in registers)
             const bool w8 = nblk > 16 || (nblk >= 6 && t32 * ns <= (long)cu);
             const bool rst = nblk > (w8 ? 16 : 8);
+            st().gemm_plan = w8 ? (rst ? "l32/w8/rst" : "l32/w8") : (rst ? "l32/w4/rst" : "l32/w4"); st().gemm_slabs = ns;
             with_layout(tA, tB, [&](auto a, auto b, auto w, auto rs) { launch_l32<a(), b(), w() ? 8 : 4, rs()>(p, r.ep, r.fr, dim3(gx, (unsigned)ns), hs); }, w8, rst);
             T4K_LAUNCH_CHECK();
             return T4K_OK;
@@ -1084,6 +1103,7 @@ int gemm_launch(const float *A, const float *B, float *O, const float *bias, flo
         }
     }
     p.kchunk = kchunk; p.nsplit = nsplit;
+    st().gemm_slabs = nsplit;
     const bool whole_k = kchunk % 64 == 0 && K % kchunk == 0;   // every K slice is whole 64-deep stages
 
     dim3 grid((unsigned)tiles, (unsigned)nsplit, (unsigned)C);
@@ -1148,6 +1168,7 @@ int gemm_launch(const float *A, const float *B, float *O, const float *bias, flo
         defer->part = p.part; defer->nsplit = nsplit; defer->mn = mn;
     } else if (nsplit > 1) {
         const Riders r = make_riders(hs, mn, epi, epi_done, rider, 4, 1024);
+        st().gemm_fold = true;
         T4K_LAUNCH(k_splitk_fold, dim3(grid_for(mn) + r.fr.cp_blocks), dim3(BLK), 0, hs, p.part, O, mn, nsplit, alpha, beta, bias, N, r.ep, r.fr);
     }
     T4K_LAUNCH_CHECK();

@@ -108,6 +108,14 @@ int t4k_gates_enabled(void) { return st().gates_off ? 0 : 1; }
 const char *t4k_last_error(void)  { return st().err; }
 unsigned long long t4k_launch_count(void) { return st().launches; }
 const char *t4k_backend_name(void) { return "hip-gfx950"; }
+const char *t4k_gemm_last_plan(void) {
+    static char text[96];
+    const State &g = st();
+    int n = snprintf(text, sizeof(text), "%s", g.gemm_plan);
+    if (g.gemm_slabs > 1 && n < (int)sizeof(text)) n += snprintf(text + n, sizeof(text) - n, "x%d", g.gemm_slabs);
+    if (g.gemm_fold && n < (int)sizeof(text)) snprintf(text + n, sizeof(text) - n, "+fold");
+    return text;
+}
 
 int t4k_device_info(int *cu_count, int *clock_khz, size_t *hbm_bytes) {
     T4K_REQUIRE_INIT();

@@ -44,6 +44,9 @@ struct State {
     int         cu_count = 256;
     unsigned    slot_epoch[16] = {};  // per stream lane: launch count of the kernels that tag the arrival slots (next_slot_epoch)
     unsigned long long launches = 0;  // kernels launched by the library since t4k_init (t4k_launch_count)
+    const char *gemm_plan = "";       // the rung the last gemm_launch took (t4k_gemm_last_plan): set by the launch_* wrappers of gemm.hip, a literal each
+    int         gemm_slabs = 1;       // ... its split-K slabs and whether a fold launch followed them
+    bool        gemm_fold = false;
     bool        gates_off = false;    // no kernel that makes workgroups wait for each other is chosen any more (t4k_gates_enable(0), or set by spin_check() after a timed-out wait)
     int         pending = 0;          // work a launch left for the NEXT entry point: bit 0 = a conv stack's dF | dB partial fold.  Set, flushed and consumed under pending_mu():
                                       // whichever thread reaches an entry point first flushes (a gradient read from a second thread must see the folded dF | dB);

@@ -11,6 +11,7 @@ Orientation (Model::_flinear / _blinear): Y[N, E0] = X[N, E1] W[E0, E1]^T + B; d
 import numpy as np
 
 import f64_witness as wt
+import gemm_cases
 
 CU = 256                                    # the MI355X
 LS_MAX_FLOATS = 12288                       # linear_small.hip: 48 KiB of dynamic LDS
@@ -47,44 +48,14 @@ def gemm_plan(M, N, K, tA, tB, cu=CU, defer=False, cs_rows=0, plain=False):
     """(label, launches, riders ride, column sums ride, slabs deferred) of gemm_launch on 16-byte aligned operands, C = 1.
     cs_rows > 0: a ColSum request over that many rows; plain: no epilogue, rider or column sum requested (the two-workgroup lean kernel asks
     for that); defer: the caller folds split slabs itself (t4k_mlp_head_fwd)"""
-    big = cdiv(M, 128) * cdiv(N, 128) >= cu * 3 // 4
-    bm = 128 if big else 64
-    tiles = cdiv(M, bm) * cdiv(N, bm)
-    vec = (M if tA else K) % 4 == 0 and (K if tB else N) % 4 == 0
-    akc, bkc = not tA, bool(tB)
-    al = (not akc or K % 4 == 0) and (not bkc or K % 4 == 0)
-    dma_ok = (K % 4 == 0 if akc else M % 4 == 0) and (K % 4 == 0 if bkc else N % 4 == 0)
-    ns, kc = 1, cdiv(K, 8) * 8
-    if defer and K >= 256:
-        want = min(cdiv(cu, t32(M, N)), K // 128, 16)
-        if want > 1:
-            kc = cdiv(cdiv(K, want), 8) * 8; ns = cdiv(K, kc)
-        if ns * M * N * 4 > WS_BYTES // 2:
-            ns, kc = 1, cdiv(K, 8) * 8
-    cs_ok = 0 < cs_rows <= 4096
-    if not big and tiles * 2 <= cu and K >= 1 and kc <= S32_MAXK and al and dma_ok:
-        return ("sliver" if ns == 1 else "sliver_deferred"), 1, ns == 1, cs_ok and ns == 1, ns > 1
-    interior = M % 64 == 0 and N % 64 == 0
-    if plain and not defer and not big and vec and interior and K % 256 == 0 and K >= 512 and tiles * 2 <= cu < tiles * 3 and tiles * 4096 * 4 <= WS_BYTES // 2:
+    r = gemm_cases.ladder(M, N, K, tA, tB, 1, cu, defer=defer, cs_rows=cs_rows, riders=not plain, bias=True)
+    if r["base"].startswith("l32"):
+        return ("sliver" if r["nsplit"] == 1 else "sliver_deferred"), 1, r["riders_ride"], r["cs_ride"], r["deferred"]
+    if r["base"] == "pair":
         return "pair", 1, False, False, False
-    nsplit, kchunk = 1, max(cdiv(K, KG) * KG, KG)
-    if not big and tiles * 2 <= cu and K >= 4 * KG:
-        want = min(cdiv(cu, tiles), K // KG, 64)
-        if want > 1:
-            kchunk = cdiv(cdiv(K, want), KG) * KG; nsplit = cdiv(K, kchunk)
-            if nsplit * M * N * 4 > WS_BYTES // 2:
-                nsplit, kchunk = 1, cdiv(K, KG) * KG
-    whole_k = kchunk % 64 == 0 and K % kchunk == 0
-    full64 = not big and vec and interior and whole_k
-    ragged8 = not big and vec and nsplit == 1 and not interior and whole_k and M >= 4 and N >= 4
-    ragk = not big and vec and not whole_k and nsplit == 1 and M >= 4 and N >= 4 and K >= 8
-    generic = big or not vec or not (full64 or ragged8 or ragk)
-    cs = cs_ok and generic and nsplit == 1
-    if nsplit > 1:
-        if defer:
-            return "splitk_deferred", 1, False, False, True
-        return "splitk", 2, True, False, False            # the fold launch carries every rider
-    return "unsplit", 1, False, cs, False
+    if r["nsplit"] > 1:
+        return ("splitk_deferred" if r["deferred"] else "splitk"), r["launches"], r["riders_ride"], False, r["deferred"]   # the fold launch carries every rider
+    return "unsplit", 1, False, r["cs_ride"], False
 
 
 def colsum_add_launches(rows):

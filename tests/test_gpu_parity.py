@@ -1303,7 +1303,9 @@ def test_gemm_large_plain_products_exact_on_integer_operands(t4k, dev, M, N, K):
                                          (1024, 1024, 784, 0, 0), (1024, 1024, 784, 0, 1), (1024, 1024, 784, 1, 0), (1024, 1024, 784, 1, 1),
                                          (1024, 1024, 132, 0, 1), (1024, 1024, 100, 0, 0), (1024, 1088, 50, 1, 0), (1024, 1024, 1021, 1, 0),
                                          (1000, 1028, 1004, 0, 1), (1028, 1000, 252, 1, 1), (1024, 1024, 8, 0, 1), (1024, 1024, 12, 0, 0),
-                                         # 65..128 tiles, K in 256s: two workgroups per tile, combined in the epilogue (k_gemm_nn_plain<.., PAIR>)
+                                         # 86..128 interior tiles, K in 256s from 1024: two workgroups per tile, combined in the epilogue (k_gemm_nn_plain<.., PAIR>) - the
+                                         # two K = 1024 shapes; K = 512 and 768 are <= 832 and stay on the sliver kernel (l32/w4/rst, l32/w8/rst): the rung in front
+                                         # takes them.  tests/test_gpu_gemm_sweep.py asserts the rung of its own pair rows (576 x 640 x 1024, 1024 x 512 x 1024, 640 x 576 x 1280)
                                          (512, 1024, 1024, 0, 0), (512, 1024, 1024, 0, 1), (1024, 512, 512, 1, 0), (576, 832, 768, 1, 1),
                                          # interior tiles, every layout, on the lean kernel (one tile per CU and several)
                                          (1024, 1024, 1024, 0, 1), (1024, 1024, 512, 1, 0), (1024, 1024, 256, 1, 1), (1088, 1024, 384, 0, 1),
@@ -1337,7 +1339,9 @@ def test_gemm_ragged_edges_and_slivers_exact_on_integer_operands(t4k, dev, M, N,
                                          # ... two workgroups per CU on 32-deep stages (k_gemm_plain128<.., 32>, grids of >= 512 tiles; the two shapes above with 544 / 576 tiles take it too):
                                          # every layout, K in whole 32s that are not whole 64s (unragged for this form), a deep K
                                          (2048, 4096, 288, 0, 0), (4096, 2048, 480, 1, 1), (4096, 2048, 512, 0, 1), (2048, 4096, 1056, 1, 0),
-                                         # ... 256 x 256 tiles on 16 waves (k_gemm_plain256: one such tile or more per CU), every layout, a second column of tiles past 4096
+                                         # ... grids of 256 x 256 tiles and more with K < 256: launch_plain128 (the only way to k_gemm_plain256) sits behind K >= 256, so these take
+                                         # plain_ragk (K = 160, 224), mfma<128,128,32,vec,skew> (K = 96) and mfma<128,128,32,vec,full> (K = 64; ragged 64-tile grid 4352 = 34 x 128);
+                                         # k_gemm_plain256 itself: the plain256 rows of tests/test_gpu_gemm_sweep.py (4096 x 4096 x 256 .. 320, every layout)
                                          (4096, 4096, 160, 0, 0), (4096, 4096, 96, 1, 1), (4096, 4352, 224, 0, 1), (4352, 4096, 64, 1, 0)])
 def test_gemm_large_transposed_products_exact_on_integer_operands(t4k, dev, M, N, K, tA, tB):
     """Large products with transposed operands and alpha / beta (the linear layers of an MLP) on the 8-wave LDS-DMA kernel, several 64x64
