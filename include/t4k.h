@@ -244,6 +244,25 @@ int t4k_tt_op_bcast(int op, const float *A, const float *B, float *O,
  *   dst[b] = transpose(src[b]) for b in [0, batch): each entry [H,W,C] -> [W,H,C] exactly as t4k_transpose, entries H*W*C apart.
  * Bit-exact, one launch per call; batch == 0 is T4K_OK without a launch; H, W, C <= 0, batch < 0 or NULL: T4K_ERR_ARG. */
 int t4k_transpose_batched(const float *src, float *dst, int H, int W, int C, int batch, t4k_stream_t s);
+/* Any order of the four axes; no reference definition: the nearest thing is k_transpose :150, which swaps H and W of one sample.
+ *   src is dense NHWC of extents dim = {N,H,W,C}; perm[i] is the source axis (0 = N ... 3 = C) that output axis i takes - NumPy's
+ *   transpose(perm); dst is dense with extents dim[perm[i]].  Bit-exact: an element is loaded and stored and nothing else (NaN payloads
+ *   and denormals survive).
+ * Exactly one launch per call, whatever the order and the shape; no allocation, no synchronisation, no workspace (legal under capture).
+ * NULL src / dst / dim / perm, an extent < 1, more than 2^40 elements, a perm that is not a permutation of 0..3, dst overlapping src
+ * (dst == src included), or an extent above 2^32 left by the merge of neighbouring axes other than the contiguous run itself:
+ * T4K_ERR_ARG. */
+int t4k_permute(const float *src, float *dst, const int dim[4], const int perm[4], t4k_stream_t s);
+/* The plan t4k_permute takes for (dim, perm) when both pointers are (aligned != 0) or are not 16-byte aligned; launches nothing and
+ * needs no device.
+ * out = { family (0 copy: nothing moves after the merge, 1 runs: the innermost group stays innermost, 2 tiles: a transpose through LDS),
+ *         float4 path (0 / 1; always 0 for tiles),
+ *         tiles: tile extent along the source's innermost group; copy / runs: lanes that share a run (256 = a chunk of a long run),
+ *         tiles: tile extent along the output's innermost group; copy / runs: runs per 256-lane pass,
+ *         work items (workgroup iterations; the grid is their count capped at 2048, the kernel strides over the rest),
+ *         groups left after dropping extents of 1 and merging,
+ *         tiles: entries of the inner batch group a tile takes (1 unless both tile sides are narrow); copy / runs: 1 }. */
+int t4k_permute_plan(const int dim[4], const int perm[4], int aligned, int out[7]);
 
 /* ------------------------------------------------ linear algebra (t4math.cu) */
 /* Tensor::inverse tensor.cu:344-369 (k_find_pivot/k_swap_rows/k_diag/k_elim :742-836):

@@ -152,6 +152,7 @@ struct Tensor : Obj {
     static Tensor &bmm(Tensor &A, Tensor &B, Tensor &O, uint32_t M, uint32_t K, uint32_t P);   // NumPy @ over N and C (beyond _tdot)
     static Tensor &gemm(int variant, Tensor &A, Tensor &B, Tensor &O, DU alpha, DU beta);
     static Tensor &transpose(Tensor &A, Tensor &T);
+    static Tensor &permute(Tensor &A, Tensor &T, const int perm[4]);    // T = numpy.transpose(A as (N,H,W,C), perm); T already has the permuted shape
     static Tensor &inverse(Tensor &A, Tensor &I);
     static Tensor &lu_inverse(Tensor &A, Tensor &I);
     static Tensor &plu(Tensor &A, Tensor &I, int *piv_dev);

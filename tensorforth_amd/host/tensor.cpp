@@ -456,6 +456,40 @@ Tensor &Tensor::transpose(Tensor &A, Tensor &T) {
     for (uint32_t n = 0; n < A.N(); n++) chk(t4k_transpose(A.slice(n), T.slice(n), A.H(), A.W(), A.C(), stream()), "transpose");
     return T;
 }
+// Axis permutation (beyond the reference, whose `transpose` swaps H and W of one matrix: k_transpose t4math.cu:150): T = A with output
+// axis i taking A's axis perm[i] (0 = N ... 3 = C), NumPy's transpose(perm).  One t4k_permute call.  The symbol is referenced weakly: over a
+// C-ABI without it (the CPU oracle) the order is reached by at most six swaps of neighbouring axes (a bubble sort of the axes by their
+// place in the output), each swap one t4k_transpose(H = the outer axis, W = the inner one, C = everything inside them) per index of the
+// axes outside them, ping-ponging between two temporaries and landing in T: pure copies, so the same bits.
+#pragma weak t4k_permute
+Tensor &Tensor::permute(Tensor &A, Tensor &T, const int perm[4]) {
+    long e[4]; nhwc_of(A, e);
+    if (t4k_permute) {
+        const int dim[4] = { (int)e[0], (int)e[1], (int)e[2], (int)e[3] };
+        chk(t4k_permute(A.data, T.data, dim, perm, stream()), "permute");
+        return T;
+    }
+    int place[4], swaps[6], ns = 0;                      // place[k]: where the axis now at position k goes
+    for (int i = 0; i < 4; i++) place[perm[i]] = i;
+    for (int pass = 0; pass < 3; pass++) for (int k = 0; k < 3 - pass; k++)
+        if (place[k] > place[k + 1]) { std::swap(place[k], place[k + 1]); swaps[ns++] = k; }
+    if (!ns) { chk(t4k_copy(A.data, T.data, (long)A.numel, stream()), "copy"); return T; }
+    Tensor *tmp[2] = { ns > 1 ? &Store::get().tensor(A.numel) : nullptr, ns > 2 ? &Store::get().tensor(A.numel) : nullptr };
+    const float *src = A.data;
+    for (int i = 0; i < ns; i++) {
+        const int k = swaps[i];
+        float *dst = i == ns - 1 ? T.data : tmp[i & 1]->data;
+        long outer = 1, inner = 1;
+        for (int j = 0; j < k; j++) outer *= e[j];
+        for (int j = k + 2; j < 4; j++) inner *= e[j];
+        const long blk = e[k] * e[k + 1] * inner;
+        for (long o = 0; o < outer; o++) chk(t4k_transpose(src + o * blk, dst + o * blk, (int)e[k], (int)e[k + 1], (int)inner, stream()), "transpose");
+        std::swap(e[k], e[k + 1]);
+        src = dst;
+    }
+    for (Tensor *t : tmp) if (t) Store::get().free(*t);
+    return T;
+}
 static int read_status() { int s = 0; t4k_memcpy_d2h(&s, g_iscalar, sizeof(int), stream()); t4k_sync(stream()); return s; }
 Tensor &Tensor::inverse(Tensor &A, Tensor &I) {          // tensor.cu:344-369
     if (A.H() != A.W() || I.H() != I.W()) { hprintf(" A: square matrix required (%d x %d)\n", A.H(), A.W()); return A; }

@@ -66,6 +66,26 @@ static Tensor &tinv(Tensor &A, bool use_lu) {
     return I;
 }
 void VM::blas1(int op) {
+    // beyond the reference ( T p -- T T' ): a scalar on top of a rank-4 tensor makes `transpose` an axis permutation.  p is a
+    // four-digit number holding each axis weight N = 8, H = 4, W = 2, C = 1 once: read left to right, the source axis each of the output's
+    // N, H, W, C takes (8421 = a copy, 8241 = what `T transpose` gives).  The reference prints its "tensor2?" for this operand set
+    if (op == B_XPOS && !IS_OBJ(tos_) && SP() >= 1 && is_t(SS(-1)) && TNOS().rank == 4) {
+        const DU p = POP();
+        int perm[4], seen = 0, v = (p >= 1000.0f && p <= 9999.0f && (DU)(int)p == p) ? (int)p : 0;
+        for (int i = 3; i >= 0; i--, v /= 10) {
+            const int dgt = v % 10;
+            perm[i] = dgt == 8 ? 0 : dgt == 4 ? 1 : dgt == 2 ? 2 : dgt == 1 ? 3 : 4;
+            seen |= 1 << perm[i];
+        }
+        if (seen != 15) { pstr("transpose: axes 8421?\n"); return; }
+        Tensor &A = TTOS();
+        const uint32_t e[4] = { A.N(), A.H(), A.W(), A.C() };
+        Tensor &T = st().tensor(e[perm[0]], e[perm[1]], e[perm[2]], e[perm[3]]);
+        Tensor::permute(A, T, perm);
+        PUSH(T);
+        return;
+    }
+    if (!TOS1T()) { pstr("tensor2?"); return; }           // before the cell is looked up as an object: a scalar is no handle
     Tensor &A = TTOS();
     const bool batch = TOS1T() && A.is_batch() && op != B_XPOS;   // beyond the reference: T4[N,K,K,1] = N matrices, each treated as the rank-2 word treats its one
     if (TOS1T() && A.rank == 4 && op == B_XPOS) {        // beyond the reference: T4[N,H,W,C] -> T4[N,W,H,C], every entry and channel in one launch
