@@ -263,6 +263,29 @@ int t4k_permute(const float *src, float *dst, const int dim[4], const int perm[4
  *         groups left after dropping extents of 1 and merging,
  *         tiles: entries of the inner batch group a tile takes (1 unless both tile sides are narrow); copy / runs: 1 }. */
 int t4k_permute_plan(const int dim[4], const int perm[4], int aligned, int out[7]);
+/* A box of one tensor onto a box of another; no reference definition: the nearest thing is MMU::slice mmu.cu:307-330, one memcpy per
+ * (sample, row) of an H / W window.
+ *   src is dense NHWC of extents sdim, dst dense NHWC of extents ddim; dst[doff + i] = src[soff + i] for every i with 0 <= i < ext on
+ *   each axis, and no other element of dst is written.  A slice is doff = 0, ddim = ext; a store is soff = 0, sdim = ext; box to box
+ *   is allowed.  Bit-exact: an element is loaded and stored and nothing else (NaN payloads and denormals survive).
+ * Exactly one launch per call, whatever the box and the shapes; no allocation, no synchronisation, no workspace (legal under capture).
+ * NULL src / dst / sdim / soff / ddim / doff / ext, an extent < 1, a negative offset, off + ext > dim on either side, more than 2^40
+ * elements in either tensor, any overlap of the two tensors' whole byte ranges (dst == src included), or a digit of the run index
+ * other than the outermost that the merge of neighbouring axes leaves at 2^32 or above: T4K_ERR_ARG. */
+int t4k_window(const float *src, const int sdim[4], const int soff[4],
+               float *dst, const int ddim[4], const int doff[4], const int ext[4], t4k_stream_t s);
+/* The plan t4k_window takes for the two boxes when both base pointers are (aligned != 0) or are not 16-byte aligned; launches nothing and
+ * needs no device (t4k_window itself looks at the two box starts, so base pointers that are off 16 bytes by what the offsets make up for
+ * still take the float4 path).  Axes of extent 1 fold into the two box starts; an axis merges with its inner neighbour when that one is taken whole
+ * on both sides (ext == sdim == ddim); what is left is R runs of L contiguous floats with at most three digits above them.
+ * out = { family (0 copy: nothing is left above the run, 1 runs),
+ *         float4 path (0 / 1: L % 4 == 0, every stride left a multiple of 4 and both box starts on 16 bytes),
+ *         run length L in floats (saturated at 2^31 - 1),
+ *         runs R (saturated likewise),
+ *         digits of the run index (0..3),
+ *         work items (256-lane passes, saturated likewise; the grid is their count capped at 2048, the kernel strides over the rest) }. */
+int t4k_window_plan(const int sdim[4], const int soff[4], const int ddim[4], const int doff[4],
+                    const int ext[4], int aligned, int out[6]);
 
 /* ------------------------------------------------ linear algebra (t4math.cu) */
 /* Tensor::inverse tensor.cu:344-369 (k_find_pivot/k_swap_rows/k_diag/k_elim :742-836):

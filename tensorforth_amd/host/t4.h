@@ -153,6 +153,7 @@ struct Tensor : Obj {
     static Tensor &gemm(int variant, Tensor &A, Tensor &B, Tensor &O, DU alpha, DU beta);
     static Tensor &transpose(Tensor &A, Tensor &T);
     static Tensor &permute(Tensor &A, Tensor &T, const int perm[4]);    // T = numpy.transpose(A as (N,H,W,C), perm); T already has the permuted shape
+    static void window(Tensor &S, const int soff[4], Tensor &D, const int doff[4], const int ext[4]);   // D[doff + i] = S[soff + i] over the box ext, both as (N,H,W,C)
     static Tensor &inverse(Tensor &A, Tensor &I);
     static Tensor &lu_inverse(Tensor &A, Tensor &I);
     static Tensor &plu(Tensor &A, Tensor &I, int *piv_dev);

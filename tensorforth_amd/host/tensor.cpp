@@ -138,11 +138,17 @@ Tensor &Store::dim(Tensor &t0) {                        // MMU::dim mmu.cu:296-3
     t.from_host(v, 4);
     return t;
 }
+#pragma weak t4k_window
 Tensor &Store::slice(Tensor &t0, uint32_t x0, uint32_t x1, uint32_t y0, uint32_t y1) {   // mmu.cu:307-330
     if (t0.rank < 2) { hprintf("dim?"); return t0; }
     if (x1 == (uint32_t)-1) x1 = t0.W();
     if (y1 == (uint32_t)-1) y1 = t0.H();
     Tensor &t1 = t0.rank == 2 ? tensor(y1 - y0, x1 - x0) : tensor(t0.N(), y1 - y0, x1 - x0, t0.C());
+    if (t4k_window && x0 < x1 && x1 <= t0.W() && y0 < y1 && y1 <= t0.H()) {   // a valid window: one launch in place of a memcpy per (sample, row)
+        const int soff[4] = { 0, (int)y0, (int)x0, 0 }, doff[4] = { 0, 0, 0, 0 }, ext[4] = { (int)t1.N(), (int)t1.H(), (int)t1.W(), (int)t1.C() };
+        Tensor::window(t0, soff, t1, doff, ext);
+        return t1;
+    }
     const uint32_t N = t1.N(), C = t1.C();
     const size_t bsz = sizeof(float) * C * t1.W();
     for (uint32_t n = 0; n < N; n++)
@@ -489,6 +495,30 @@ Tensor &Tensor::permute(Tensor &A, Tensor &T, const int perm[4]) {
     }
     for (Tensor *t : tmp) if (t) Store::get().free(*t);
     return T;
+}
+// Box windows (beyond the reference, whose `slice` cuts H and W with one memcpy per (sample, row): mmu.cu:307-330): the box of
+// extents ext at soff of S lands at doff of D, both viewed as (N,H,W,C); nothing else of D is written.  One t4k_window call.  The
+// symbol is referenced weakly: over a C-ABI without it (the CPU oracle) the box is walked run by run - the trailing axes taken whole on
+// both sides and the innermost cut one are one contiguous t4k_copy - so both VMs give the same bits.  for_each_group is not the walk
+// here: it gathers a group into a temporary row, and a box has two sides and nothing to gather.
+void Tensor::window(Tensor &S, const int soff[4], Tensor &D, const int doff[4], const int ext[4]) {
+    long es[4], ed[4]; nhwc_of(S, es); nhwc_of(D, ed);
+    if (t4k_window) {
+        const int sdim[4] = { (int)es[0], (int)es[1], (int)es[2], (int)es[3] }, ddim[4] = { (int)ed[0], (int)ed[1], (int)ed[2], (int)ed[3] };
+        chk(t4k_window(S.data, sdim, soff, D.data, ddim, doff, ext, stream()), "window");
+        return;
+    }
+    long ss[4], ds[4], a = 1, b = 1, run = ext[3];
+    for (int i = 3; i >= 0; i--) { ss[i] = a; a *= es[i]; ds[i] = b; b *= ed[i]; }
+    int top = 3;                                         // the axes from `top` inwards are one run
+    while (top > 0 && ext[top] == es[top] && ext[top] == ed[top]) { top--; run *= ext[top]; }
+    long k[4] = { 0, 0, 0, 0 };
+    const long K[4] = { top > 0 ? ext[0] : 1, top > 1 ? ext[1] : 1, top > 2 ? ext[2] : 1, 1 };
+    for (k[0] = 0; k[0] < K[0]; k[0]++) for (k[1] = 0; k[1] < K[1]; k[1]++) for (k[2] = 0; k[2] < K[2]; k[2]++) {
+        long so = 0, dn = 0;
+        for (int i = 0; i < 4; i++) { so += (soff[i] + k[i]) * ss[i]; dn += (doff[i] + k[i]) * ds[i]; }
+        chk(t4k_copy(S.data + so, D.data + dn, run, stream()), "copy");
+    }
 }
 static int read_status() { int s = 0; t4k_memcpy_d2h(&s, g_iscalar, sizeof(int), stream()); t4k_sync(stream()); return s; }
 Tensor &Tensor::inverse(Tensor &A, Tensor &I) {          // tensor.cu:344-369

@@ -243,13 +243,57 @@ void VM::init_tensor() {
     CODE("norm", [this, axes] { if (TOS1T()) PUSH(TTOS().norm()); else axes("norm", Tensor::AX_NORM); });
     CODE("{", [this] { if (TOS1T() && ten_lvl_ > 0) ++ten_lvl_; });
     CODE("}", [this, lit_flush] { if (TOS1T() && ten_lvl_ > 0) { if (--ten_lvl_ == 0) lit_flush(); } });
-    CODE("slice", [this] {
+    // beyond the reference: box windows over N, H, W, C.  A cell of either word is a whole number when as_int takes it
+    auto as_int = [](DU v, long &i) { if (!(v >= -1.0f && v <= 2147483520.0f)) return false; i = (long)v; return (DU)i == v; };
+    auto scalars_on_top = [this](int n) { if (IS_OBJ(tos_)) return false; for (int i = 1; i < n; i++) if (IS_OBJ(SS(-i))) return false; return true; };
+    CODE("slice", [this, as_int, scalars_on_top] {
+        // ( T n0 n1 h0 h1 w0 w1 c0 c1 -- T T' ): eight scalars on top of a tensor, half-open ranges on the four axes of T viewed as (N,H,W,C), an
+        // upper bound of -1 the extent; T' has T's rank.  The four-scalar form below is looked for first
+        if (!(SP() >= 4 && is_t(SS(-4))) && SP() >= 8 && is_t(SS(-8)) && scalars_on_top(8)) {
+            DU b[8]; for (int i = 7; i >= 0; i--) b[i] = POP();
+            Tensor &T = TTOS();
+            const uint32_t e[4] = { T.N(), T.H(), T.W(), T.C() };
+            int off[4], ext[4]; bool ok = true;
+            for (int a = 0; a < 4; a++) {
+                long lo = 0, hi = 0;
+                ok = ok && as_int(b[2 * a], lo) && as_int(b[2 * a + 1], hi);
+                if (hi == -1) hi = e[a];
+                ok = ok && 0 <= lo && lo < hi && hi <= (long)e[a];
+                off[a] = (int)lo; ext[a] = (int)(hi - lo);
+            }
+            if (!ok) { pstr("slice: range?\n"); return; }
+            Tensor &R = T.rank == 4 ? st().tensor(ext[0], ext[1], ext[2], ext[3]) : T.rank == 2 ? st().tensor(ext[1], ext[2]) : st().tensor((uint64_t)ext[1]);
+            const int zero[4] = { 0, 0, 0, 0 };
+            Tensor::window(T, off, R, zero, ext);
+            PUSH(R);
+            return;
+        }
         uint32_t y1 = (uint32_t)POPi(), y0 = (uint32_t)POPi(), x1 = (uint32_t)POPi(), x0 = (uint32_t)POPi();
         if (TOS1T()) PUSH(st().slice(TTOS(), x0, x1, y0, y1));
     });
     CODE("dim", [this] { if (TOS1D()) PUSH(st().dim(TTOS())); else pstr("TOS tensor?"); });
     CODE("t@",  [this] { if (!IS_OBJ(tos_) && IS_OBJ(SS(-1))) { int i = POPi(); DU v = TTOS().get(i); PUSH(SCALAR(v)); } });
-    CODE("t!",  [this] { int i = POPi(); DU v = POP(); if (IS_OBJ(tos_)) TTOS().set(i, v); });
+    CODE("t!",  [this, as_int, scalars_on_top] {
+        // ( T S n0 h0 w0 c0 -- T ): four scalars on top of two tensors write S into T with its first element at (n0,h0,w0,c0); S is dropped as
+        // `+=` drops its right operand.  ( T v i -- T ) below has its tensor at SS(-2), where this form has a scalar
+        if (SP() >= 5 && scalars_on_top(4) && is_t(SS(-4)) && is_t(SS(-5))) {
+            DU b[4]; for (int i = 3; i >= 0; i--) b[i] = POP();
+            Tensor &S = TTOS(), &T = TNOS();
+            const uint32_t es[4] = { S.N(), S.H(), S.W(), S.C() }, et[4] = { T.N(), T.H(), T.W(), T.C() };
+            int off[4], ext[4]; bool ok = !(S.data < T.data + T.numel && T.data < S.data + S.numel);   // S shares T's storage (T dup ... t!)
+            for (int a = 0; a < 4; a++) {
+                long o = -1;
+                ok = ok && as_int(b[a], o) && o >= 0 && o + (long)es[a] <= (long)et[a];
+                off[a] = (int)o; ext[a] = (int)es[a];
+            }
+            if (!ok) { pstr("t!: range?\n"); return; }
+            const int zero[4] = { 0, 0, 0, 0 };
+            Tensor::window(S, zero, T, off, ext);
+            DROP(POP());
+            return;
+        }
+        int i = POPi(); DU v = POP(); if (IS_OBJ(tos_)) TTOS().set(i, v);
+    });
     CODE("exp",     [this] { xop1(T4K_EXP); });
     CODE("ln",      [this] { xop1(T4K_LN); });
     CODE("log",     [this] { xop1(T4K_LOG); });
