@@ -95,6 +95,16 @@ unsigned long long t4k_launch_count(void);
  * next call of this function.  Plain, unsynchronised stores by the launch wrappers of gemm.hip: read it on the thread that issued the product, right
  * behind the call - a product issued from a second host thread, or a later entry that reaches the same wrappers, overwrites it. */
 const char *t4k_gemm_last_plan(void);
+/* The engine decisions of the last convolution entry of this process (t4k_conv2d_fwd / _fwd2 / _bn_fwd / _bn_block_fwd / _block_fwd / _bwd / _bwd2,
+ * t4k_dconv2d_fwd / _bwd), in launch order, as one static string of blank-separated tokens: test hook - the conv sweep asserts it for every row
+ * of its table.  Forward: "few<G,CH,VW>", "thin" ("+copy": the layer-0 copy leaves from the same launch, "+stat": the batch-norm sums ride),
+ * "img_block", "gather<raw|staged,ksN>", "gather_pool<raw|staged,ksN>", "big<64|128>", "big8<64|128,bk64|bk32>" ("+bn": the batch-norm rider);
+ * "memcpy": the layer-0 copy was a copy command.  dF | dB: "dfw<ciw,ntw>xN", "df8<tp1|tp2>xN", "dfxN" (N slices; no bias row: dB is "colsum<chunks>",
+ * "+fold" behind it when the chunks are folded by a second launch), "thin_dfxN+b", "df_mfmaxN+b" ("+b": the bias row of the slab is dB); the fold of
+ * the slices: "fold_add" or "df_fold" as launches of their own, or "+fold" behind the dX engine that carries it.  dX: "dx_big8<..>", "dx_big<..>",
+ * "dx_wide<lanes per pixel>", "dx_few", "fewch<G,CH,VW>", "dx_and_fold<raw|staged,ksN>".  The transposed convolution adds "xpose" per filter
+ * transposition and "bias".  Valid until the next call of this function; plain, unsynchronised stores as t4k_gemm_last_plan. */
+const char *t4k_conv_last_plan(void);
 
 /* Library streams own a private workspace, so independent work (e.g. dW beside dX) may be forked
  * onto them and still be captured into one graph through event edges. */

@@ -55,6 +55,7 @@ int colsum_add(const float *X, float *OUT, long rows, int E, hipStream_t hs) {
     const int nchunk = (int)((rows + rpc - 1) / rpc);
     float *part = ws_for(hs) + (8 << 20);            // second 32 MiB half of the workspace
     if ((size_t)nchunk * E * sizeof(float) > st().ws_bytes / 2) return fail(T4K_ERR_NOMEM, "colsum workspace");
+    conv_plan_note("colsum<%d>%s", nchunk, nchunk > 1 ? "+fold" : "");
     if (nchunk == 1) {
         T4K_LAUNCH(k_colsum_part, dim3(1, (E + 63) / 64), dim3(BLK), 0, hs, X, part, rows, E, rpc, OUT);
         return T4K_OK;

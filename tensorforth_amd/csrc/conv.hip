@@ -346,6 +346,8 @@ GatherShape gather_shape(long npix, int Cout, int Cin, int K) {
     const int ksplit = conv_gemm_ksplit(npix, Cout, Cin, K);
     return { ksplit, LDS_FILTER_FLOATS / (K * K * 2 * 32) /* channel pairs per LDS filter slice */, (int)((npix + (128 / ksplit) - 1) / (128 / ksplit)), (Cout + 31) / 32 };
 }
+// what conv_gemm_body decides from the filter's size: copied verbatim into the LDS stage (raw) or staged per chunk of channel pairs
+const char *gather_filter(int C1, int K, int C0) { return C1 * K * K * C0 <= LDS_FILTER_FLOATS ? "raw" : "staged"; }
 // many channels: the LDS-staged GEMM tiling of conv_big.hip (16-byte loads of both operands)
 bool big_path(int Cin, int Cout, const void *a, const void *b) { return conv_lab().big && conv_big_ok(Cin, Cout) && aligned16(a) && aligned16(b); }
 // 3x3 / stride 1 / padding 1 on a shared pixel grid: what the kernels of conv_img.hip serve
@@ -359,6 +361,7 @@ bool fusable(const t4k_poolblock *blk, int H0, int W0, int C1, int C0, int K, in
 }
 // the layer-0 copy of the batch (forward.cu:39) where no kernel writes it from its own launch
 int copy_input(float *ICOPY, const float *I, int N, int H1, int W1, int C1, hipStream_t hs) {
+    conv_plan_note("memcpy");
     T4K_HIP(hipMemcpyAsync(ICOPY, I, sizeof(float) * (size_t)N * H1 * W1 * C1, hipMemcpyDeviceToDevice, hs));
     return T4K_OK;
 }
@@ -367,6 +370,7 @@ template <bool BWD>
 void launch_conv_gemm(int K, int S, int P, hipStream_t hs, const float *X, float *Y, float *Y2, const float *F, const float *B,
                       int N, int Hx, int Wx, int Cin, int Hy, int Wy, int Cout, int C0) {
     const GatherShape gs = gather_shape((long)N * Hy * Wy, Cout, Cin, K);
+    conv_plan_note("gather<%s,ks%d>", gather_filter(BWD ? Cout : Cin, K, C0), gs.ksplit);
     with_geometry(K, S, P, [&](auto geo) {
         using Ge = decltype(geo);
         T4K_LAUNCH((k_conv_gemm<Ge::K, Ge::S, Ge::P, BWD>), dim3(gs.gx, gs.gy), dim3(256), 0, hs, X, Y, Y2, F, B, N, Hx, Wx, Cin, Hy, Wy, Cout, C0, gs.ppc, gs.ksplit);
@@ -421,13 +425,14 @@ int conv_df_stage(const float *I, const float *DO, float *DF, float *DB, int N, 
             const int ntot = ntaps * C0;                     // no bias row in these slabs: dB is a plain column sum of dO
             // few slices x many outputs: one thread per output walks the slices (coalesced); the wave-per-output fold is
             // for the opposite shape (hundreds of slices, few outputs) and would run 8 of 64 lanes here
-            if (nbig <= 32) launch_fold_add(part, DF, ntot, nbig, hs);
-            else            launch_df_fold(part, DF, DB, nbig, ntot, ntot, hs);
+            if (nbig <= 32) { conv_plan_note("fold_add"); launch_fold_add(part, DF, ntot, nbig, hs); }
+            else            { conv_plan_note("df_fold");  launch_df_fold(part, DF, DB, nbig, ntot, ntot, hs); }
             return colsum_add(DO, DB, (long)N * H0 * W0, C0, hs);
         }
     }
     int nthin = 0;                                           // image in, a tile or two of channels out: 32 pixels per wave and trip (conv_img.hip)
     if (same3x3(K, S, P, H1, W1, H0, W0) && conv_thin_df(I, DO, part, st().ws_bytes / 2, N, H0, W0, C1, C0, &nthin, hs)) {
+        conv_plan_note("thin_dfx%d+b", nthin);
         *pending = with_bias_row; pending->nslice = nthin;
         return T4K_OK;
     }
@@ -439,6 +444,7 @@ int conv_df_stage(const float *I, const float *DO, float *DF, float *DB, int N, 
     nslice = (rows + rpw * 4 - 1) / (rpw * 4);
     if ((size_t)nslice * nrow1 * C0 * sizeof(float) > st().ws_bytes / 2) return fail(T4K_ERR_NOMEM, "conv dF workspace");
     const dim3 g(nslice, (nrow1 + 31) / 32, (C0 + 31) / 32);
+    conv_plan_note("df_mfmax%d+b", nslice);
     with_geometry(K, S, P, [&](auto geo) {
         using Ge = decltype(geo);
         T4K_LAUNCH((k_conv_df_mfma<Ge::K, Ge::S, Ge::P>), g, dim3(256), 0, hs, I, DO, part, N, H1, W1, C1, H0, W0, C0, rpw);
@@ -452,9 +458,9 @@ void conv_dx_stage(const float *DO, float *DX, float *DX2, const float *F, int N
                    int K, int S, int P, FoldArgs fa, hipStream_t hs) {
     int fG = 0, fNG = 0;
     const bool dx_big   = DX && big_path(C0, C1, DO, F);
-    const bool dx_few   = DX && !dx_big && conv_dx_few_ok(K, C1, C0);
+    const bool dx_few   = DX && !dx_big && conv_dx_few_ok(K, C1, C0, DO);
     const bool dx_fewch = DX && !dx_big && !dx_few && conv_lab().few && conv_few_ok(K, C0, C1, &fG, &fNG);
-    if (fa.nfold && (!DX || dx_big || dx_fewch)) { launch_df_fold(fa.part, fa.DF, fa.DB, fa.nslice, fa.ndf, fa.ntot, hs); fa.nfold = 0; }
+    if (fa.nfold && (!DX || dx_big || dx_fewch)) { conv_plan_note("df_fold"); launch_df_fold(fa.part, fa.DF, fa.DB, fa.nslice, fa.ndf, fa.ntot, hs); fa.nfold = 0; }
     if (!DX) return;
     if (dx_big)        launch_conv_big<true>(K, S, P, hs, DO, DX, DX2, F, nullptr, N, H0, W0, C0, H1, W1, C1, C0);
     else if (dx_few)   launch_conv_dx_few(K, S, P, hs, DO, DX, DX2, F, N, H0, W0, C0, H1, W1, C1, fa);     // image-input layer: one thread (or C0 / 4 lanes) per input pixel
@@ -462,6 +468,7 @@ void conv_dx_stage(const float *DO, float *DX, float *DX2, const float *F, int N
     else {
         // gather over dO (Hx = H0, Wx = W0, Cin = C0), output the input grid (Hy = H1, Wy = W1, Cout = C1), grid linearised behind the fold's workgroups
         const GatherShape gs = gather_shape((long)N * H1 * W1, C1, C0, K);
+        conv_plan_note("dx_and_fold<%s,ks%d>%s", gather_filter(C1, K, C0), gs.ksplit, fa.nfold ? "+fold" : "");
         with_geometry(K, S, P, [&](auto geo) {
             using Ge = decltype(geo);
             T4K_LAUNCH((k_conv_dx_and_fold<Ge::K, Ge::S, Ge::P>), dim3((unsigned)(fa.nfold + gs.gx * gs.gy)), dim3(256), 0, hs, fa.part, fa.DF, fa.DB, fa.nslice, fa.ndf, fa.ntot, fa.nfold,
@@ -482,6 +489,7 @@ int t4k_conv2d_fwd(const float *I, float *O, const float *F, const float *B,
 int t4k_conv2d_fwd2(const float *I, float *ICOPY, float *O, const float *F, const float *B,
                     int N, int H1, int W1, int C1, int H0, int W0, int C0,
                     int K, int S, int P, t4k_stream_t s) {
+    ConvPlanScope plan;
     return conv2d_fwd_impl(I, ICOPY, O, F, B, N, H1, W1, C1, H0, W0, C0, K, S, P, nullptr, 0, nullptr, s);
 }
 // conv forward + the batch-norm forward behind it: same tensors, same arithmetic per element as t4k_conv2d_fwd2 + t4k_batchnorm_fwd; with the rider
@@ -491,6 +499,7 @@ int t4k_conv2d_bn_fwd(const float *I, float *ICOPY, float *Y, const float *F, co
                       float *O, float *XH, const float *W, const float *B, float *stat_dev, t4k_stream_t s) {
     T4K_REQUIRE_INIT();
     if (!O || !XH || !W || !B || !stat_dev) return fail(T4K_ERR_ARG, "t4k_conv2d_bn_fwd: null batch-norm tensor");
+    ConvPlanScope plan;
     int chunks = 0;
     int rc = conv2d_fwd_with_bn_rider(I, ICOPY, Y, F, Bc, N, H1, W1, C1, H0, W0, C0, K, S, P, &chunks, s);
     if (rc != T4K_OK) return rc;
@@ -507,6 +516,7 @@ int t4k_conv2d_bn_block_fwd(const float *I, float *ICOPY, float *Y, const float 
                             const t4k_poolblock *blk, int Hq, int Wq, t4k_stream_t s) {
     T4K_REQUIRE_INIT();
     if (!O || !XH || !W || !B || !stat_dev || !blk) return fail(T4K_ERR_ARG, "t4k_conv2d_bn_block_fwd: null tensor");
+    ConvPlanScope plan;
     int chunks = 0;
     int rc = conv2d_fwd_with_bn_rider(I, ICOPY, Y, F, Bc, N, H1, W1, C1, H0, W0, C0, K, S, P, &chunks, s);
     if (rc != T4K_OK) return rc;
@@ -520,13 +530,16 @@ int t4k_conv2d_block_fwd(const float *I, float *ICOPY, float *O, const float *F,
                          int N, int H1, int W1, int C1, int H0, int W0, int C0, int K, int S, int P, t4k_stream_t s) {
     T4K_REQUIRE_INIT();
     if (!blk) return fail(T4K_ERR_ARG, "t4k_conv2d_block_fwd: null block");
+    ConvPlanScope plan;
+    // the block is validated BEFORE the convolution runs and before H0 / KS is formed (KS = 0 divided by zero here): a rejected block writes nothing
+    { int rc = poolblock_check(blk, "t4k_conv2d_block_fwd"); if (rc) return rc; }
     if (!(I && O && F && B && fusable(blk, H0, W0, C1, C0, K, S, P))) {
         int rc = t4k_conv2d_fwd2(I, ICOPY, O, F, B, N, H1, W1, C1, H0, W0, C0, K, S, P, s); if (rc) return rc;
         return t4k_poolblock_fwd(O, blk, N, H0, W0, H0 / blk->KS, W0 / blk->KS, C0, s);
     }
     hipStream_t hs = t4k::S(s);
     // image-input layer (1 or 3 channels in, <= 16 out): the thread-per-pool-window vector kernel of conv_img.hip
-    if (K == 3 && P == 1 && H1 == H0 && W1 == W0 && conv_img_block_fwd(I, ICOPY, O, F, B, blk, N, H0, W0, C1, C0, hs)) { T4K_LAUNCH_CHECK(); return T4K_OK; }
+    if (K == 3 && P == 1 && H1 == H0 && W1 == W0 && conv_img_block_fwd(I, ICOPY, O, F, B, blk, N, H0, W0, C1, C0, hs)) { conv_plan_note("img_block"); T4K_LAUNCH_CHECK(); return T4K_OK; }
     // layer-0 copy: written by the conv launch itself when input and output share the pixel grid and the channels are few
     float *xc = (ICOPY && H1 == H0 && W1 == W0 && C1 <= 4) ? ICOPY : nullptr;
     if (ICOPY && !xc) { int rc = copy_input(ICOPY, I, N, H1, W1, C1, hs); if (rc) return rc; }
@@ -537,6 +550,7 @@ int t4k_conv2d_block_fwd(const float *I, float *ICOPY, float *O, const float *F,
     pe.rng = RngArg{0, 0, nullptr};
     if (pe.pre == T4K_L_DROPOUT) pe.rng = rng_draw(hs, (uint64_t)((npix * C0 + 3) >> 2), true);
     const GatherShape gs = gather_shape(npix, C0, C1, K);
+    conv_plan_note("gather_pool<%s,ks%d>", gather_filter(C1, K, C0), gs.ksplit);
     with_geometry(K, S, P, [&](auto geo) {                  // fusable(): stride 1, K 3 or 5
         using Ge = decltype(geo);
         if constexpr (Ge::K == 3 || Ge::K == 5)
@@ -557,6 +571,7 @@ int t4k_conv2d_bwd2(const float *I, const float *DO, float *DX, float *DX2, cons
                     int N, int H1, int W1, int C1, int H0, int W0, int C0,
                     int K, int S, int P, int train, t4k_stream_t s) {
     T4K_REQUIRE_INIT();
+    ConvPlanScope plan;
     if (!conv_supported(K, S, P))
         return fail(T4K_ERR_UNSUPPORTED, "nn#bconv kernel_size=%d stride=%d padding=%d not supported", K, S, P);
     if (!I || !DO || !F || N <= 0 || H0 <= 0 || W0 <= 0) return fail(T4K_ERR_ARG, "t4k_conv2d_bwd: bad argument");

@@ -974,6 +974,7 @@ void launch_conv_big(int K, int S, int P, hipStream_t hs, const float *X, float 
         // grids of two or more tiles per CU: 32-channel stages, half the LDS, at most 128 registers - two workgroups share a CU and one's stage barrier
         // (and prologue, and epilogue) runs under the other's MFMAs (as k_gemm_plain128<.., 32>)
         const bool two = lab.big8_bk32 && (lab.big8_bk32 >= 2 || (long)tiles_m * q.tiles_n >= 2L * st().cu_count);
+        conv_plan_note("%s<%d,%s>%s", BWD ? "dx_big8" : "big8", BN, two ? "bk32" : "bk64", rider ? "+bn" : "");
         const size_t lds8 = std::max(sizeof(float) * 2 * (128 + BN) * (two ? 32 : 64), sizeof(float) * 4 * 2 * (BN / 64) * 16 * 64);   // stages | the k-groups' meeting
         with_geometry(K, S, P, [&](auto geo) {
             using Ge = decltype(geo);
@@ -990,6 +991,7 @@ void launch_conv_big(int K, int S, int P, hipStream_t hs, const float *X, float 
     p.tiles_n = (Cout + BN - 1) / BN;
     const dim3 g((unsigned)(tiles_m * p.tiles_n)), b(256);
     const size_t lds = sizeof(float) * 2 * (128 + BN) * BK;
+    conv_plan_note("%s<%d>", BWD ? "dx_big" : "big", BN);
     with_geometry(K, S, P, [&](auto geo) {
         using Ge = decltype(geo);
         if (wide) launch_lds<k_convbig<Ge::K, Ge::S, Ge::P, BWD, 128>>(g, b, lds, hs, p);
@@ -1017,6 +1019,7 @@ int launch_conv_big_df(int K, int S, int P, hipStream_t hs, const float *I, cons
         ns = (npix + pp - 1) / pp;
         if ((size_t)ns * C1 * KK * C0 <= part_floats) {
             Cdw q = { I, DO, part, H0, W0, C1, C0, (int)pp, (int)ns, cit, ctl, kks, npix };
+            conv_plan_note("dfw<%d,%d>x%d", ciw, ntw, (int)ns);
             const long T = ns * ctl * kks;
             const dim3 gw((unsigned)(8 * ((T + 7) / 8))), bw(512);
             const size_t ldsw = std::max(sizeof(float) * 2 * (128 + bn) * bkp, sizeof(float) * 4 * 2 * ntw * 16 * 64);
@@ -1046,6 +1049,7 @@ int launch_conv_big_df(int K, int S, int P, hipStream_t hs, const float *I, cons
         if ((size_t)ns * C1 * KK * C0 > part_floats) return 0;
         const int ctl = ci_tiles * co_tiles;
         Cd8 q = { I, DO, st().d_zero, part, N, H1, W1, C1, H0, W0, C0, (int)pp, ci_tiles, npix, lab.df8_dbg, (int)ns, ctl, tp2 };
+        conv_plan_note("df8<tp%d>x%d", tp2 ? 2 : 1, (int)ns);
         const long groups = ns * ctl;
         const dim3 g8((unsigned)(8 * kks * ((groups + 7) / 8))), b8(512);
         with_geometry(K, S, P, [&](auto geo) {
@@ -1072,6 +1076,7 @@ int launch_conv_big_df(int K, int S, int P, hipStream_t hs, const float *I, cons
     // L2 instead of crossing the fabric once per tap (a trailing slice may be empty: it writes a zero slab)
     if (lab.df_xcd && nslice >= 8) { nslice = (nslice + 7) / 8 * 8; pps = (npix + nslice - 1) / nslice; pps = (pps + BK - 1) / BK * BK; }
     if ((size_t)nslice * C1 * KK * C0 > part_floats) return 0;
+    conv_plan_note("dfx%d", (int)nslice);
     CdP p = { I, DO, part, N, H1, W1, C1, H0, W0, C0, (int)pps, ci_tiles };
     const dim3 g((unsigned)nslice, (unsigned)(KK * ci_tiles), (unsigned)co_tiles), b(256);
     with_geometry(K, S, P, [&](auto geo) {

@@ -266,6 +266,7 @@ void launch_conv_few(int K, hipStream_t hs, const float *X, float *Y, float *Y2,
                        X, Y, Y2, XC, F, B, N, Hx, Wx, Cin, Hy, Wy, Cout, C0f, NG);
         };
         auto geo = [&](auto ch, auto vw) { if (K == 3) go(Geo<3, 1, 1>{}, ch, vw); else go(Geo<5, 1, 2>{}, ch, vw); };
+        conv_plan_note("%s<%d,%d,%d>", BWD ? "fewch" : "few", G, Cin == 1 ? 1 : 4, Cin == 1 ? 1 : v2 ? 2 : 1);
         if (Cin == 1) geo(int_c<1>{}, int_c<1>{});
         else if (v2)  geo(int_c<4>{}, int_c<2>{});
         else          geo(int_c<4>{}, int_c<1>{});
@@ -274,7 +275,10 @@ void launch_conv_few(int K, hipStream_t hs, const float *X, float *Y, float *Y2,
 template void launch_conv_few<false>(int, hipStream_t, const float *, float *, float *, float *, const float *, const float *, int, int, int, int, int, int, int, int, int, int);
 template void launch_conv_few<true>(int, hipStream_t, const float *, float *, float *, float *, const float *, const float *, int, int, int, int, int, int, int, int, int, int);
 
-bool conv_dx_few_ok(int K, int C1, int C0) { return C1 <= 4 && C1 * K * K * C0 <= LDS_FILTER_FLOATS; }
+bool conv_dx_few_ok(int K, int C1, int C0, const float *DO) {
+    const uintptr_t need = (C0 & 3) == 0 ? 15 : (C0 & 1) == 0 ? 7 : 3;       // the widest load k_conv_dx_few makes of a dO pixel row (a row starts C0 floats after the last)
+    return C1 <= 4 && C1 * K * K * C0 <= LDS_FILTER_FLOATS && (((uintptr_t)DO) & need) == 0;
+}
 
 void launch_conv_dx_few(int K, int S, int P, hipStream_t hs, const float *DO, float *DX, float *DX2, const float *F,
                         int N, int H0, int W0, int C0, int H1, int W1, int C1, FoldArgs fa) {
@@ -285,11 +289,13 @@ void launch_conv_dx_few(int K, int S, int P, hipStream_t hs, const float *DO, fl
             const int ppb = 4 * (64 / (C0 / 4));
             long gw = (npix + ppb - 1) / ppb; if (gw > (long)st().cu_count * conv_lab().dx_wide_wpc) gw = (long)st().cu_count * conv_lab().dx_wide_wpc;
             const dim3 gg((unsigned)gw + fa.nfold), bb(256);
+            conv_plan_note("dx_wide<%d>%s", C0 / 4, fa.nfold ? "+fold" : "");
             pick<8, 16, 32>(C0 / 4, [&](auto lpp) { T4K_LAUNCH((k_conv_dx_wide<CO, decltype(lpp)::value>), gg, bb, 0, hs, DO, DX, DX2, F, N, H0, W0, H1, W1, fa); });
             return;
         }
         long gx = (npix + 255) / 256; if (gx > 8192) gx = 8192;
         const dim3 g((unsigned)gx + fa.nfold), b(256);
+        conv_plan_note("dx_few%s", fa.nfold ? "+fold" : "");
         with_geometry(K, S, P, [&](auto geo) {
             using Ge = decltype(geo);
             T4K_LAUNCH((k_conv_dx_few<Ge::K, Ge::S, Ge::P, CO>), g, b, 0, hs, DO, DX, DX2, F, N, H0, W0, C0, H1, W1, fa);

@@ -395,6 +395,7 @@ bool conv_thin_fwd(const float *I, float *ICOPY, float *O, const float *F, const
     const dim3 g((unsigned)wg), b(256);
     const bool stat = bn_part && bn_chunks && ((long)N * H * W) % 32 == 0 && (size_t)wg * 2 * C0 <= bn_part_floats;    // batch-norm sums from the epilogue: whole tiles only
     if (stat) *bn_chunks = (int)wg;
+    conv_plan_note("thin%s%s", ICOPY ? "+copy" : "", stat ? "+stat" : "");
     pick<1, 2, 3, 4>(C1, [&](auto c1) { pick<1, 2>(C0 / 32, [&](auto nt) {
         with_flags([&](auto copy, auto nts, auto st_) {
             T4K_LAUNCH((k_conv_thin_fwd<c1.value, nt.value, copy.value, nts.value, st_.value>), g, b, 0, hs, I, O, ICOPY, F, B, N, H, W, ntile, bn_part);
@@ -423,7 +424,9 @@ bool conv_img_block_fwd(const float *I, float *ICOPY, float *O, const float *F, 
     const ConvLab &lab = conv_lab();
     if (!lab.img || (C1 != 1 && C1 != 3) || C0 > 16 || (H & 1) || (W & 1) || blk->KS != 2 || !blk->pool_layer) return false;
     if (blk->pre_layer == T4K_L_DROPOUT || blk->post_layer == T4K_L_DROPOUT) return false;      // mask draws stay with the Philox-carrying kernels
-    if ((C0 & 1) == 0 && (!aligned16(O) || !aligned16(blk->pool_out))) return false;
+    // even C0: every tensor of the block leaves in 8-byte stores (store_rows / store_win), absent ones (nullptr) pass
+    if ((C0 & 1) == 0 && (!aligned16(O) || !aligned16(blk->pool_out) || !aligned16(blk->pre_out) || !aligned16(blk->pre_mask) ||
+                          !aligned16(blk->post_out) || !aligned16(blk->post_mask) || !aligned16(blk->copy_out))) return false;
     ImgBlk p;
     p.X = I; p.F = F; p.B = B; p.XC = ICOPY; p.Y = O;
     p.P = blk->pre_out; p.Fpre = blk->pre_mask; p.Q = blk->pool_out; p.R = blk->post_out; p.Fpost = blk->post_mask; p.R2 = blk->copy_out;

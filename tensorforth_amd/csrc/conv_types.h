@@ -16,7 +16,8 @@ void launch_conv_few(int K, hipStream_t hs, const float *X, float *Y, float *Y2,
 // the dF fold a dX launch may carry in its first `nfold` workgroups (nfold == 0: nothing pending); see k_conv_dx_and_fold
 struct FoldArgs { const float *part; float *DF, *DB; int nslice, ndf, ntot, nfold; };
 // dX of an image-input layer (C1 <= 4, filter within the LDS stage): k_conv_dx_wide or k_conv_dx_few, either carries `fa`
-bool conv_dx_few_ok(int K, int C1, int C0);
+// (k_conv_dx_few reads dO 16 bytes at a time when C0 % 4 == 0 and 8 when C0 is even: DO must sit on that boundary, or the gather kernel takes the layer)
+bool conv_dx_few_ok(int K, int C1, int C0, const float *DO);
 void launch_conv_dx_few(int K, int S, int P, hipStream_t hs, const float *DO, float *DX, float *DX2, const float *F,
                         int N, int H0, int W0, int C0, int H1, int W1, int C1, FoldArgs fa);
 
@@ -37,6 +38,9 @@ bool conv_thin_fwd(const float *I, float *ICOPY, float *O, const float *F, const
 bool conv_thin_df(const float *I, const float *DO, float *part, size_t part_bytes, int N, int H, int W, int C1, int C0, int *nslice, hipStream_t hs);
 bool conv_img_block_fwd(const float *I, float *ICOPY, float *O, const float *F, const float *B, const t4k_poolblock *blk,
                         int N, int H, int W, int C1, int C0, hipStream_t hs);
+
+// ---- fused.hip: the validation of t4k_poolblock_fwd on its own (T4K_OK, or the status it would return, with the message set)
+int poolblock_check(const t4k_poolblock *b, const char *who);
 
 // ---- reduce.hip: batch-norm forward from the chunk partials a conv epilogue left
 int bn_stats_for(const float *I, float *stat, int N, int HW, int C, const float *part, int nchunk, t4k_stream_t s);

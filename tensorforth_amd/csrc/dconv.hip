@@ -52,14 +52,17 @@ int t4k_dconv2d_fwd(const float *I, float *O, const float *F, const float *B,
                     int N, int H1, int W1, int C1, int H0, int W0, int C0, int K, int S, int P, t4k_stream_t s) {
     T4K_REQUIRE_INIT();
     if (!I || !O || !F || !B || N <= 0 || C0 <= 0 || C1 <= 0 || H1 <= 0 || W1 <= 0) return fail(T4K_ERR_ARG, "t4k_dconv2d_fwd: bad argument");
+    ConvPlanScope plan;
     if ((H0 - K + 2 * P) / S + 1 != H1 || (W0 - K + 2 * P) / S + 1 != W1) return fail(T4K_ERR_ARG, "t4k_dconv2d_fwd: output %dx%d does not map back to %dx%d", H0, W0, H1, W1);
     const size_t nf = (size_t)C1 * K * K * C0;
     float *ft, *unused; int rc = scratch(nf + C1 + 64, &ft, &unused); if (rc) return rc;
     hipStream_t hs = t4k::S(s);
+    conv_plan_note("xpose");
     T4K_LAUNCH(k_filter_xpose<false>, dim3(grid_for((long)nf)), dim3(BLK), 0, hs, F, ft, C1, C0, K, 1);   // flipped: the dX kernel flips back
     T4K_LAUNCH_CHECK();
     // virtual conv: input O [N,H0,W0,C0] -> output I [N,H1,W1,C1]; its dX, given "dO" = I, is the transposed convolution
     rc = t4k_conv2d_bwd(O, I, O, ft, nullptr, nullptr, N, H0, W0, C0, H1, W1, C1, K, S, P, 0, s); if (rc) return rc;
+    conv_plan_note("bias");
     return t4k_bias(B, O, N * H0 * W0, C0, s);
 }
 
@@ -67,6 +70,7 @@ int t4k_dconv2d_bwd(const float *I, const float *DO, float *DX, const float *F, 
                     int N, int H1, int W1, int C1, int H0, int W0, int C0, int K, int S, int P, int train, t4k_stream_t s) {
     T4K_REQUIRE_INIT();
     if (!I || !DO || !F || N <= 0 || C0 <= 0 || C1 <= 0) return fail(T4K_ERR_ARG, "t4k_dconv2d_bwd: bad argument");
+    ConvPlanScope plan;
     if ((DF == nullptr) != (DB == nullptr)) return fail(T4K_ERR_ARG, "t4k_dconv2d_bwd: DF and DB go together");
     const size_t nf = (size_t)C1 * K * K * C0;
     float *ft, *dfv; int rc = scratch(nf + C1 + 64, &ft, &dfv); if (rc) return rc;   // + room for a C1-long vector behind each
@@ -78,11 +82,13 @@ int t4k_dconv2d_bwd(const float *I, const float *DO, float *DX, const float *F, 
         if ((size_t)(dbv - g_buf) + (size_t)C1 > g_cap) return fail(T4K_ERR_NOMEM, "dconv2d scratch (C1 = %d)", C1);
         T4K_HIP(hipMemsetAsync(dbv, 0, (size_t)C1 * sizeof(float), hs));
         rc = t4k_conv2d_bwd(DO, I, nullptr, F /* unused: no dX */, dfv, dbv, N, H0, W0, C0, H1, W1, C1, K, S, P, 1, s); if (rc) return rc;
+        conv_plan_note("xpose");
         T4K_LAUNCH(k_filter_xpose<true>, dim3(grid_for((long)nf)), dim3(BLK), 0, hs, dfv, DF, C0, C1, K, 0);
         T4K_LAUNCH_CHECK();
         rc = colsum_add(DO, DB, (long)N * H0 * W0, C0, hs); if (rc) return rc;
     }
     if (DX) {
+        conv_plan_note("xpose");
         T4K_LAUNCH(k_filter_xpose<false>, dim3(grid_for((long)nf)), dim3(BLK), 0, hs, F, ft, C1, C0, K, 0);
         T4K_LAUNCH_CHECK();
         float *zb = dfv + nf;                            // zero bias for the plain convolution (re-zeroed: dF may have used the slot)

@@ -248,6 +248,8 @@ int check_block(const t4k_poolblock *b, const char *who) {
 
 } // namespace
 
+namespace t4k { int poolblock_check(const t4k_poolblock *b, const char *who) { return check_block(b, who); } }   // t4k_conv2d_block_fwd validates before it convolves
+
 extern "C" {
 
 static int poolblock_fwd_impl(const float *X, const t4k_poolblock *b, int N, int H1, int W1, int H0, int W0, int C, t4k_stream_t s,

@@ -5,6 +5,7 @@
 #include "t4k_common.h"
 #include <stdarg.h>
 #include <string.h>
+#include <algorithm>
 
 namespace t4k {
 
@@ -15,6 +16,15 @@ int fail(int code, const char *fmt, ...) {
     vsnprintf(st().err, sizeof(st().err), fmt, ap);
     va_end(ap);
     return code;
+}
+void conv_plan_note(const char *fmt, ...) {
+    State &g = st();
+    if (g.conv_plan_depth <= 0 || g.conv_plan_len >= (int)sizeof(g.conv_plan) - 1) return;
+    if (g.conv_plan_len) g.conv_plan[g.conv_plan_len++] = ' ';
+    va_list ap; va_start(ap, fmt);
+    const int n = vsnprintf(g.conv_plan + g.conv_plan_len, sizeof(g.conv_plan) - g.conv_plan_len, fmt, ap);
+    va_end(ap);
+    if (n > 0) g.conv_plan_len = std::min(g.conv_plan_len + n, (int)sizeof(g.conv_plan) - 1);
 }
 int hip_fail(hipError_t e, const char *what) {
     snprintf(st().err, sizeof(st().err), "HIP error %d (%s) at %s", (int)e, hipGetErrorString(e), what);
@@ -114,6 +124,11 @@ const char *t4k_gemm_last_plan(void) {
     int n = snprintf(text, sizeof(text), "%s", g.gemm_plan);
     if (g.gemm_slabs > 1 && n < (int)sizeof(text)) n += snprintf(text + n, sizeof(text) - n, "x%d", g.gemm_slabs);
     if (g.gemm_fold && n < (int)sizeof(text)) snprintf(text + n, sizeof(text) - n, "+fold");
+    return text;
+}
+const char *t4k_conv_last_plan(void) {
+    static char text[sizeof(State::conv_plan)];
+    memcpy(text, st().conv_plan, sizeof(text));
     return text;
 }
 

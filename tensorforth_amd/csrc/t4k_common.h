@@ -47,6 +47,8 @@ struct State {
     const char *gemm_plan = "";       // the rung the last gemm_launch took (t4k_gemm_last_plan): set by the launch_* wrappers of gemm.hip, a literal each
     int         gemm_slabs = 1;       // ... its split-K slabs and whether a fold launch followed them
     bool        gemm_fold = false;
+    char        conv_plan[256] = {0}; // the engine decisions of the last conv entry in launch order (t4k_conv_last_plan): appended by the launch wrappers and dispatch functions of the conv units
+    int         conv_plan_len = 0, conv_plan_depth = 0;   // ... its length, and how many conv entries are open (t4k_dconv2d_* call t4k_conv2d_*: the outermost one starts the string)
     bool        gates_off = false;    // no kernel that makes workgroups wait for each other is chosen any more (t4k_gates_enable(0), or set by spin_check() after a timed-out wait)
     int         pending = 0;          // work a launch left for the NEXT entry point: bit 0 = a conv stack's dF | dB partial fold.  Set, flushed and consumed under pending_mu():
                                       // whichever thread reaches an entry point first flushes (a gradient read from a second thread must see the folded dF | dB);
@@ -71,6 +73,13 @@ struct RngArg { uint64_t base, seed; uint64_t *state; };
 RngArg rng_draw(hipStream_t hs, uint64_t nq, bool sample_keyed = false);    // host: reserve nq counters (4 elements each) of the stream for one launch (optim.hip)
 
 int  fail(int code, const char *fmt, ...);
+// t4k_conv_last_plan: one token per engine decision, separated by blanks.  A conv entry point opens a ConvPlanScope; tokens noted outside one
+// (colsum_add behind a linear layer) are dropped.  Host code only: plain stores into State.
+void conv_plan_note(const char *fmt, ...);
+struct ConvPlanScope {
+    ConvPlanScope()  { State &g = st(); if (g.conv_plan_depth++ == 0) { g.conv_plan_len = 0; g.conv_plan[0] = 0; } }
+    ~ConvPlanScope() { --st().conv_plan_depth; }
+};
 int  hip_fail(hipError_t e, const char *what);
 inline hipStream_t S(t4k_stream_t s) { return s ? (hipStream_t)s : st().stream; }
 // workspace of the stream a kernel is launched on: work forked to a side stream must not share partial slabs
