@@ -103,7 +103,8 @@ const char *t4k_gemm_last_plan(void);
  * "+fold" behind it when the chunks are folded by a second launch), "thin_dfxN+b", "df_mfmaxN+b" ("+b": the bias row of the slab is dB); the fold of
  * the slices: "fold_add" or "df_fold" as launches of their own, or "+fold" behind the dX engine that carries it.  dX: "dx_big8<..>", "dx_big<..>",
  * "dx_wide<lanes per pixel>", "dx_few", "fewch<G,CH,VW>", "dx_and_fold<raw|staged,ksN>".  The transposed convolution adds "xpose" per filter
- * transposition and "bias".  Valid until the next call of this function; plain, unsynchronised stores as t4k_gemm_last_plan. */
+ * transposition and "bias".  The run-time-geometry entries (t4k_conv2d_geo_fwd / _bwd): "geo<64|128,v4|v1,f4|f1>" (channel tile, 16-byte or dword
+ * gather, 16-byte or dword filter loads), "geo_dfxN<tap|rows,d4|rows,d1>" (N slices, the bias row in the slab; a tile's rows one tap's channels, or (c1, tap) rows with 16-byte / dword dO), "fold_add" or "df_fold", "geo_dx<64|128,v4|v1>".  Valid until the next call of this function; plain, unsynchronised stores as t4k_gemm_last_plan. */
 const char *t4k_conv_last_plan(void);
 
 /* Library streams own a private workspace, so independent work (e.g. dW beside dX) may be forked
@@ -412,6 +413,42 @@ int t4k_conv2d_bwd2(const float *I, const float *DO, float *DX, float *DX2, cons
                     float *DF, float *DB,
                     int N, int H1, int W1, int C1, int H0, int W0, int C0,
                     int K, int S, int P, int train, t4k_stream_t s);
+/* conv2d with RUN-TIME geometry (csrc/conv_geo.hip): what the reference leaves open - "TODO: stride, dilation" nmath.tcu:12, nmath.cu:269, nmath.h:25;
+ * "TODO: dilation" model.cpp:125 - finished for k_conv2d / k_dconv2d nmath.tcu:12,34-104,211-338 and Model::_iconv model.cpp:124-137.
+ * Admitted: K 1..7, S 1..4, D 1..4, 0 <= P <= D(K-1), H0 == (H1 + 2P - D(K-1) - 1)/S + 1 >= 1 (W likewise), every extent >= 1, N H0 W0 and N H1 W1
+ * below 2^31, one dF | dB slab ((C1 K K + 1) C0 floats) within half the stream workspace.  An extent below 1, a NULL tensor or an H0 / W0 that the
+ * geometry does not give: T4K_ERR_ARG; a geometry outside the set: T4K_ERR_UNSUPPORTED; either leaves a t4k_last_error text and writes nothing.
+ * The four geometries of t4k_conv2d_fwd (D = 1) are admitted too and run on THESE kernels, not the specialised ones.
+ *   O[n,i,j,c0] = B[c0] + sum F[((c1*K+ky)*K+kx)*C0+c0] * I[n,i*S+ky*D-P,j*S+kx*D-P,c1]     (zero border; O is written once, not accumulated)
+ * ICOPY (may be NULL) receives I as in t4k_conv2d_fwd2, by a copy command.  One kernel launch; no allocation, no synchronisation (legal under capture). */
+int t4k_conv2d_geo_fwd(const float *I, float *ICOPY, float *O, const float *F, const float *B,
+                       int N, int H1, int W1, int C1, int H0, int W0, int C0,
+                       int K, int S, int P, int D, t4k_stream_t s);
+/* its backward (k_dconv2d nmath.tcu:211-338 finished for nmath.tcu:12): DB[c0] += sum dO, DF += sum I*dO (both only if train); DX (overwritten, every
+ * element stored exactly once) and the optional second copy DX2, which may be I itself (`in = dx`, backprop.cu:185: dF | dB read I first).
+ * DX == NULL: dF | dB only; DF == DB == NULL: dX only - as t4k_conv2d_bwd2.
+ * DX is the TEXTBOOK gradient, dX[n,y,x,c1] = sum F[c1,ky,kx,c0] * dO[n,i,j,c0] over the taps with i*S + ky*D - P == y, j*S + kx*D - P == x - what
+ * autograd gives - NOT the rotated-filter dX of t4k_conv2d_bwd (quirk a-11), which stays with the four geometries the reference itself computes:
+ * for geometries it never computes there is nothing to be faithful to.  On those four, this DX equals t4k_conv2d_bwd's DX of the filter rotated by 180 degrees.
+ * At most three launches (slabs, their fold, dX), one for dX alone; fixed summation order, no atomics. */
+int t4k_conv2d_geo_bwd(const float *I, const float *DO, float *DX, float *DX2, const float *F,
+                       float *DF, float *DB,
+                       int N, int H1, int W1, int C1, int H0, int W0, int C0,
+                       int K, int S, int P, int D, int train, t4k_stream_t s);
+/* The plan the two entries above take (nmath.tcu:12,34-104,211-338; model.cpp:124-137) when the tensors the 16-byte paths read - I and F of the forward; dO, F and I of the backward - are ALL on 16 bytes (aligned bit 0 set) or are not,
+ * and DB lies right behind DF (DB == DF + C1 K K C0: a layer's gradient block; aligned bit 1 clear) or does not (bit 1 set);
+ * pure host arithmetic: launches nothing, needs no device; the launch code calls the same function.  Admission and return codes as above.
+ * out = { forward channel tile (64 | 128; the pixel tile is 128),
+ *         forward load path (bit 0: 16-byte gather of I - C1 % 4 == 0 and aligned; bit 1: 16-byte loads of F - C0 % 4 == 0 and aligned),
+ *         dX channel tile (64 | 128), dX load path (1: 16-byte loads of dO and F - C0 % 4 == 0 and aligned),
+ *         dF load path (bit 0: 16-byte loads of dO; bit 1: a tile's rows are the channels of ONE tap and I is gathered 16 bytes at a time -
+ *                       C1 % 4 == 0, C1 >= 32, bit 0; otherwise the rows are (c1, ky, kx) side by side and I is gathered by dwords),
+ *         dF slices (pixel slices of whole 32-pixel stages aiming at 1024 workgroups over the 64 x 64 tiles, shrunk until the slabs fit 8 MiB of workspace -
+ *                    down to one, which may take the 32 MiB),
+ *         the fold behind them (1: k_fold_add - up to 32 slices and DB right behind DF, because it walks whole slabs into one destination; 2: k_conv_df_fold),
+ *         launches of a whole backward (3) }. */
+int t4k_conv2d_geo_plan(int N, int H1, int W1, int C1, int C0, int K, int S, int P, int D,
+                        int aligned, int out[8]);
 /* Transposed convolution layer (word `dconv2d`, L_DCONV; allocation Model::_iconv txn model.cpp:121-180, dispatch forward.cu:110 /
  * backprop.cu:137 - the reference routes the layer's forward through the conv backward routine and vice versa but never finished it, see
  * csrc/dconv.hip).  I[N,H1,W1,C1] -> O[N,H0,W0,C0], F = T4(C1,K,K,C0), (H0-K+2P)/S+1 == H1:

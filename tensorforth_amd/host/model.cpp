@@ -30,14 +30,24 @@ Model &Model::add(int fn, uint32_t n, DU bias, uint16_t *opt) {
         const uint32_t N1 = in.N(), H1 = in.H(), W1 = in.W(), C1 = in.C(), C0 = n;
         const uint16_t K = opt[0], S = opt[1];
         const uint16_t P = (K > 1 && opt[2]) ? opt[2] : (K - 1) / 2;
-        uint16_t H0, W0;
+        uint16_t H0, W0, D = 0;
         if (txn) { const uint16_t P0 = (H1 + P * 2 - K) % S; H0 = (H1 - 1) * S - P * 2 + K + P0; W0 = (W1 - 1) * S - P * 2 + K + P0; }
-        else     { H0 = (H1 - K + P * 2) / S + 1; W0 = (H1 - K + P * 2) / S + 1; }      // W0 from H1: reference quirk :137
-        if ((!txn && K != 1 && K != 3 && K != 5) || (txn && K != 4)) {
+        else {
+            // conv2d takes any K 1..7 with stride, padding and dilation (the reference: "TODO: dilation" model.cpp:125): a D cell of 0 means 1
+            if (K < 1 || K > 7) { hprintf("nn#iconv %s f=[%d,%d]? 1x1 to 7x7 supported only.\n", LAYER_NAME[fn], K, K); return *this; }
+            D = opt[3] ? opt[3] : 1;
+            if (S < 1 || S > 4 || D > 4 || P > D * (K - 1) || (int)H1 + P * 2 < D * (K - 1) + 1) {
+                hprintf("nn#iconv %s stride=%d padding=%d dilation=%d?\n", LAYER_NAME[fn], S, P, D);
+                return *this;
+            }
+            H0 = (H1 - D * (K - 1) - 1 + P * 2) / S + 1; W0 = (H1 - D * (K - 1) - 1 + P * 2) / S + 1;      // W0 from H1: reference quirk :137
+        }
+        if (txn && K != 4) {
             hprintf("nn#iconv %s f=[%d,%d]? 1x1, 3x3, 4x4, and 5x5 supported only.\n", LAYER_NAME[fn], K, K);
             return *this;
         }
         in.stride[0] = in.stride[1] = S; in.stride[2] = in.stride[3] = P; in.xparm = bias;
+        in.iparm = D;                                   // convolutions use iparm for nothing else; 1 (and the 0 of a transposed layer) = undilated
         Tensor *f = in.grad[0] = &T4(C1, K, K, C0);
         Tensor *b = in.grad[1] = &VEC(C0);
         in.grad[2] = &T4(C1, K, K, C0).zeros();
@@ -99,6 +109,35 @@ Model &Model::add(int fn, uint32_t n, DU bias, uint16_t *opt) {
 // Both are OFF by default: measured on MI355X (ROCm 7.2, LeNet step, 40 launches) the single in-order stream is the
 // fastest schedule - 0.26 ms/step vs 0.28 (hipGraph replay) vs 0.31 (forked side stream; every cross-queue event edge
 // costs more than the ~4.5 us in-order dispatch it hides).  What pays is fewer launches (fused kernels below).
+// ---- conv2d layers outside the reference's four geometries.  ONE predicate decides the route at every call site of the conv family:
+// such a layer runs t4k_conv2d_geo_fwd / _bwd and joins no fused group.  The two entries are referenced weakly: over a C-ABI without them (the CPU
+// oracle) the layer keeps the refusal at forward / backprop.
+#pragma weak t4k_conv2d_geo_fwd
+#pragma weak t4k_conv2d_geo_bwd
+static int conv_D(const Tensor &in) { return in.iparm > 1 ? in.iparm : 1; }
+static bool conv_geo(const Tensor &in) {
+    if (in.grad_fn != T4K_L_CONV) return false;
+    const int K = in.grad[0]->H(), S = in.stride[0], P = in.stride[2];
+    const bool four = (K == 1 && S == 1 && P == 0) || (K == 3 && S == 1 && P == 1) || (K == 4 && S == 2 && P == 1) || (K == 5 && S == 1 && P == 2);
+    return !four || conv_D(in) > 1;
+}
+static void geo_refusal(const char *who, int K, int S, int P, int D) {      // the line the four-geometry entries leave through chk(), the dilation named where there is one
+    if (D > 1) hprintf("%s failed: %s kernel_size=%d stride=%d padding=%d dilation=%d not supported\n", who, who, K, S, P, D);
+    else       hprintf("%s failed: %s kernel_size=%d stride=%d padding=%d not supported\n", who, who, K, S, P);
+}
+static int geo_fwd(Tensor &in, Tensor &out, const float *x, float *cp, t4k_stream_t s) {
+    const int K = in.grad[0]->H(), S = in.stride[0], P = in.stride[2];
+    if (!t4k_conv2d_geo_fwd) { geo_refusal("nn#fconv", K, S, P, conv_D(in)); return T4K_ERR_UNSUPPORTED; }
+    return chk(t4k_conv2d_geo_fwd(x, cp, out.data, in.grad[0]->data, in.grad[1]->data, out.N(), in.H(), in.W(), in.C(), out.H(), out.W(), out.C(),
+                                  K, S, P, conv_D(in), s), "nn#fconv");
+}
+static int geo_bwd(Tensor &in, Tensor &out, const float *dy, float *dx, float *dx2, const float *w, bool grads, int train, t4k_stream_t s) {
+    const int K = in.grad[0]->H(), S = in.stride[0], P = in.stride[2];
+    if (!t4k_conv2d_geo_bwd) { geo_refusal("nn#bconv", K, S, P, conv_D(in)); return T4K_ERR_UNSUPPORTED; }
+    return chk(t4k_conv2d_geo_bwd(in.data, dy, dx, dx2, w, grads ? in.grad[2]->data : nullptr, grads ? in.grad[3]->data : nullptr,
+                                  in.N(), in.H(), in.W(), in.C(), out.H(), out.W(), out.C(), K, S, P, conv_D(in), train, s), "nn#bconv");
+}
+
 Model *Model::current = nullptr;
 void (*Model::grad_hook)(int, long, long, void *) = nullptr;
 void *Model::grad_hook_user = nullptr;
@@ -137,6 +176,7 @@ void Model::materialize_dx0() {
         const float *w = w0_saved_ ? w0_save_->data : in.grad[0]->data, *dy = dx0_dy_;
         const bool conv = dx0_conv_;
         clear_dx0_marks();
+        if (conv && conv_geo(in)) { geo_bwd(in, o, dy, in.grad[4]->data, in.data, w, false, 0, stream()); return; }
         if (conv) {                                     // dX into the scratch tensor and over x, as the eager launch leaves them (backprop.cu:185)
             chk(t4k_conv2d_bwd2(in.data, dy, in.grad[4]->data, in.data, w, nullptr, nullptr, in.N(), in.H(), in.W(), in.C(), o.H(), o.W(), o.C(),
                                 in.grad[0]->H(), in.stride[0], in.stride[2], 0, stream()), "nn#bconv dX0");
@@ -234,7 +274,7 @@ int Model::stack_at(int i, t4k_conv_stage *st, int &ops) {
     while (ns < 3 && j < L && at(j).grad_fn == T4K_L_CONV) {
         Tensor &in = at(j), &out = at(j + 1);
         const int K = in.grad[0]->H();
-        if (in.stride[0] != 1 || in.stride[2] != K / 2 || !(K & 1) || out.H() != in.H() || out.W() != in.W()) break;
+        if (in.stride[0] != 1 || in.stride[2] != K / 2 || !(K & 1) || out.H() != in.H() || out.W() != in.W() || conv_geo(in)) break;   // (a dilated layer is no stage)
         t4k_conv_stage &t = st[ns]; memset(&t, 0, sizeof(t));
         t.F = in.grad[0]->data; t.B = in.grad[1]->data; t.O = out.data;
         t.DF = in.grad[2] ? in.grad[2]->data : nullptr; t.DB = in.grad[3] ? in.grad[3]->data : nullptr;
@@ -426,6 +466,10 @@ void Model::run_forward(Tensor &input) {
             x = prob.data; i++;
             continue;
         }
+        if (fused && conv_geo(in)) {                    // run-time geometry: the layer alone (with the layer-0 copy), no group; what stands behind it runs as behind any lone conv
+            geo_fwd(in, out, x, cp, stream());
+            x = out.data; continue;
+        }
         if (fused && in.grad_fn == T4K_L_CONV) {        // a conv layer and what rides in its launch: the widest group first
             t4k_conv_stage stg[3]; int ops = 0;
             const int ns = use_stack ? stack_at(i, stg, ops) : 0;
@@ -480,6 +524,7 @@ const float *Model::fstep(Tensor &in, Tensor &out, const float *x) {
     t4k_stream_t s = stream();
     switch (fn) {
     case T4K_L_CONV:
+        if (conv_geo(in)) { geo_fwd(in, out, x, nullptr, s); break; }
         chk(t4k_conv2d_fwd(x, out.data, in.grad[0]->data, in.grad[1]->data, out.N(), in.H(), in.W(), in.C(),
                            out.H(), out.W(), out.C(), in.grad[0]->H(), in.stride[0], in.stride[2], s), "nn#fconv"); break;
     case T4K_L_DCONV:                                   // transposed convolution: the scatter form of the conv backward (forward.cu:110, see csrc/dconv.hip)
@@ -809,11 +854,20 @@ Model::Back Model::bstep(int i, Tensor &in, Tensor &out, const float *dy, bool l
         Tensor &dx = *in.grad[4];
         const int N = in.N(), H1 = in.H(), W1 = in.W(), C1 = in.C(), H0 = out.H(), W0 = out.W(), C0 = out.C();
         const int K = in.grad[0]->H(), S = in.stride[0], P = in.stride[2];
+        const bool geo = conv_geo(in);
         if (i == 0 && train && use_lazy_dx0 && use_fusion && !(trace && *trace) && !concurrent() && !capturing_ && !use_graphs && in.grad[2] && in.grad[3] &&
             offer_dx0(dy, true)) {                      // the net's first layer: dF | dB now, dX0 when a word asks
+            if (geo) { geo_bwd(in, out, dy, nullptr, nullptr, in.grad[0]->data, true, 1, s); return { in.data }; }
             chk(t4k_conv2d_bwd(in.data, dy, nullptr, in.grad[0]->data, in.grad[2]->data, in.grad[3]->data,
                                N, H1, W1, C1, H0, W0, C0, K, S, P, 1, s), "nn#bconv dF");
             return { in.data };
+        }
+        if (geo && !concurrent()) { geo_bwd(in, out, dy, dx.data, in.data, in.grad[0]->data, train != 0, train, s); return { in.data }; }
+        if (geo) {                                      // forked: dF | dB beside dX, then x = dX
+            if (train) geo_bwd(in, out, dy, nullptr, nullptr, in.grad[0]->data, true, 1, fork());
+            geo_bwd(in, out, dy, dx.data, nullptr, in.grad[0]->data, false, 0, s);
+            lazy_copy(dx.data, in);
+            return { dx.data };
         }
         if (!concurrent()) {                            // one stream: dF|dB read x first, then dX lands in the scratch tensor AND over x
             chk(t4k_conv2d_bwd2(in.data, dy, dx.data, in.data, in.grad[0]->data, train ? in.grad[2]->data : nullptr, train ? in.grad[3]->data : nullptr,

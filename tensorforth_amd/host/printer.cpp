@@ -97,7 +97,9 @@ static std::string parm_s(Tensor &in, Tensor &out) {     // aio_model.cpp:103-14
     const DU p = in.xparm;
     std::ostringstream o;
     switch (fn) {
-    case T4K_L_CONV: case T4K_L_DCONV: o << "bias=" << p << ", C=" << out.C() << ", K=" << in.grad[0]->H() << ", S=" << S << ", P=" << in.stride[2]; break;
+    case T4K_L_CONV: case T4K_L_DCONV: o << "bias=" << p << ", C=" << out.C() << ", K=" << in.grad[0]->H() << ", S=" << S << ", P=" << in.stride[2];
+        if (fn == T4K_L_CONV && in.iparm > 1) o << ", D=" << in.iparm;      // a dilated layer says so; every other line is the reference's
+        break;
     case T4K_L_LINEAR: o << "bias=" << p << ", H=" << in.grad[0]->H(); break;
     case T4K_L_SELU: case T4K_L_LEAKYRL: case T4K_L_ELU: o << "bias=" << p; break;
     case T4K_L_DROPOUT: o << "rate=" << p * 100.0 << '%'; break;
