@@ -546,8 +546,7 @@ constexpr int head_rpg() { return (CS_H_EA + CS_WAVES - 1) / CS_WAVES; }        
 __device__ __forceinline__ int grp_member(int img) { return (img >> 3) & 7; }
 __device__ __forceinline__ int grp_image(int img, int j) { return (img & ~63) | (img & 7) | (j << 3); }
 // W1 PREFETCH (CS_H_PF rows per wave, as many as the LDS left over by the stack holds).  The first linear layer reads the band's slice of
-// every row of W1 - 196 KB per workgroup for the LeNet head, at the ~18 B/clk a CU's outstanding misses sustain that was 10.5 k of the
-// forward's 35 k cycles.  The bytes cannot shrink (a per-sample kernel has no reuse of W1 across images), but their latency can hide: at
+// every row of W1 - 196 KB per workgroup for the LeNet head.  The bytes cannot shrink (a per-sample kernel has no reuse of W1 across images), but their latency can hide: at
 // kernel START every wave asks the LDS-DMA engine (global_load_lds_dwordx4: no VGPRs, no instruction slots while in flight) for its first
 // CS_H_PF rows, which land under the two convolution stages; the head then reads those rows out of LDS and fetches only the rest.
 __device__ __forceinline__ void head_prefetch(const FwdArgs &p, float *L, int img, int band) {
@@ -593,6 +592,20 @@ __device__ __forceinline__ void head_prefetch(const FwdArgs &p, float *L, int im
         }
     }
 }
+// The lanes' shares of NR dot products added up across the wave, all rows SIDE BY SIDE: one butterfly step of every row is issued before the first is waited
+// for.  A row's own chain - six dependent cross-lane exchanges through the LDS crossbar, ~110 cycles each - is unchanged, so every sum keeps its order and
+// its bits; done row after row, the 13 rows of a wave's share of W1 were 78 exchange latencies in a chain (8.6 k of the matvec's 10.2 k cycles, and the
+// reason neither a prefetch of W1 nor a warm L2 ever changed it); side by side they are 6.
+template <int NR> __device__ __forceinline__ void lanes_sum(float (&a)[NR]) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        float t[NR];
+#pragma unroll
+        for (int r = 0; r < NR; r++) t[r] = __shfl_xor(a[r], off, 64);
+#pragma unroll
+        for (int r = 0; r < NR; r++) a[r] += t[r];
+    }
+}
 __device__ __forceinline__ void head_fwd(const FwdArgs &p, float *L, int img, int band) {
     constexpr int S = CS_NS - 1, row0C = W0(S) * SH[S].C0, E1 = H0(S) * row0C, EA = CS_H_EA, EB = CS_H_EB, MID = CS_H_MID;
     constexpr int nk_max_ = own_rows_max(S) * row0C, KI = (nk_max_ + 63) / 64, RB = KI <= 9 ? 7 : (KI <= 12 ? 5 : 3);      // rows of W1 in flight per trip (RB x KI registers)
@@ -603,7 +616,8 @@ __device__ __forceinline__ void head_fwd(const FwdArgs &p, float *L, int img, in
     float *part = L + out_off(), *x2 = part + ((EA + 3) & ~3), *y2 = x2 + ((EA + 3) & ~3);
     // 16-byte loads when every band's slice of a W1 row starts and ends on a 16-byte boundary (LeNet: 560 | 420 floats): a quarter of the load
     // instructions for the same bytes.  The matvec moves N x E1 x EA x 4 bytes through the L2s (50 MB for the LeNet head: every image reads W1
-    // once - a per-sample kernel has no reuse across images), which is what this phase costs (5.5 of the head's 8 us with 4-byte loads).
+    // once - a per-sample kernel has no reuse across images); what the phase costs is one round trip, those bytes through the CU's L1 and the
+    // lanes' sums (lanes_sum above: they were most of it while they ran row after row).
     constexpr bool V4 = head_v4_ok();
     CS_STAMP(11);
 #if CS_H_GRP
@@ -675,12 +689,10 @@ __device__ __forceinline__ void head_fwd(const FwdArgs &p, float *L, int img, in
         v4f xq[KI4];
 #pragma unroll
         for (int q = 0; q < KI4; q++) { const int k4 = lane + q * 64; xq[q] = k4 < nk4 ? *reinterpret_cast<const v4f *>(x + 4 * k4) : v4f{0.f, 0.f, 0.f, 0.f}; }
-        auto dot_row = [&](const v4f (&wr)[KI4]) {
+        auto dot_lane = [&](const v4f (&wr)[KI4]) {                                                // this lane's share of a row's dot product (lanes_sum adds the lanes up)
             float a = 0.f;
 #pragma unroll
             for (int q = 0; q < KI4; q++) { a = fmaf(xq[q][0], wr[q][0], a); a = fmaf(xq[q][1], wr[q][1], a); a = fmaf(xq[q][2], wr[q][2], a); a = fmaf(xq[q][3], wr[q][3], a); }
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) a += __shfl_xor(a, off, 64);
             return a;
         };
         for (int e0 = PF, trip = 0; e0 < hr.nrw || trip == 0; e0 += RB4, trip++) {
@@ -694,27 +706,33 @@ __device__ __forceinline__ void head_fwd(const FwdArgs &p, float *L, int img, in
                     for (int q = 0; q < KI4; q++) { const int k4 = lane + q * 64; wq[r][q] = w[k4 < nk4 ? k4 : 0]; }
                 }
             }
+            __builtin_amdgcn_sched_barrier(0);                    // every load of the trip is issued before the first row is consumed: ONE round trip (the scheduler would otherwise
+                                                                  // sink loads between the rows' multiply-adds to save registers, a dependent round trip each)
             if (PF > 0 && trip == 0) {
                 // the prefetched rows first, while those loads fly.  vmcnt counts in issue order: once no more than the loads just issued are
                 // outstanding, this wave's DMA transfers (its oldest vector-memory operations) have landed; a wave reads only rows it fetched itself
                 if (RG > 0) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(RB4 * KI4 < 63 ? RB4 * KI4 : 63) : "memory");
                 else        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                float al[PF > 0 ? PF : 1];
 #pragma unroll
                 for (int sl = 0; sl < PF; sl++) {
                     v4f wl[KI4];
                     const float *src = L + head_pf_off() + (wave * CS_H_PF + sl) * head_pf_row();
 #pragma unroll
                     for (int q = 0; q < KI4; q++) { const int k4 = lane + q * 64; wl[q] = *reinterpret_cast<const v4f *>(src + 4 * (k4 < nk4 ? k4 : 0)); }
-                    const float a = dot_row(wl);
-                    if (lane == 0 && sl < hr.nrw) part[hr.row(sl)] = a;
+                    al[sl] = dot_lane(wl);
                 }
+                lanes_sum(al);
+#pragma unroll
+                for (int sl = 0; sl < PF; sl++) if (lane == 0 && sl < hr.nrw) part[hr.row(sl)] = al[sl];
             }
             if (RG > 0) {
+                float ar[RB4];
 #pragma unroll
-                for (int r = 0; r < RB4; r++) {
-                    const float a = dot_row(wq[r]);
-                    if (lane == 0 && row[r] >= 0) part[row[r]] = a;
-                }
+                for (int r = 0; r < RB4; r++) ar[r] = dot_lane(wq[r]);
+                lanes_sum(ar);
+#pragma unroll
+                for (int r = 0; r < RB4; r++) if (lane == 0 && row[r] >= 0) part[row[r]] = ar[r];
             }
         }
     } else {
@@ -729,15 +747,18 @@ __device__ __forceinline__ void head_fwd(const FwdArgs &p, float *L, int img, in
 #pragma unroll
                 for (int q = 0; q < KI; q++) { const int k = lane + q * 64; wv[r][q] = w[k < nk ? k : 0]; }
             }
+            __builtin_amdgcn_sched_barrier(0);                    // (as above: all loads of the trip first)
+            float ar[RB];
 #pragma unroll
             for (int r = 0; r < RB; r++) {
                 float a = 0.f;
 #pragma unroll
                 for (int q = 0; q < KI; q++) a = fmaf(xv[q], wv[r][q], a);
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) a += __shfl_xor(a, off, 64);
-                if (lane == 0 && e0 + r < EA) part[e0 + r] = a;
+                ar[r] = a;
             }
+            lanes_sum(ar);
+#pragma unroll
+            for (int r = 0; r < RB; r++) if (lane == 0 && e0 + r < EA) part[e0 + r] = ar[r];
         }
     }
 #endif
@@ -803,16 +824,17 @@ __device__ __forceinline__ void head_fwd(const FwdArgs &p, float *L, int img, in
     }
     lds_barrier();
     CS_STAMP(13);
+    float a2[NR2];
 #pragma unroll
     for (int r = 0; r < NR2; r++) {                                 // second linear layer: a wave per output, lanes along its EA inputs
-        const int j = wave + r * CS_WAVES;
         float a = 0.f;
 #pragma unroll
         for (int q = 0; q < NE2; q++) { const int e = lane + q * 64; a = fmaf(e < EA ? x2[e] : 0.f, w2v[r][q], a); }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) a += __shfl_xor(a, off, 64);
-        if (lane == 0 && j < EB) y2[j] = a + b2v[r];
+        a2[r] = a;
     }
+    lanes_sum(a2);
+#pragma unroll
+    for (int r = 0; r < NR2; r++) { const int j = wave + r * CS_WAVES; if (lane == 0 && j < EB) y2[j] = a2[r] + b2v[r]; }
     lds_barrier();
     if (tid < 64) {                                               // softmax over the EB outputs (k_softmax's arithmetic, as k_linsmall_fwd)
         const bool live = tid < EB;

@@ -59,6 +59,27 @@ int main(int argc, char **argv) {
             for (int b = 0; b < N * 4; b++) if (h[b * 32 + k] && h[b * 32]) { const double d = (double)(h[b * 32 + k] - h[b * 32]); sum += d; cnt++; if (d > mx) mx = d; }
             if (cnt) printf("  %2d: avg %8.0f  max %8.0f  (%d workgroups)\n", k, sum / cnt, mx, cnt);
         }
+        // forward: the same per DISPATCH ROUND.  Workgroups are placed in the order of their linear id (blockIdx.x fastest); the first `cus` of them start on
+        // L2s that hold none of the launch's operands, the later ones on CUs whose XCD has already read W1.  11 -> 12 is the head's W1 matvec.
+        if (!bwd) {
+            int split = 1, bsplit = 1, cus = 256; t4k_conv_stack_plan(st, 2, N, &split, &bsplit);
+            { hipDeviceProp_t pr; if (hipGetDeviceProperties(&pr, 0) == hipSuccess) cus = pr.multiProcessorCount; }
+            for (int late = 0; late < 2; late++) {
+                double sum[32] = {0}, d1112 = 0, mx1112 = 0; int cnt[32] = {0}, c1112 = 0;
+                for (int b = 0; b < N * split; b++) {
+                    const unsigned long long *s = &h[(size_t)b * 32];
+                    const int w = b / split + N * (b % split);
+                    if ((w >= cus) != (late != 0) || !s[0]) continue;
+                    for (int k = 1; k < 32; k++) if (s[k]) { sum[k] += (double)(s[k] - s[0]); cnt[k]++; }
+                    if (s[11] && s[12]) { const double d = (double)(s[12] - s[11]); d1112 += d; c1112++; if (d > mx1112) mx1112 = d; }
+                }
+                if (!cnt[2]) continue;
+                printf("  %s (linear id %s %d, split %d):", late ? "later rounds" : "first round", late ? ">=" : "<", cus, split);
+                for (int k = 1; k < 32; k++) if (cnt[k]) printf(" %d:%.0f", k, sum[k] / cnt[k]);
+                if (c1112) printf("  | 11->12 avg %.0f max %.0f (%d workgroups)", d1112 / c1112, mx1112, c1112);
+                printf("\n");
+            }
+        }
         // banded backward: the two wave roles of every stage (stamps 3 / 4 + 8 S: dF role, thread 0; 24 / 25 + 2 S: dX role, first lane of wave 8;
         // 5 + 8 S: thread 0 past the barrier the roles share) - how long each role ran and how long it then stood at the barrier
         for (int S = 2; bwd && S >= 0; S--) {
