@@ -466,6 +466,30 @@ int t4k_pool(int layer, const float *I, float *O, int N, int H1, int W1, int H0,
  * tile, writes dy at the first arg-max/min; avg: dy/KS^2; usample: broadcast) */
 int t4k_dpool(int layer, float *I, const float *DY, int N, int H1, int W1, int H0, int W0, int C,
               int KS, t4k_stream_t s);
+/* avg / max / min pooling with RUN-TIME geometry (csrc/pool_geo.hip): what k_pool / k_dpool nmath.tcu:400-568 and Model::_ipool model.cpp:261 leave
+ * out - their window is the stride, 2 or 3, without padding.  Admitted: layer AVGPOOL / MAXPOOL / MINPOOL, K 1..16, S 1..16, 0 <= P <= K/2, K <= H1 + 2P and
+ * K <= W1 + 2P, N H1 W1 and N H0 W0 below 2^31 - otherwise T4K_ERR_UNSUPPORTED; an extent below 1: T4K_ERR_ARG.  A FLOOR grid, H0 == (H1 + 2P - K)/S + 1 and
+ * W0 == (W1 + 2P - K)/S + 1 (from W1).  Pure host arithmetic: launches nothing, needs no device; the launch code calls the same function.
+ * out = { H0, W0, channel vector width of the forward (4 | 1), of the backward (4 | 1) };
+ * aligned bit 0: I and O on 16 bytes (and CODE, where given, on 4), bit 1: DY and DX on 16 bytes (and CODE on 4); a width of 4 also needs C % 4 == 0 */
+int t4k_pool_geo_plan(int layer, int N, int H1, int W1, int C, int K, int S, int P, int aligned, int out[4]);
+/* the forward (k_pool nmath.tcu:400-474 finished for any window, stride and padding; Model::_ipool model.cpp:261).  Window (i, j) covers rows
+ * i*S - P .. i*S - P + K - 1, columns likewise; every channel on its own.  max / min: the extreme of the cells INSIDE the image, the first one in
+ * (ky, kx) row-major order by a strict compare (torch max_pool2d, ties included); avg: (sum of the cells inside the image) / (float)(K K) - padding counts
+ * as zeros, torch's count_include_pad=True.  NaN operands: unspecified.
+ * CODE (may be NULL: inference, avg) receives the winning tap ky*K + kx of every output element as one byte, [n][i][j][c] with a pixel pitch of
+ * 4 ceil(C / 4) bytes, the pad bytes written as 0; avg stores none.  An H0 / W0 that the rule does not give, a NULL I or O: T4K_ERR_ARG.
+ * One launch; no allocation, no synchronisation (legal under capture). */
+int t4k_pool_geo_fwd(int layer, const float *I, float *O, unsigned char *CODE,
+                     int N, int H1, int W1, int C, int H0, int W0, int K, int S, int P, t4k_stream_t s);
+/* its backward (k_dpool nmath.tcu:475-568 finished likewise; model.cpp:261): the TEXTBOOK gradient, dX[n,y,x,c] = sum of DY[n,i,j,c] over the windows
+ * whose winning tap is (y, x) (max / min, from CODE - required, else T4K_ERR_ARG) or (sum of DY over the covering windows) / (float)(K K) (avg; CODE
+ * ignored), the windows in ascending (i, j) order, no atomics: the same bits on every run.  EVERY element of DX is stored exactly once - a cell that
+ * no window covers (S > K, rows / columns behind the last window) gets 0, where t4k_dpool leaves the forward value.  The forward input is not read:
+ * DX may be its buffer (the in-place convention of t4k_dpool without its race on overlapping windows); DY must not overlap DX.
+ * One launch; no allocation, no synchronisation. */
+int t4k_pool_geo_bwd(int layer, const unsigned char *CODE, const float *DY, float *DX,
+                     int N, int H1, int W1, int C, int H0, int W0, int K, int S, int P, t4k_stream_t s);
 /* k_sgd nmath.cu:419: dg=DG/Nw; beta~0: G-=lr*dg else M=b*M+(1-b)*dg, G-=lr*M; DG=0 */
 int t4k_sgd(float *G, float *DG, float *M, int Nw, float lr, float beta, long n, t4k_stream_t s);
 /* k_adam nmath.cu:438 (no bias correction, eps outside sqrt): zeroes DG */

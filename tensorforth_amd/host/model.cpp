@@ -75,6 +75,19 @@ Model &Model::add(int fn, uint32_t n, DU bias, uint16_t *opt) {
         in.grad[4] = &T4(1, in.H(), in.W(), in.C());
         layer.push_back(&T4(in.N(), in.H(), in.W(), in.C())); break;
     case T4K_L_AVGPOOL: case T4K_L_MAXPOOL: case T4K_L_MINPOOL: {    // _ipool model.cpp:260-274 (ceil dims)
+        if (opt) {
+            // the vector form takes any K 1..16 with stride and padding on a FLOOR grid, W0 from W1 (the reference has window = stride in {2, 3} only)
+            const int K = opt[0], S = opt[1], P = opt[2], H1 = in.H(), W1 = in.W(), C = in.C();
+            if (K < 1 || K > 16) { hprintf("nn#ipool %s k=%dx%d? 1x1 to 16x16 supported only\n", LAYER_NAME[fn], K, K); return *this; }
+            if (S < 1 || S > 16 || P > K / 2 || K > H1 + 2 * P || K > W1 + 2 * P) { hprintf("nn#ipool %s stride=%d padding=%d?\n", LAYER_NAME[fn], S, P); return *this; }
+            const int H0 = (H1 + 2 * P - K) / S + 1, W0 = (W1 + 2 * P - K) / S + 1;
+            in.stride[0] = K; in.stride[1] = S; in.stride[2] = P; in.stride[3] = 0;
+            in.iparm = 1;                               // the mark of the vector form: pooling layers use iparm for nothing else, and {3,1,1,0} is what `3 maxpool` stores
+            // max / min keep the winning tap of every output element, one byte each at a pixel pitch of 4 ceil(C / 4): bytes in a float tensor
+            if (fn != T4K_L_AVGPOOL) in.grad[4] = &T4(in.N(), H0, W0, (C + 3) / 4).zeros();
+            layer.push_back(&T4(in.N(), H0, W0, C));
+            break;
+        }
         const uint16_t k = (uint16_t)n;
         if (k != 2 && k != 3) { hprintf("nn#ipool k=%dx%d? 2x2 and 3x3 supported only\n", k, k); return *this; }
         in.stride[0] = k; in.stride[1] = 1; in.stride[2] = 1; in.stride[3] = 0;
@@ -136,6 +149,25 @@ static int geo_bwd(Tensor &in, Tensor &out, const float *dy, float *dx, float *d
     if (!t4k_conv2d_geo_bwd) { geo_refusal("nn#bconv", K, S, P, conv_D(in)); return T4K_ERR_UNSUPPORTED; }
     return chk(t4k_conv2d_geo_bwd(in.data, dy, dx, dx2, w, grads ? in.grad[2]->data : nullptr, grads ? in.grad[3]->data : nullptr,
                                   in.N(), in.H(), in.W(), in.C(), out.H(), out.W(), out.C(), K, S, P, conv_D(in), train, s), "nn#bconv");
+}
+// ---- pooling layers of the vector form, `vector{ K S P } maxpool | avgpool | minpool`.  ONE predicate decides the route at every call site of
+// the pool family: such a layer runs t4k_pool_geo_fwd / _bwd and joins no fused run, stack or block.  The entries are referenced weakly: over a C-ABI
+// without them (the CPU oracle) the layer is admitted, shaped and printed, and forward / backprop refuse it - there is no host-side fallback.
+#pragma weak t4k_pool_geo_fwd
+#pragma weak t4k_pool_geo_bwd
+static bool pool_geo(const Tensor &in) {
+    return (in.grad_fn == T4K_L_AVGPOOL || in.grad_fn == T4K_L_MAXPOOL || in.grad_fn == T4K_L_MINPOOL) && in.iparm == 1;
+}
+static unsigned char *pool_codes(Tensor &in) { return in.grad[4] ? (unsigned char *)in.grad[4]->data : nullptr; }
+static int pool_geo_fwd(Tensor &in, Tensor &out, const float *x, t4k_stream_t s) {
+    const int K = in.stride[0], S = in.stride[1], P = in.stride[2];
+    if (!t4k_pool_geo_fwd) { hprintf("nn#fpool failed: nn#fpool kernel_size=%d stride=%d padding=%d not supported\n", K, S, P); return T4K_ERR_UNSUPPORTED; }
+    return chk(t4k_pool_geo_fwd(in.grad_fn, x, out.data, pool_codes(in), out.N(), in.H(), in.W(), in.C(), out.H(), out.W(), K, S, P, s), "nn#fpool");
+}
+static int pool_geo_bwd(Tensor &in, Tensor &out, const float *dy, t4k_stream_t s) {      // dX over x, the reference's in-place convention: the backward reads no forward input
+    const int K = in.stride[0], S = in.stride[1], P = in.stride[2];
+    if (!t4k_pool_geo_bwd) { hprintf("nn#bpool failed: nn#bpool kernel_size=%d stride=%d padding=%d not supported\n", K, S, P); return T4K_ERR_UNSUPPORTED; }
+    return chk(t4k_pool_geo_bwd(in.grad_fn, pool_codes(in), dy, in.data, out.N(), in.H(), in.W(), in.C(), out.H(), out.W(), K, S, P, s), "nn#bpool");
 }
 
 Model *Model::current = nullptr;
@@ -248,7 +280,7 @@ void Model::plan_runs() {
     for (int i = 0; i < L; ) {
         int j = i, pre = -1, pool = -1, post = -1, flat = -1;
         if (j < L && (is_mact(at(j).grad_fn) || at(j).grad_fn == T4K_L_DROPOUT)) pre = j++;
-        if (j < L && is_pool(at(j).grad_fn) && (at(j).H() % at(j).stride[0] == 0) && (at(j).W() % at(j).stride[0] == 0)) pool = j++;
+        if (j < L && is_pool(at(j).grad_fn) && !pool_geo(at(j)) && (at(j).H() % at(j).stride[0] == 0) && (at(j).W() % at(j).stride[0] == 0)) pool = j++;
         if (j < L && (pool >= 0 || pre >= 0) &&
             (is_mact(at(j).grad_fn) || (at(j).grad_fn == T4K_L_DROPOUT && !(pre >= 0 && at(pre).grad_fn == T4K_L_DROPOUT)))) post = j++;   // activation or dropout behind
                                                                 // (`leakyrelu dropout` of the GAN nets, `maxpool dropout` of the CIFAR nets): one dropout per run
@@ -542,6 +574,7 @@ const float *Model::fstep(Tensor &in, Tensor &out, const float *x) {
     case T4K_L_LOGSMAX:                                 // _flogsoftmax forward.cu:245-259 (log10 and exp(x) kept: reference bug a-16)
         chk(t4k_logsoftmax(x, out.data, out.N(), (int)out.HWC(), s), "nn#flogsoftmax"); break;
     case T4K_L_AVGPOOL: case T4K_L_MAXPOOL: case T4K_L_MINPOOL:
+        if (pool_geo(in)) { pool_geo_fwd(in, out, x, s); break; }
         chk(t4k_pool(fn, x, out.data, out.N(), in.H(), in.W(), out.H(), out.W(), out.C(), in.stride[0], s), "nn#fpool"); break;
     case T4K_L_BATCHNM:
         chk(t4k_batchnorm_fwd(x, out.data, in.grad[4]->data, in.grad[0]->data, in.grad[1]->data, in.mtum[4]->data,
@@ -902,6 +935,7 @@ Model::Back Model::bstep(int i, Tensor &in, Tensor &out, const float *dy, bool l
     case T4K_L_RELU: case T4K_L_TANH: case T4K_L_SELU: case T4K_L_LEAKYRL: case T4K_L_ELU: case T4K_L_DROPOUT:
         chk(t4k_tt_op(T4K_MUL, dy, in.grad[4]->data, in.data, (long)in.numel, s), "nn#bactivate"); break;
     case T4K_L_AVGPOOL: case T4K_L_MAXPOOL: case T4K_L_MINPOOL:
+        if (pool_geo(in)) { pool_geo_bwd(in, out, dy, s); break; }
         chk(t4k_dpool(fn, in.data, dy, out.N(), in.H(), in.W(), out.H(), out.W(), out.C(), in.stride[0], s), "nn#bpool"); break;
     case T4K_L_BATCHNM:
         chk(t4k_batchnorm_bwd(in.grad[0]->data, dy, in.grad[4]->data, in.data, in.grad[2]->data, in.grad[3]->data,

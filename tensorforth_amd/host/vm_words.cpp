@@ -431,6 +431,18 @@ void VM::nnop(int op) {
         Tensor::softmax_axes(TTOS(), mask);
         return;
     }
+    // beyond the reference ( N V -- N ): a vector{ K S P } on top of a model makes `maxpool` / `avgpool` / `minpool` a pooling layer of any K 1..16 with
+    // stride and padding; a missing or 0 S cell means K, a missing P cell 0.  The reference prints "( N n -- ) one param required!" here
+    if ((op == T4K_L_AVGPOOL || op == T4K_L_MAXPOOL || op == T4K_L_MINPOOL) && TOS1T() && TTOS().rank == 1 && SP() > 0 && is_m(SS(-1))) {
+        Tensor &t = TTOS();
+        std::vector<float> vo; t.to_host(vo, std::min<uint64_t>(t.numel, 3));
+        DU x = POP(); DROP(x);                           // the vector is dropped and freed, as VM::conv does
+        uint16_t opt[4] = {0, 0, 0, 0};
+        for (size_t i = 0; i < vo.size(); i++) opt[i] = (uint16_t)(int)vo[i];
+        if (!opt[1]) opt[1] = opt[0];
+        MTOS().add(op, opt[0], 0, opt);
+        return;
+    }
     if (TOS1T()) {                                       // tensor ops (destructive)
         Tensor &t = TTOS();
         switch (op) {
