@@ -490,6 +490,29 @@ int t4k_pool_geo_fwd(int layer, const float *I, float *O, unsigned char *CODE,
  * One launch; no allocation, no synchronisation. */
 int t4k_pool_geo_bwd(int layer, const unsigned char *CODE, const float *DY, float *DX,
                      int N, int H1, int W1, int C, int H0, int W0, int K, int S, int P, t4k_stream_t s);
+/* up-sampling by any integer factor (csrc/upsample.hip): what _iup model.cpp:294-310 (2x2 and 3x3 only), `const int me = in.iparm; ///< upsample method, TODO`
+ * forward.cu:318 / backprop.cu:289 and the enum of ntypes.h:53-58, which no kernel reads, leave out.  The methods are that enum's. */
+enum { T4K_UP_NEAREST = 0, T4K_UP_LINEAR, T4K_UP_BILINEAR, T4K_UP_CUBIC };   /* ntypes.h:53-58 */
+/* The rule, separable and the same on both axes: H0 == K H1, W0 == K W1 (from W1); output row i = q K + r, 0 <= r < K, reads T taps at input rows
+ * clamp(q + base[r] + a, 0, H1 - 1), a = 0 .. T - 1, with weights wt[r][a]:
+ *   nearest (T 1): base 0, {1}                                                                   torch interpolate(scale_factor=K, mode='nearest')
+ *   linear = bilinear (T 2): u = 2r + 1 - K; u >= 0: base 0, l = u / 2K, else base -1, l = (u + 2K) / 2K; {1 - l, l}        mode='bilinear', align_corners=False
+ *   cubic (T 4): that base - 1 and l; {c2(l + 1), c1(l), c1(1 - l), c2(2 - l)}, the cubic-convolution polynomials with A = -0.75  mode='bicubic', align_corners=False
+ * Admitted: method 0..3, K 1..16 (cubic 1..8: the 64-float table), N H0 W0 below 2^31 - otherwise T4K_ERR_UNSUPPORTED; an extent below 1: T4K_ERR_ARG.
+ * Pure host arithmetic: launches nothing, needs no device; the launch code calls the same function.
+ * out = { H0, W0, channel vector width of the forward (4 | 1), of the backward (4 | 1) }; aligned bit 0: I and O on 16 bytes, bit 1: DY and DX on 16 bytes; a
+ * width of 4 also needs C % 4 == 0.  wt[r * 4 + a] and base[r] (either may be NULL) receive the table the kernels take: l as a rational, the polynomials
+ * in double, each weight rounded once to float; unused cells 0. */
+int t4k_upsample_plan(int method, int N, int H1, int W1, int C, int K, int aligned, int out[4], float wt[64], int base[16]);
+/* the forward (_fupsample forward.cu:318 finished for any factor and for the method it ignores): every channel on its own,
+ * O[n,i,j,c] = sum_a sum_b (wt[ri][a] wt[rj][b]) I[n, row_a, col_b, c] in ascending (a, b) order.  NaN operands: unspecified.
+ * An H0 / W0 that the rule does not give, a NULL I or O: T4K_ERR_ARG.  One launch; no allocation, no synchronisation (legal under capture). */
+int t4k_upsample_fwd(int method, const float *I, float *O, int N, int H1, int W1, int C, int H0, int W0, int K, t4k_stream_t s);
+/* its backward (_bupsample backprop.cu:285-300 finished likewise; where the 2x2 / 3x3 route takes t4k_pool(AVGPOOL) and a scale map, this is ONE launch): the transpose of the forward
+ * map, clamped taps included - a border row of DX collects every tap that was clamped onto it -, summed in ascending (i, j) order without atomics: the
+ * same bits on every run, every element of DX stored exactly once.  The forward input is not read: DX may be its buffer (the in-place convention of
+ * t4k_pool_geo_bwd); DY must not overlap DX.  One launch; no allocation, no synchronisation. */
+int t4k_upsample_bwd(int method, const float *DY, float *DX, int N, int H1, int W1, int C, int H0, int W0, int K, t4k_stream_t s);
 /* k_sgd nmath.cu:419: dg=DG/Nw; beta~0: G-=lr*dg else M=b*M+(1-b)*dg, G-=lr*M; DG=0 */
 int t4k_sgd(float *G, float *DG, float *M, int Nw, float lr, float beta, long n, t4k_stream_t s);
 /* k_adam nmath.cu:438 (no bias correction, eps outside sqrt): zeroes DG */

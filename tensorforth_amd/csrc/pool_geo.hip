@@ -5,27 +5,13 @@
 // once (zeros included) and the forward input is never read: dX may land in its buffer.
 #include "t4k_common.h"
 #include "launch.h"
+#include "fastdiv.h"
 
 using namespace t4k;
 
 namespace {
 
 enum { PG_AVG = 0, PG_MAX = 1, PG_MIN = 2 };
-
-// x / d for x below 2^31 without a divide instruction sequence: m = ceil(2^(31 + l) / d) with l = ceil(log2 d) fits 32 bits and (x m) >> (31 + l) is the
-// quotient for every 31-bit x (Granlund & Montgomery, "Division by invariant integers using multiplication", PLDI 1994, theorem 4.2 with N = 31); d = 1 has
-// m = 0 and passes x through.  The host works m out once per launch; a work item's digits and its window range cost a multiply and a shift each instead
-// of the ~30 instructions of a 32-bit divide, which made the backward - seven divisions per 16 bytes stored - instruction-bound.
-struct FastDiv { unsigned m, s, d; };
-FastDiv fast_div(int d) {
-    FastDiv f = { 0u, 0u, (unsigned)d };
-    if (d > 1) {
-        const int l = 32 - __builtin_clz((unsigned)d - 1);
-        f.m = (unsigned)((((uint64_t)1 << (31 + l)) + (unsigned)d - 1) / (unsigned)d); f.s = (unsigned)(l - 1);
-    }
-    return f;
-}
-__device__ __forceinline__ unsigned fdiv(unsigned x, const FastDiv &f) { return f.m ? __umulhi(x, f.m) >> f.s : x; }
 
 struct PoolGeoP {
     int N, H1, W1, C, H0, W0, K, S, P;
@@ -34,13 +20,8 @@ struct PoolGeoP {
     long total;                        // work items: pixels * CV
     FastDiv dCV, dW, dH, dS;           // by CV, by the width and height of the grid the work items run over (outputs forward, inputs backward), by S
 };
-// work item -> (channel group, column, row, image) of an [N][H][W][CV] grid; the pixel index comes back too.  Items that fit 31 bits (every tensor below
-// 2^31 items) take the multiplies, the others the 64-bit divides of t4k_common.h
 __device__ __forceinline__ void pg_digits(long z, const PoolGeoP &p, int W, int H, int &cv, int &j, int &i, int &n, long &pix) {
-    if (z < 0x7fffffffL) {
-        const unsigned q = (unsigned)z, px = fdiv(q, p.dCV), t = fdiv(px, p.dW), m = fdiv(t, p.dH);
-        cv = (int)(q - px * (unsigned)p.CV); j = (int)(px - t * (unsigned)W); i = (int)(t - m * (unsigned)H); n = (int)m; pix = (long)px;
-    } else { split2(z, p.CV, cv, pix); split3(pix, W, H, j, i, n); }
+    fd_digits(z, p.CV, W, H, p.dCV, p.dW, p.dH, cv, j, i, n, pix);
 }
 
 template <int KIND> __device__ __forceinline__ bool pg_better(float e, float best) { return KIND == PG_MAX ? e > best : e < best; }   // strict: the first extreme wins

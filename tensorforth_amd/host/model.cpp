@@ -103,9 +103,13 @@ Model &Model::add(int fn, uint32_t n, DU bias, uint16_t *opt) {
         layer.push_back(&T4(in.N(), in.H(), in.W(), in.C()));
     } break;
     case T4K_L_USAMPLE: {                               // _iup model.cpp:294-310
+        // any factor 1..16 and the four methods of ntypes.h:53-58 (cubic: 1..8); the reference has 2x2 and 3x3 and ignores the method
         const uint16_t k = (uint16_t)n;
-        if (k != 2 && k != 3) { hprintf("nn#iup k=%dx%d? only 2x2 and 3x3 supported\n", k, k); return *this; }
-        in.iparm = (int)bias;
+        const int me = (int)bias;
+        if (me < T4K_UP_NEAREST || me > T4K_UP_CUBIC) { hprintf("nn#iup method=%d?\n", me); return *this; }
+        const int kmax = me == T4K_UP_CUBIC ? 8 : 16;
+        if (k < 1 || k > kmax) { hprintf("nn#iup k=%dx%d? 1x1 to %dx%d supported only\n", k, k, kmax, kmax); return *this; }
+        in.iparm = me;
         in.stride[0] = k; in.stride[1] = 1; in.stride[2] = 1; in.stride[3] = 1;
         layer.push_back(&T4(in.N(), in.H() * k, in.W() * k, in.C()));
     } break;
@@ -168,6 +172,25 @@ static int pool_geo_bwd(Tensor &in, Tensor &out, const float *dy, t4k_stream_t s
     const int K = in.stride[0], S = in.stride[1], P = in.stride[2];
     if (!t4k_pool_geo_bwd) { hprintf("nn#bpool failed: nn#bpool kernel_size=%d stride=%d padding=%d not supported\n", K, S, P); return T4K_ERR_UNSUPPORTED; }
     return chk(t4k_pool_geo_bwd(in.grad_fn, pool_codes(in), dy, in.data, out.N(), in.H(), in.W(), in.C(), out.H(), out.W(), K, S, P, s), "nn#bpool");
+}
+// ---- upsample layers beyond the reference's form, any factor 1..16 and the methods linear / bilinear / cubic.  ONE predicate decides the
+// route at both call sites: `2 upsample` and `3 upsample` with method 0 keep t4k_dpool / t4k_pool + scale, every other layer runs t4k_upsample_fwd / _bwd.
+// No upsample layer joins a fused run, stack or block.  The entries are referenced weakly: over a C-ABI without them (the CPU oracle) the layer is
+// admitted, shaped and printed, and forward / backprop refuse it - there is no host-side fallback.
+#pragma weak t4k_upsample_fwd
+#pragma weak t4k_upsample_bwd
+static bool up_geo(const Tensor &in) {
+    return in.grad_fn == T4K_L_USAMPLE && ((in.stride[0] != 2 && in.stride[0] != 3) || in.iparm != T4K_UP_NEAREST);
+}
+static int up_geo_fwd(Tensor &in, Tensor &out, const float *x, t4k_stream_t s) {
+    const int K = in.stride[0];
+    if (!t4k_upsample_fwd) { hprintf("nn#fupsample failed: nn#fupsample size=%d method=%d not supported\n", K, in.iparm); return T4K_ERR_UNSUPPORTED; }
+    return chk(t4k_upsample_fwd(in.iparm, x, out.data, in.N(), in.H(), in.W(), in.C(), out.H(), out.W(), K, s), "nn#fupsample");
+}
+static int up_geo_bwd(Tensor &in, Tensor &out, const float *dy, t4k_stream_t s) {        // dX over x in ONE launch: the backward reads no forward input
+    const int K = in.stride[0];
+    if (!t4k_upsample_bwd) { hprintf("nn#bupsample failed: nn#bupsample size=%d method=%d not supported\n", K, in.iparm); return T4K_ERR_UNSUPPORTED; }
+    return chk(t4k_upsample_bwd(in.iparm, dy, in.data, in.N(), in.H(), in.W(), in.C(), out.H(), out.W(), K, s), "nn#bupsample");
 }
 
 Model *Model::current = nullptr;
@@ -580,6 +603,7 @@ const float *Model::fstep(Tensor &in, Tensor &out, const float *x) {
         chk(t4k_batchnorm_fwd(x, out.data, in.grad[4]->data, in.grad[0]->data, in.grad[1]->data, in.mtum[4]->data,
                               out.N(), out.H() * out.W(), out.C(), s), "nn#fbatchnorm"); break;
     case T4K_L_USAMPLE:                                 // nearest: broadcast each cell to a kxk tile
+        if (up_geo(in)) { up_geo_fwd(in, out, x, s); break; }
         chk(t4k_dpool(T4K_L_USAMPLE, out.data, x, in.N(), out.H(), out.W(), in.H(), in.W(), in.C(), in.stride[0], s), "nn#fupsample"); break;
     default: hprintf("nn#fstep layer=%d not supported\n", fn);
     }
@@ -941,6 +965,7 @@ Model::Back Model::bstep(int i, Tensor &in, Tensor &out, const float *dy, bool l
         chk(t4k_batchnorm_bwd(in.grad[0]->data, dy, in.grad[4]->data, in.data, in.grad[2]->data, in.grad[3]->data,
                               in.mtum[4]->data, in.N(), in.H() * in.W(), in.C(), train, s), "nn#bbatchnorm"); break;
     case T4K_L_USAMPLE:                                 // gradient of nearest upsampling = sum over the tile = k*k * avgpool
+        if (up_geo(in)) { up_geo_bwd(in, out, dy, s); break; }
         chk(t4k_pool(T4K_L_AVGPOOL, dy, in.data, in.N(), out.H(), out.W(), in.H(), in.W(), in.C(), in.stride[0], s), "nn#bupsample");
         in.map(T4K_SCALE, (DU)(in.stride[0] * in.stride[0])); break;
     default: hprintf("nn#bstep layer=%d not supported\n", fn);

@@ -486,7 +486,7 @@ void VM::nnop(int op) {
     case T4K_L_FLATTEN: case T4K_L_SELU: case T4K_L_SOFTMAX: case T4K_L_LOGSMAX: pstr("( N -- ) no param needed!"); break;
     case T4K_L_LEAKYRL: case T4K_L_ELU: case T4K_L_DROPOUT: case T4K_L_AVGPOOL: case T4K_L_MAXPOOL: case T4K_L_MINPOOL:
     case T4K_L_BATCHNM: pstr("( N n -- ) one param required!"); break;
-    case T4K_L_USAMPLE:
+    case T4K_L_USAMPLE:                                  // ( N m n -- N' ): m = 0 nearest, 1 linear, 2 bilinear, 3 cubic is now honoured, n = 1..16
         if (M2V()) { uint16_t n = (uint16_t)POPi(); DU m = POP(); MTOS().add(op, n, m); }
         else pstr("( N [mtum] n -- ) for upsample required?");
         break;
