@@ -104,7 +104,8 @@ const char *t4k_gemm_last_plan(void);
  * the slices: "fold_add" or "df_fold" as launches of their own, or "+fold" behind the dX engine that carries it.  dX: "dx_big8<..>", "dx_big<..>",
  * "dx_wide<lanes per pixel>", "dx_few", "fewch<G,CH,VW>", "dx_and_fold<raw|staged,ksN>".  The transposed convolution adds "xpose" per filter
  * transposition and "bias".  The run-time-geometry entries (t4k_conv2d_geo_fwd / _bwd): "geo<64|128,v4|v1,f4|f1>" (channel tile, 16-byte or dword
- * gather, 16-byte or dword filter loads), "geo_dfxN<tap|rows,d4|rows,d1>" (N slices, the bias row in the slab; a tile's rows one tap's channels, or (c1, tap) rows with 16-byte / dword dO), "fold_add" or "df_fold", "geo_dx<64|128,v4|v1>".  Valid until the next call of this function; plain, unsynchronised stores as t4k_gemm_last_plan. */
+ * gather, 16-byte or dword filter loads), "geo_dfxN<tap|rows,d4|rows,d1>" (N slices, the bias row in the slab; a tile's rows one tap's channels, or (c1, tap) rows with 16-byte / dword dO), "fold_add" or "df_fold", "geo_dx<64|128,v4|v1>".  The grouped entries (t4k_conv2d_grp_fwd / _bwd): "grp_dw<v4|v1>" (depthwise, Cg1 == 1) or "grp<v4|v1>" (4 output
+ * channels per thread with 16-byte loads and stores, or one with dwords), "grp_dfxN" (N slices, the bias row in the slab), "fold_add" or "df_fold", "grp_dx<v4|v1>".  Valid until the next call of this function; plain, unsynchronised stores as t4k_gemm_last_plan. */
 const char *t4k_conv_last_plan(void);
 
 /* Library streams own a private workspace, so independent work (e.g. dW beside dX) may be forked
@@ -448,6 +449,49 @@ int t4k_conv2d_geo_bwd(const float *I, const float *DO, float *DX, float *DX2, c
  *         the fold behind them (1: k_fold_add - up to 32 slices and DB right behind DF, because it walks whole slabs into one destination; 2: k_conv_df_fold),
  *         launches of a whole backward (3) }. */
 int t4k_conv2d_geo_plan(int N, int H1, int W1, int C1, int C0, int K, int S, int P, int D,
+                        int aligned, int out[8]);
+/* Grouped and depthwise conv2d with RUN-TIME geometry (csrc/conv_group.hip): the entries above with the channels cut into G groups.  The reference has
+ * NO groups - Model::_iconv model.cpp:121-180 allocates the dense T4(C1, K, K, C0) and k_conv2d ("TODO: stride, dilation" nmath.tcu:12) walks every input
+ * channel - so there is no quirk to keep: this finishes those two for torch's conv2d(groups=G).  With Cg1 = C1 / G and Cg0 = C0 / G, output channel c0
+ * belongs to group g = c0 / Cg0, F = T4(Cg1, K, K, C0):
+ *   O[n,i,j,c0] = B[c0] + sum_{cg < Cg1, ky, kx} F[((cg*K+ky)*K+kx)*C0+c0] * I[n,i*S+ky*D-P,j*S+kx*D-P,g*Cg1+cg]     (zero border; O is written once, not accumulated)
+ * = torch.nn.functional.conv2d(groups=G) with weight[c0][cg][ky][kx] = F[cg,ky,kx,c0].
+ * Admitted: the geometries of t4k_conv2d_geo_fwd (K 1..7, S 1..4, D 1..4, 0 <= P <= D(K-1), H0 == (H1 + 2P - D(K-1) - 1)/S + 1 >= 1, W likewise, N H0 W0 and
+ * N H1 W1 below 2^31), 1 <= G with C1 % G == 0 and C0 % G == 0, one dF | dB slab ((Cg1 K K + 1) C0 floats) within 32 MiB, Cg1 and the channel tiles of the dF grid (C0 / 128, dwords: C0 / 32) within 65535 - anything else:
+ * T4K_ERR_UNSUPPORTED.
+ * An extent below 1, a NULL tensor or an H0 / W0 that the geometry does not give: T4K_ERR_ARG.  Either leaves a t4k_last_error text and writes nothing.
+ * G == 1 is admitted and runs on THESE kernels (the host never sends it: a dense layer stays with the entries above).
+ * ICOPY (may be NULL) receives I by a copy command.  One kernel launch; no allocation, no synchronisation (legal under capture). */
+int t4k_conv2d_grp_fwd(const float *I, float *ICOPY, float *O, const float *F, const float *B,
+                       int N, int H1, int W1, int C1, int H0, int W0, int C0,
+                       int K, int S, int P, int D, int G, t4k_stream_t s);
+/* its backward (k_dconv2d nmath.tcu:211-338 finished likewise; the reference has no groups): the TEXTBOOK gradients, what autograd gives.
+ * DB[c0] += sum dO, DF[cg,ky,kx,c0] += sum I[.., g*Cg1+cg] * dO[.., c0] (both only if train); DX (overwritten, every element stored exactly once - an
+ * input pixel no window covers gets 0) sums, for input channel c1 of group g, the Cg0 output channels of that group in ascending order; the optional
+ * second copy DX2 may be I itself (dF | dB read I first).  DX == NULL: dF | dB only; DF == DB == NULL: dX only; DF and DB go together.
+ * At most three launches (slabs, their fold, dX), one for dX alone; fixed summation order, no atomics; the slabs live in the stream workspace half that
+ * t4k_conv2d_geo_bwd uses and are folded by the same two kernels. */
+int t4k_conv2d_grp_bwd(const float *I, const float *DO, float *DX, float *DX2, const float *F,
+                       float *DF, float *DB,
+                       int N, int H1, int W1, int C1, int H0, int W0, int C0,
+                       int K, int S, int P, int D, int G, int train, t4k_stream_t s);
+/* The plan the two entries above take (the reference has no groups: model.cpp:121-180, nmath.tcu:12) when EVERY tensor a 16-byte path touches - I, F and O
+ * of the forward; dO, F, I, DX and DX2 of the backward - is on 16 bytes (aligned bit 0 set) or is not, and DB lies right behind DF (DB == DF + Cg1 K K C0;
+ * aligned bit 1 clear) or does not (bit 1 set); pure host arithmetic: launches nothing, needs no device; the launch code calls the same function.
+ * Admission and return codes as above; a refusal writes nothing into out.
+ * out = { engine (1: depthwise, Cg1 == 1; 2: general, an inner loop over the Cg1 input channels of the group),
+ *         load path of the forward and of the dF | dB kernel: 0 one channel per thread, dwords; the others need C0 % 4 == 0 and bit 0 and give a thread 4
+ *                   consecutive output channels, 16-byte loads of F and dO and 16-byte stores - 1: depthwise with multiplier 1, the four inputs are ONE
+ *                   16-byte load of I per tap; 2: Cg0 % 4 == 0, the four channels lie in one group and share one dword of I per (cg, tap); 3: depthwise
+ *                   with another multiplier, four dwords of I per tap,
+ *         channels of a dX thread (4: load path 1, 16-byte loads of dO and F; 1 otherwise),
+ *         channel lanes of a dF workgroup (a power of two up to 32; its other 256 / lanes rows are K tap rows x pixel sub-slices),
+ *         pixel sub-slices of a dF workgroup ((256 / lanes) / K, added through LDS in ascending order),
+ *         dF slices (pixel slices of whole 32-pixel stages aiming at 1024 workgroups over Cg1 x channel tiles, shrunk until the slabs fit 8 MiB of
+ *                    workspace - down to one, which may take the 32 MiB),
+ *         the fold behind them (1: k_fold_add - up to 32 slices and DB right behind DF; 2: k_conv_df_fold),
+ *         launches of a whole backward (3) }. */
+int t4k_conv2d_grp_plan(int N, int H1, int W1, int C1, int C0, int K, int S, int P, int D, int G,
                         int aligned, int out[8]);
 /* Transposed convolution layer (word `dconv2d`, L_DCONV; allocation Model::_iconv txn model.cpp:121-180, dispatch forward.cu:110 /
  * backprop.cu:137 - the reference routes the layer's forward through the conv backward routine and vice versa but never finished it, see

@@ -31,6 +31,7 @@ Model &Model::add(int fn, uint32_t n, DU bias, uint16_t *opt) {
         const uint16_t K = opt[0], S = opt[1];
         const uint16_t P = (K > 1 && opt[2]) ? opt[2] : (K - 1) / 2;
         uint16_t H0, W0, D = 0;
+        uint32_t G = 1;
         if (txn) { const uint16_t P0 = (H1 + P * 2 - K) % S; H0 = (H1 - 1) * S - P * 2 + K + P0; W0 = (W1 - 1) * S - P * 2 + K + P0; }
         else {
             // conv2d takes any K 1..7 with stride, padding and dilation (the reference: "TODO: dilation" model.cpp:125): a D cell of 0 means 1
@@ -41,6 +42,11 @@ Model &Model::add(int fn, uint32_t n, DU bias, uint16_t *opt) {
                 return *this;
             }
             H0 = (H1 - D * (K - 1) - 1 + P * 2) / S + 1; W0 = (H1 - D * (K - 1) - 1 + P * 2) / S + 1;      // W0 from H1: reference quirk :137
+            // the fifth cell cuts the channels into G groups (the reference has none): 0 or 1 = ungrouped, the filter is T4(C1 / G, K, K, C0)
+            if (opt[4] > 1) {
+                G = opt[4];
+                if (C1 % G || C0 % G) { hprintf("nn#iconv %s groups=%d? in=%d out=%d\n", LAYER_NAME[fn], G, C1, C0); return *this; }
+            }
         }
         if (txn && K != 4) {
             hprintf("nn#iconv %s f=[%d,%d]? 1x1, 3x3, 4x4, and 5x5 supported only.\n", LAYER_NAME[fn], K, K);
@@ -48,12 +54,12 @@ Model &Model::add(int fn, uint32_t n, DU bias, uint16_t *opt) {
         }
         in.stride[0] = in.stride[1] = S; in.stride[2] = in.stride[3] = P; in.xparm = bias;
         in.iparm = D;                                   // convolutions use iparm for nothing else; 1 (and the 0 of a transposed layer) = undilated
-        Tensor *f = in.grad[0] = &T4(C1, K, K, C0);
+        Tensor *f = in.grad[0] = &T4(C1 / G, K, K, C0);     // G is not stored: conv_G() reads it back from the filter
         Tensor *b = in.grad[1] = &VEC(C0);
-        in.grad[2] = &T4(C1, K, K, C0).zeros();
+        in.grad[2] = &T4(C1 / G, K, K, C0).zeros();
         in.grad[3] = &VEC(C0).zeros();
         in.grad[4] = &T4(N1, H1, W1, C1).zeros();
-        RAND(*f, sqrtf(6.0f / (K * K * C1))); RAND(*b, bias);
+        RAND(*f, sqrtf(6.0f / (K * K * (C1 / G)))); RAND(*b, bias);
         layer.push_back(&T4(N1, H0, W0, C0));
     } break;
     case T4K_L_LINEAR: {                                // _ilinear model.cpp:182-226
@@ -127,30 +133,45 @@ Model &Model::add(int fn, uint32_t n, DU bias, uint16_t *opt) {
 // fastest schedule - 0.26 ms/step vs 0.28 (hipGraph replay) vs 0.31 (forked side stream; every cross-queue event edge
 // costs more than the ~4.5 us in-order dispatch it hides).  What pays is fewer launches (fused kernels below).
 // ---- conv2d layers outside the reference's four geometries.  ONE predicate decides the route at every call site of the conv family:
-// such a layer runs t4k_conv2d_geo_fwd / _bwd and joins no fused group.  The two entries are referenced weakly: over a C-ABI without them (the CPU
-// oracle) the layer keeps the refusal at forward / backprop.
+// such a layer runs t4k_conv2d_geo_fwd / _bwd and joins no fused group.  So does a GROUPED layer of any geometry, on t4k_conv2d_grp_fwd /
+// _bwd: the same predicate keeps it out of every fused group, stack, conv + batch-norm epilogue and the lazy-dX0 stack path.  The entries are referenced
+// weakly: over a C-ABI without them (the CPU oracle) the layer keeps the refusal at forward / backprop.
 #pragma weak t4k_conv2d_geo_fwd
 #pragma weak t4k_conv2d_geo_bwd
+#pragma weak t4k_conv2d_grp_fwd
+#pragma weak t4k_conv2d_grp_bwd
 static int conv_D(const Tensor &in) { return in.iparm > 1 ? in.iparm : 1; }
+static int conv_G(const Tensor &in) { return (int)(in.shape[2] / in.grad[0]->N()); }     // the filter is T4(C1 / G, K, K, C0)
 static bool conv_geo(const Tensor &in) {
     if (in.grad_fn != T4K_L_CONV) return false;
     const int K = in.grad[0]->H(), S = in.stride[0], P = in.stride[2];
     const bool four = (K == 1 && S == 1 && P == 0) || (K == 3 && S == 1 && P == 1) || (K == 4 && S == 2 && P == 1) || (K == 5 && S == 1 && P == 2);
-    return !four || conv_D(in) > 1;
+    return !four || conv_D(in) > 1 || conv_G(in) > 1;
 }
-static void geo_refusal(const char *who, int K, int S, int P, int D) {      // the line the four-geometry entries leave through chk(), the dilation named where there is one
-    if (D > 1) hprintf("%s failed: %s kernel_size=%d stride=%d padding=%d dilation=%d not supported\n", who, who, K, S, P, D);
-    else       hprintf("%s failed: %s kernel_size=%d stride=%d padding=%d not supported\n", who, who, K, S, P);
+static void geo_refusal(const char *who, int K, int S, int P, int D, int G) {      // the line the four-geometry entries leave through chk(), the dilation and the groups named where there are any
+    char grp[24] = ""; if (G > 1) snprintf(grp, sizeof grp, " groups=%d", G);
+    if (D > 1) hprintf("%s failed: %s kernel_size=%d stride=%d padding=%d dilation=%d%s not supported\n", who, who, K, S, P, D, grp);
+    else       hprintf("%s failed: %s kernel_size=%d stride=%d padding=%d%s not supported\n", who, who, K, S, P, grp);
 }
 static int geo_fwd(Tensor &in, Tensor &out, const float *x, float *cp, t4k_stream_t s) {
-    const int K = in.grad[0]->H(), S = in.stride[0], P = in.stride[2];
-    if (!t4k_conv2d_geo_fwd) { geo_refusal("nn#fconv", K, S, P, conv_D(in)); return T4K_ERR_UNSUPPORTED; }
+    const int K = in.grad[0]->H(), S = in.stride[0], P = in.stride[2], G = conv_G(in);
+    if (G > 1) {
+        if (!t4k_conv2d_grp_fwd) { geo_refusal("nn#fconv", K, S, P, conv_D(in), G); return T4K_ERR_UNSUPPORTED; }
+        return chk(t4k_conv2d_grp_fwd(x, cp, out.data, in.grad[0]->data, in.grad[1]->data, out.N(), in.H(), in.W(), in.C(), out.H(), out.W(), out.C(),
+                                      K, S, P, conv_D(in), G, s), "nn#fconv");
+    }
+    if (!t4k_conv2d_geo_fwd) { geo_refusal("nn#fconv", K, S, P, conv_D(in), 1); return T4K_ERR_UNSUPPORTED; }
     return chk(t4k_conv2d_geo_fwd(x, cp, out.data, in.grad[0]->data, in.grad[1]->data, out.N(), in.H(), in.W(), in.C(), out.H(), out.W(), out.C(),
                                   K, S, P, conv_D(in), s), "nn#fconv");
 }
 static int geo_bwd(Tensor &in, Tensor &out, const float *dy, float *dx, float *dx2, const float *w, bool grads, int train, t4k_stream_t s) {
-    const int K = in.grad[0]->H(), S = in.stride[0], P = in.stride[2];
-    if (!t4k_conv2d_geo_bwd) { geo_refusal("nn#bconv", K, S, P, conv_D(in)); return T4K_ERR_UNSUPPORTED; }
+    const int K = in.grad[0]->H(), S = in.stride[0], P = in.stride[2], G = conv_G(in);
+    if (G > 1) {
+        if (!t4k_conv2d_grp_bwd) { geo_refusal("nn#bconv", K, S, P, conv_D(in), G); return T4K_ERR_UNSUPPORTED; }
+        return chk(t4k_conv2d_grp_bwd(in.data, dy, dx, dx2, w, grads ? in.grad[2]->data : nullptr, grads ? in.grad[3]->data : nullptr,
+                                      in.N(), in.H(), in.W(), in.C(), out.H(), out.W(), out.C(), K, S, P, conv_D(in), G, train, s), "nn#bconv");
+    }
+    if (!t4k_conv2d_geo_bwd) { geo_refusal("nn#bconv", K, S, P, conv_D(in), 1); return T4K_ERR_UNSUPPORTED; }
     return chk(t4k_conv2d_geo_bwd(in.data, dy, dx, dx2, w, grads ? in.grad[2]->data : nullptr, grads ? in.grad[3]->data : nullptr,
                                   in.N(), in.H(), in.W(), in.C(), out.H(), out.W(), out.C(), K, S, P, conv_D(in), train, s), "nn#bconv");
 }

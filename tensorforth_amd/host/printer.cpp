@@ -99,6 +99,7 @@ static std::string parm_s(Tensor &in, Tensor &out) {     // aio_model.cpp:103-14
     switch (fn) {
     case T4K_L_CONV: case T4K_L_DCONV: o << "bias=" << p << ", C=" << out.C() << ", K=" << in.grad[0]->H() << ", S=" << S << ", P=" << in.stride[2];
         if (fn == T4K_L_CONV && in.iparm > 1) o << ", D=" << in.iparm;      // a dilated layer says so; every other line is the reference's
+        if (fn == T4K_L_CONV && in.grad[0]->N() < in.C()) o << ", G=" << in.C() / in.grad[0]->N();      // ... and a grouped one: its filter is T4(C1 / G, K, K, C0)
         break;
     case T4K_L_LINEAR: o << "bias=" << p << ", H=" << in.grad[0]->H(); break;
     case T4K_L_SELU: case T4K_L_LEAKYRL: case T4K_L_ELU: o << "bias=" << p; break;

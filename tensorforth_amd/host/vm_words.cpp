@@ -502,11 +502,11 @@ void VM::nnop(int op) {
     }
 }
 void VM::conv(uint16_t k, bool txn, uint16_t s, uint16_t p, uint16_t d) {   // netvm.cpp:203-226
-    uint16_t opt[] = {k, s, p, d};
+    uint16_t opt[5] = {k, s, p, d, 0};                    // the fifth cell: groups (conv2d only)
     if (TOS1T()) {
         Tensor &t = TTOS();
         if (t.rank == 1) {
-            std::vector<float> vo; t.to_host(vo, std::min<uint64_t>(t.numel, 4));
+            std::vector<float> vo; t.to_host(vo, std::min<uint64_t>(t.numel, 5));
             DU x = POP(); DROP(x);
             for (size_t i = 0; i < vo.size(); i++) opt[i] = (uint16_t)(int)vo[i];
         } else { pstr("vec?"); return; }
