@@ -184,13 +184,24 @@ int t4k_reduce(int red_op, const float *src, long n, float avg, float *out_dev, 
  * T4K_ERR_ARG. */
 int t4k_reduce_axes(int red_op, const float *src, float *dst, const int dim[4], int mask,
                     const float *center, t4k_stream_t s);
+/* The plan t4k_reduce_axes takes for (dim, mask) when src is (aligned != 0) or is not 16-byte aligned; launches nothing.  ws_bytes > 0
+ * plans for a workspace of that size and needs no device and no t4k_init; ws_bytes == 0 means the initialised library's own workspace
+ * (T4K_ERR_NODEVICE before t4k_init); ws_bytes < 0 or NULL out: T4K_ERR_ARG, and dim / mask as t4k_reduce_axes.
+ * out = { family (0 row: innermost group reduced, 1 column), launches, float4 path (0 / 1),
+ *         row: log2 of the lanes of a group | column: log2 of a tile's lanes,
+ *         row: log2 of the lanes side by side along a run | column: tiles along the kept extent,
+ *         parts per group, the extent dealt to the parts (0 none; 1 the units of a run (row) or the rows (column); 2 the outer reduced
+ *         extent), passes of the grid-stride loop = ceil(work items / 2048) }.
+ * With two launches this is the first; the second is the same planner applied to the partials (S floats behind each output). */
+int t4k_reduce_axes_plan(const int dim[4], int mask, int aligned, long ws_bytes, int out[8]);
 /* Softmax along any subset of the axes: for every index of the unmasked axes the elements along the masked axes form one group,
  * x <- exp(x - max_group) / sum_group exp(x - max_group).  No reference definition: the reference's only softmax forms are the layer's
  * rows (_fsoftmax forward.cu:222-243, t4k_softmax below) and the whole-tensor word (netvm.cpp:36-39).
  *   src and dst are dense NHWC of extents dim = {N,H,W,C}; mask adds N = 8, H = 4, W = 2, C = 1 for the axes of a group.  dst == src is
  *   allowed (in place).  A masked axis of extent 1 has no effect; a group of one element becomes 1.
- * Arithmetic as t4k_softmax: max shift, __expf, fp32 sum, one fp32 division per element.  Inputs are finite; the result for +-inf or
- * NaN inputs is unspecified.
+ * Arithmetic as t4k_softmax: max shift, __expf, fp32 sum, one fp32 division per element.  Inputs are finite, with one exception: -inf is
+ * admitted where the group keeps a finite element (the masking idiom) - such an element becomes exactly +0 in every regime and takes no
+ * part in the others' values.  The result for +inf, NaN or a group of nothing but -inf is unspecified.
  * One launch while a lane's share of a group fits its registers, or as two passes over the source inside one launch (a running
  * (max, sum) pair, rescaled when the max moves); for few groups behind long reductions three launches: parts of a group leave pairs in
  * the stream's workspace, a merge folds them in index order, a last launch normalises.  No allocation, no synchronisation, no read-back,
@@ -203,6 +214,9 @@ int t4k_softmax_axes(const float *src, float *dst, const int dim[4], int mask, t
  *         float4 path (0 / 1), log2 of the lanes of a group (row) or of a tile's lanes (column), parts per group,
  *         rescales of the running sum on an element's way into its group's sum (0 in regime 0) }. */
 int t4k_softmax_axes_plan(const int dim[4], int mask, int aligned, int out[6]);
+/* The launch geometry behind that plan: out[8] and ws_bytes as t4k_reduce_axes_plan (launches 1 or 3; the parts' launch and the
+ * normalising launch share the geometry). */
+int t4k_softmax_axes_geometry(const int dim[4], int mask, int aligned, long ws_bytes, int out[8]);
 /* k_nan_inf :278 / Tensor::has_nan tensor.cu:326-333: count of NaN/Inf -> *cnt_dev (int) */
 int t4k_nan_inf(const float *src, long n, int *cnt_dev, t4k_stream_t s);
 /* k_copy :134 */

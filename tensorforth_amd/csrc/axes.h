@@ -128,6 +128,28 @@ inline bool col_split(ColPlan &p, long floats_per_group, long parts_reserved, lo
     return true;
 }
 
+// ---- host: what t4k_reduce_axes_plan and t4k_softmax_axes_geometry report
+
+// the workspace a plan entry plans for, in floats: ws_bytes > 0 as given (no device, no t4k_init), 0 the initialised library's own
+inline int plan_workspace(long ws_bytes, const char *who, long *ws_floats) {
+    if (ws_bytes < 0) return fail(T4K_ERR_ARG, "%s: ws_bytes %ld", who, ws_bytes);
+    if (ws_bytes == 0) {
+        if (!st().ready) return fail(T4K_ERR_NODEVICE, "%s: ws_bytes 0 asks for the library's workspace: t4k_init not called or no gfx950 device", who);
+        ws_bytes = (long)st().ws_bytes;
+    }
+    *ws_floats = ws_bytes / (long)sizeof(float);
+    return T4K_OK;
+}
+// out = { family, launches, float4 path, shift | sx, su | ntile, parts, split extent (0 none, 1 U | r0, 2 r1), trips of the grid-stride loop }
+inline void report_plan(int out[8], const RowPlan &p, bool vec, int launches) {
+    out[0] = 0; out[1] = launches; out[2] = vec ? 1 : 0; out[3] = (int)p.shift; out[4] = (int)p.su; out[5] = (int)p.S;
+    out[6] = p.S > 1 ? (p.split_u ? 1 : 2) : 0; out[7] = (int)ceil_div(p.nitem, (long)MAX_WG);
+}
+inline void report_plan(int out[8], const ColPlan &p, bool vec, int launches) {
+    out[0] = 1; out[1] = launches; out[2] = vec ? 1 : 0; out[3] = (int)p.sx; out[4] = (int)p.ntile; out[5] = (int)p.S;
+    out[6] = p.S > 1 ? (p.split_r1 ? 2 : 1) : 0; out[7] = (int)ceil_div(p.nitem, (long)MAX_WG);
+}
+
 // ---- device
 
 // one step of a lane's walk over its units, two counters and no division: `in` goes on by in_step, at in_end back to the lane's first (in0)

@@ -146,14 +146,25 @@ void launch(int op, bool vec, const float *X, const float *Cn, float *O, const P
     }, vec); });
 }
 
+// the plan of one launch, for the launcher and for t4k_reduce_axes_plan: one float per part in a workspace of ws_floats, nothing reserved;
+// true when the groups are split and a second launch folds the partials
+bool plan_row(RowPlan &p, const Merged &m, bool vec, bool may_split, long ws_floats) {
+    row_geometry(p, m, vec);
+    p.shift = row_lanes(p.U * p.r1, LANE_UNITS, p.nout);
+    const bool split = may_split && p.shift == 8 && row_split(p, 1, 0, ws_floats);
+    p.su = std::min(p.shift, log2_ceil(split && p.split_u ? p.per : p.U, 8));
+    p.nitem = ceil_div(p.nout, BLK >> p.shift) * p.S;
+    return split;
+}
+bool plan_col(ColPlan &p, const Merged &m, bool vec, bool may_split, long ws_floats) {
+    col_geometry(p, m, vec);
+    return may_split && col_split(p, 1, 0, ws_floats);
+}
+
 void launch_row(int op, const float *X, const float *Cn, float *O, const Merged &m, bool may_split, hipStream_t hs) {
     const bool vec = (m.r0 & 3) == 0 && aligned16(X);
     RowPlan p;
-    row_geometry(p, m, vec);
-    p.shift = row_lanes(p.U * p.r1, LANE_UNITS, p.nout);
-    const bool split = may_split && p.shift == 8 && row_split(p, 1, 0, (long)(st().ws_bytes / sizeof(float)));
-    p.su = std::min(p.shift, log2_ceil(split && p.split_u ? p.per : p.U, 8));
-    p.nitem = ceil_div(p.nout, BLK >> p.shift) * p.S;
+    const bool split = plan_row(p, m, vec, may_split, (long)(st().ws_bytes / sizeof(float)));
     float *dst = split ? ws_for(hs) : O;
     launch(op, vec, X, Cn, dst, p, hs);
     if (split) launch_row(fold_op(op), dst, nullptr, O, Merged{false, false, (long)p.S, p.nout, 1, 1}, false, hs);   // a row of S partials per output
@@ -162,8 +173,7 @@ void launch_row(int op, const float *X, const float *Cn, float *O, const Merged 
 void launch_col(int op, const float *X, const float *Cn, float *O, const Merged &m, bool may_split, hipStream_t hs) {
     const bool vec = (m.k0 & 3) == 0 && aligned16(X);
     ColPlan p;
-    col_geometry(p, m, vec);
-    const bool split = may_split && col_split(p, 1, 0, (long)(st().ws_bytes / sizeof(float)));
+    const bool split = plan_col(p, m, vec, may_split, (long)(st().ws_bytes / sizeof(float)));
     float *dst = split ? ws_for(hs) : O;
     launch(op, vec, X, Cn, dst, p, hs);
     if (split) launch_col(fold_op(op), dst, nullptr, O, Merged{true, false, (long)p.S, p.nout, 1, 1}, false, hs);   // column sums of the [S, nout] partials
@@ -188,6 +198,18 @@ int t4k_reduce_axes(int red_op, const float *src, float *dst, const int dim[4], 
     if (m.col) launch_col(op, src, cn, dst, m, true, S(s));
     else       launch_row(op, src, cn, dst, m, true, S(s));
     T4K_LAUNCH_CHECK(); return T4K_OK;
+}
+
+int t4k_reduce_axes_plan(const int dim[4], int mask, int aligned, long ws_bytes, int out[8]) {
+    if (!out) return fail(T4K_ERR_ARG, "t4k_reduce_axes_plan: null");
+    long total, ws_floats; Merged m;
+    int rc = check_axes(dim, mask, "t4k_reduce_axes_plan", &total); if (rc != T4K_OK) return rc;
+    rc = plan_workspace(ws_bytes, "t4k_reduce_axes_plan", &ws_floats); if (rc != T4K_OK) return rc;
+    rc = merge_axes(dim, mask, "t4k_reduce_axes_plan", m); if (rc != T4K_OK) return rc;
+    const bool vec = aligned != 0 && ((m.col ? m.k0 : m.r0) & 3) == 0;
+    if (m.col) { ColPlan p; const bool split = plan_col(p, m, vec, true, ws_floats); report_plan(out, p, vec, split ? 2 : 1); }
+    else       { RowPlan p; const bool split = plan_row(p, m, vec, true, ws_floats); report_plan(out, p, vec, split ? 2 : 1); }
+    return T4K_OK;
 }
 
 } // extern "C"

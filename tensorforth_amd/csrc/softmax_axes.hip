@@ -368,10 +368,9 @@ void plan_col(Plan &P, const Merged &m, long ws_floats) {
     P.chunks = (int)ceil_div(n, NV);
 }
 
-int make_plan(Plan &P, const int dim[4], int mask, bool aligned, const char *who) {
+int make_plan(Plan &P, const int dim[4], int mask, bool aligned, long ws_floats, const char *who) {
     Merged m;
     const int rc = merge_axes(dim, mask, who, m); if (rc != T4K_OK) return rc;
-    const long ws_floats = (long)(st().ws_bytes / sizeof(float));
     P.col = m.col;
     P.vec = aligned && ((m.col ? m.k0 : m.r0) & 3) == 0;                     // every row starts on a multiple of k0 elements, every run on one of r0
     if (m.col) plan_col(P, m, ws_floats); else plan_row(P, m, ws_floats);
@@ -408,7 +407,7 @@ int t4k_softmax_axes(const float *src, float *dst, const int dim[4], int mask, t
     long total; Plan P;
     int rc = check_axes(dim, mask, "t4k_softmax_axes", &total); if (rc != T4K_OK) return rc;
     if (src != dst && src < dst + total && dst < src + total) return fail(T4K_ERR_ARG, "t4k_softmax_axes: dst overlaps src");
-    rc = make_plan(P, dim, mask, aligned16(src) && aligned16(dst), "t4k_softmax_axes"); if (rc != T4K_OK) return rc;
+    rc = make_plan(P, dim, mask, aligned16(src) && aligned16(dst), (long)(st().ws_bytes / sizeof(float)), "t4k_softmax_axes"); if (rc != T4K_OK) return rc;
     if (P.col) run(P, P.cl, P.cl.nout, 1, P.cl.nout, src, dst, S(s));        // pairs laid out [S, groups]
     else       run(P, P.row, P.row.nout, (long)P.row.S, 1, src, dst, S(s));  // a row of S pairs per group
     T4K_LAUNCH_CHECK(); return T4K_OK;
@@ -419,11 +418,22 @@ int t4k_softmax_axes_plan(const int dim[4], int mask, int aligned, int out[6]) {
     if (!out) return fail(T4K_ERR_ARG, "t4k_softmax_axes_plan: null");
     long total; Plan P;
     int rc = check_axes(dim, mask, "t4k_softmax_axes_plan", &total); if (rc != T4K_OK) return rc;
-    rc = make_plan(P, dim, mask, aligned != 0, "t4k_softmax_axes_plan"); if (rc != T4K_OK) return rc;
+    rc = make_plan(P, dim, mask, aligned != 0, (long)(st().ws_bytes / sizeof(float)), "t4k_softmax_axes_plan"); if (rc != T4K_OK) return rc;
     out[0] = P.col ? 1 : 0; out[1] = P.regime; out[2] = P.vec ? 1 : 0;
     out[3] = P.col ? (int)P.cl.sx : (int)P.row.shift;
     out[4] = P.col ? (int)P.cl.S : (int)P.row.S;
     out[5] = P.regime == 0 ? 0 : P.chunks + 1 + (P.regime == 2 ? 1 : 0);     // rescales on an element's way into the sum: the lane's chunks, lane -> group, part -> whole
+    return T4K_OK;
+}
+
+int t4k_softmax_axes_geometry(const int dim[4], int mask, int aligned, long ws_bytes, int out[8]) {
+    if (!out) return fail(T4K_ERR_ARG, "t4k_softmax_axes_geometry: null");
+    long total, ws_floats; Plan P;
+    int rc = check_axes(dim, mask, "t4k_softmax_axes_geometry", &total); if (rc != T4K_OK) return rc;
+    rc = plan_workspace(ws_bytes, "t4k_softmax_axes_geometry", &ws_floats); if (rc != T4K_OK) return rc;
+    rc = make_plan(P, dim, mask, aligned != 0, ws_floats, "t4k_softmax_axes_geometry"); if (rc != T4K_OK) return rc;
+    const int launches = P.regime == 2 ? 3 : 1;
+    if (P.col) report_plan(out, P.cl, P.vec, launches); else report_plan(out, P.row, P.vec, launches);
     return T4K_OK;
 }
 
