@@ -225,7 +225,8 @@ int t4k_copy(const float *src, float *dst, long n, t4k_stream_t s);
 int t4k_transpose(const float *src, float *dst, int H, int W, int C, t4k_stream_t s);
 /* k_identity :160 (one sample) */
 int t4k_identity(float *dst, int H, int W, int C, t4k_stream_t s);
-/* k_math :173 in-place unary / scalar op (LN/LOG clamp 1e-12, SQRT clamp 0, GFILL = v*j/n) */
+/* k_math :173 in-place unary / scalar op (LN/LOG clamp 1e-12, SQRT clamp 0, GFILL = v*j/n).  The clamps are fmaxf / fminf, which return
+ * their other operand for a NaN: LN / LOG of NaN give the clamp's log (ln 1e-12, log10 1e-12); SQRT, RELU and SAT of NaN give 0. */
 int t4k_math(int op, float *A, float v, long n, t4k_stream_t s);
 /* k_ts_op :206  O = A op v,  op in {ADD,SUB,MUL,DIV} */
 int t4k_ts_op(int op, const float *A, float v, float *O, long n, t4k_stream_t s);

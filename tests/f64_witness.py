@@ -46,12 +46,18 @@ def bound_of(exact, mag, n, c=C_SUM):
 
 
 def ratio(got, w):
-    """worst |got - exact| / bound over the tensor (inf where an exact-only witness differs), its flat index"""
+    """worst |got - exact| / bound over the tensor (inf where an exact-only witness differs), its flat index.  Where the witness itself is
+    not finite (the math-op domain, `math` below) no bound applies: an exact NaN asks for a NaN, an exact infinity for that infinity; a NaN
+    anywhere else is inf as before."""
     got = np.asarray(got, np.float64).reshape(w.exact.shape)
-    err = np.abs(got - w.exact)
-    b = np.broadcast_to(w.bound(), err.shape)
-    r = np.where(b > 0, err / np.where(b > 0, b, 1.0), np.where(err > 0, np.inf, 0.0))
+    with np.errstate(invalid="ignore"):
+        err = np.abs(got - w.exact)
+        b = np.broadcast_to(w.bound(), err.shape)
+        r = np.where(b > 0, err / np.where(b > 0, b, 1.0), np.where(err > 0, np.inf, 0.0))
     r = np.where(np.isnan(got), np.inf, r)
+    special = ~np.isfinite(w.exact)
+    if special.any():
+        r = np.where(special, np.where((np.isnan(w.exact) & np.isnan(got)) | (got == w.exact), 0.0, np.inf), r)
     i = int(np.argmax(r)) if r.size else 0
     return (float(r.flat[i]) if r.size else 0.0), i
 
@@ -290,7 +296,14 @@ def mul(g, m):
 MEASURED_LOG = 3.137    # MI355X: t4k_math LN 3.137, single BCE terms 2.234 (tests/test_gpu_small_kernels_sweep.py::test_device_log_error_is_inside_the_allowance prints both)
 ULP_LOG = 6.3           # 2 x 3.137, rounded up
 ULP_LOG_LIBM = 2.0
-EPS = float(np.float32(1.0e-6))                                    # DU_EPS as the kernels hold it
+# t4k_math POW / SIN / COS (powf, sinf, cosf of the device library): no figure in the project or the guides either, so MEASURED the same way -
+# worst |got - exact| / (2^-24 |exact|) against float64 over the tables of small_kernel_cases.MATH_DOMAIN on the MI355X
+# (tests/test_gpu_math_domain.py prints them) - and the allowance is twice the measurement, rounded up to one decimal (twice: the tables
+# sample the domain, and a point release of the device library may move a last ulp).  The same constants hold libm and NumPy's float32
+# loops on the CPU (tests/test_f64_witness.py: libm powf 0.990, NumPy power 1.730, sin 1.800, cos 1.781 on the same tables).
+MEASURED_POW, MEASURED_SIN, MEASURED_COS = 2.19023, 1.80014, 2.29681     # MI355X: at (-2.0427191)^2, sin 3.1100991, cos 81126.922
+ULP_POW, ULP_SIN, ULP_COS = 4.4, 3.7, 4.6                                # 2 x each, rounded up to one decimal
+EPS =float(np.float32(1.0e-6))                                    # DU_EPS as the kernels hold it
 
 
 def is_int_exact(n, max_term):
@@ -549,3 +562,90 @@ def logdet(LU):
 
 def lu_extract(LU, get_u):
     L, Uu = split_lu(LU); return W(Uu if get_u else L, 0.0, 0)
+
+
+# ----------------------------------------------------------------------------- t4k_math (k_math<OP>): every op over its whole domain
+FLT_MAX = float(np.finfo(np.float32).max)
+LNX = np.float32(1.0e-12)                                        # DU_LNX as the kernel holds it: the clamp of LN / LOG
+MATH_EXACT = ("ABS", "NEG", "RELU", "SAT", "FILL", "SCALE", "ADD", "SUB", "MUL", "DIV", "SQRT", "RCP")   # single IEEE operations
+MATH_OPS = MATH_EXACT + ("GFILL", "EXP", "LN", "LOG", "TANH", "SIGM", "POW", "SIN", "COS")
+GAP = (0.99, 1.01)                                               # x FLT_MAX: no table holds an element whose exact value lies in here
+
+
+def _math_single(op, x, v):
+    """the single IEEE operation `op` in the dtype of x (float32: the expected bits; float64: the value before rounding).  fmax / fmin
+    return their other operand for a NaN, as fmaxf / fminf do: the guards of RELU, SAT and SQRT turn a NaN into 0."""
+    zero, one = x.dtype.type(0), x.dtype.type(1)
+    if op == "ABS": return np.abs(x)
+    if op == "NEG": return -x
+    if op == "RELU": return np.fmax(zero, x)
+    if op == "SAT": return np.fmin(one, np.fmax(zero, x))
+    if op == "FILL": return np.full_like(x, v)
+    if op in ("SCALE", "MUL"): return x * v
+    if op == "ADD": return x + v
+    if op == "SUB": return x - v
+    if op == "DIV": return x / v
+    if op == "SQRT": return np.sqrt(np.fmax(x, zero))
+    if op == "RCP": return one / x
+    raise ValueError(op)
+
+
+def math(op, x, v=0.0, n_total=None, j0=0):
+    """witness of t4k_math(op, x, v) on the fp32 operands x (GFILL / FILL read only its shape; GFILL: element i is index j0 + i of n_total).
+      single IEEE operations and GFILL (two of them on the rounded conversions of j and n): n = 0, the same expression in NumPy float32 -
+        subnormal operands and results included; the expected bits are `.f32`
+      EXP  ULP_EXP + 2|x| ulps of e^x;  SIGM  two more (the sum and the quotient);  TANH  4 ulps: `act`'s figures
+      LN / LOG  ULP_LOG ulps of |ln c|, |log10 c| with c = fmaxf(x, 1e-12) - the clamp is part of the witness (a NaN takes it too) - and
+        c = 1 gives exactly 0
+      POW / SIN / COS  ULP_POW / ULP_SIN / ULP_COS ulps of |exact|; POW follows C powf: a negative base is signed under an integral
+        exponent and NaN under a fractional one, 0^0 = 1
+    One overflow rule: where |exact| > FLT_MAX the result must be the infinity of that sign (no table holds an element within GAP of
+    FLT_MAX, where an honest rounding could go either way - tests/test_f64_witness.py asserts it on `.true`, the float64 value before any
+    rounding).  Results below FLT_MIN may flush: the n 2^-126 term.  |x| in the exp terms is capped at 128, past every saturation."""
+    x32 = np.ascontiguousarray(x, np.float32); v32 = np.float32(v); xd = x32.astype(np.float64); vd = float(v32)
+    with np.errstate(all="ignore"):
+        if op == "GFILL":
+            n = x32.size if n_total is None else int(n_total)
+            j = (j0 + np.arange(x32.size, dtype=np.int64)).astype(np.float32).reshape(x32.shape)
+            r = v32 * j / np.float32(n)
+            w = W(r.astype(np.float64), 0.0, 0, 1.0); w.f32 = r; w.true = w.exact
+            return w
+        if op in MATH_EXACT:
+            r = _math_single(op, x32, v32); assert r.dtype == np.float32
+            w = W(r.astype(np.float64), 0.0, 0, 1.0); w.f32 = r; w.true = _math_single(op, xd, vd)
+            return w
+        ax = np.minimum(np.nan_to_num(np.abs(xd), nan=0.0), 128.0)
+        if op == "EXP":
+            t = np.exp(xd); n = ULP_EXP + 2.0 * ax
+        elif op in ("LN", "LOG"):
+            c = np.fmax(x32, LNX).astype(np.float64)
+            t = np.log(c) if op == "LN" else np.log10(c); n = np.where(c == 1.0, 0.0, ULP_LOG)
+        elif op == "TANH":
+            t = np.tanh(xd); n = ULP_EXP
+        elif op == "SIGM":
+            t = 1.0 / (1.0 + np.exp(-xd)); n = ULP_EXP + 2.0 * ax + 2.0
+        elif op == "POW":
+            t = np.power(xd, vd); n = ULP_POW
+        elif op == "SIN":
+            t = np.sin(xd); n = ULP_SIN
+        elif op == "COS":
+            t = np.cos(xd); n = ULP_COS
+        else:
+            raise ValueError(op)
+        over = np.abs(t) > FLT_MAX
+        w = W(np.where(over, np.copysign(np.inf, t), t), np.where(over | np.isnan(t), 0.0, np.abs(t)), n, 1.0)
+    w.true = t
+    return w
+
+
+def in_gap(w):
+    """the elements of a `math` witness whose value before rounding lies within GAP of FLT_MAX"""
+    a = np.abs(w.true)
+    return (a >= GAP[0] * FLT_MAX) & (a <= GAP[1] * FLT_MAX)
+
+
+def kinds(a):
+    """0 finite, 1 NaN, 2 +inf, 3 -inf: what two implementations must agree on before their finite values are held to a witness (zeros are
+    finite, of either sign)"""
+    a = np.asarray(a, np.float64)
+    return np.where(np.isnan(a), 1, np.where(a == np.inf, 2, np.where(a == -np.inf, 3, 0)))

@@ -166,3 +166,103 @@ POOL_WRAP_CASES = ((3, 75, 75, 123, 2), (3, 113, 113, 123, 3))       # 3 x 38 x 
 RUN_TENSORS = ("X", "pre_mask", "pre_out", "pool_out", "post_mask", "post_out", "copy_out")
 RUN_MISALIGNED = tuple(("misaligned_%s" % t, t, off, vw) for t in RUN_TENSORS for off, vw in ((4, 1), (8, 2))) + \
     tuple(("misaligned_%s" % t, t, off, 1) for t in ("DY", "XH", "O") for off in (4, 8))      # the second step drops to scalar, never to 2
+
+
+# ----------------------------------------------------------------------------- t4k_math over its whole domain (tests/test_gpu_math_domain.py)
+F32_MAX = np.finfo(np.float32).max
+F32_MIN = np.finfo(np.float32).tiny                     # the smallest normal
+SUB_MAX = np.nextafter(F32_MIN, np.float32(0))          # the largest subnormal
+SUB_MIN = np.float32(1.4e-45)                           # the smallest
+MATH_N = 8191                                           # n % 4 == 3: the last three elements are k_math's scalar tail behind 2047 float4s
+MATH_SPECIALS = np.array([np.nan, np.inf, -np.inf, 0.0, -0.0, SUB_MIN, SUB_MAX, F32_MIN, F32_MAX, -F32_MAX, 1.0, -1.0], np.float32)
+MATH_SPECIALS_ROW = np.concatenate([MATH_SPECIALS, MATH_SPECIALS[:3]])          # 15 = 3 float4s and a tail of NaN, +inf, -inf
+MATH_V = (1.5, -0.0, 2.0 ** -100)                       # the scalar operand of FILL / SCALE / ADD / SUB / MUL / DIV
+POW_V = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 7.0, -1.0, -2.5)
+POW_NEG_V, POW_ZERO_V = (2.0, 3.0, -1.0, 0.5), (0.0, 2.0, -1.0)   # exponents that also meet negative bases (sign; 0.5: NaN) / a zero base
+GFILL_CASES = ((1, 1.5), (3, 1.5), (1025, 1.5), (2 ** 24 - 1, 1.5), (2 ** 24 + 7, 1.5), (1025, -0.3))   # (n, v): float(j) repeats past 2^24
+ACT_DOMAIN_KINDS = (("relu", 0.0), ("tanh", 0.0), ("sigmoid", 0.0), ("selu", 0.0), ("leaky", 0.01), ("elu", 1.0))
+
+
+def _f32(*v):
+    return np.array(v, np.float32)
+
+
+def _uni(lo, hi):
+    return lambda rng, k: rng.uniform(lo, hi, k)
+
+
+def _logu(lo, hi, signed=False):
+    """10^uniform(log10 lo, log10 hi), with a random sign if asked"""
+    return lambda rng, k: 10.0 ** rng.uniform(np.log10(lo), np.log10(hi), k) * (rng.choice((-1.0, 1.0), k) if signed else 1.0)
+
+
+def _table(seed, edges, tail, *parts, true=None):
+    """MATH_N fp32 values: the edge values first (in the float4 body), the random parts in equal shares, three of the edges again as the last
+    three elements (the scalar tail).  `true` = the op in float64: an element whose exact result lies within 1 % of FLT_MAX, where an honest
+    rounding may or may not overflow, is replaced by 1."""
+    rng = np.random.default_rng(seed); edges = np.asarray(edges, np.float32); tail = np.asarray(tail, np.float32)
+    assert tail.size == 3 and all(np.any((edges == t) | (np.isnan(edges) & np.isnan(t))) for t in tail), "the tail repeats edge values"
+    fill = MATH_N - 3 - edges.size; share = [fill // len(parts)] * len(parts); share[-1] += fill - sum(share)
+    x = np.concatenate([edges] + [np.asarray(f(rng, k)) for f, k in zip(parts, share)] + [tail]).astype(np.float32)
+    if true is not None:
+        with np.errstate(all="ignore"):
+            t = np.abs(true(x.astype(np.float64)))
+        x[(t >= 0.98 * float(F32_MAX)) & (t <= 1.02 * float(F32_MAX))] = 1.0
+    assert x.size == MATH_N and MATH_N % 4 == 3
+    return x
+
+
+class MathCase:
+    """one table: op name, scalar operand v, operands x (GFILL: None, n elements are generated by the op itself)"""
+
+    def __init__(self, op, v, x, n=None, tag=""):
+        self.op, self.v, self.x, self.n = op, float(v), x, (x.size if n is None else n)
+        self.id = op + (tag and "-" + tag)
+
+
+def _math_domain():
+    cases = []
+    cases.append(MathCase("EXP", 0.0, _table(80, _f32(-104, -103.97, -87.4, -87.3, -1e-30, 0, 1e-30, 88.5, 89, 100, 3e38), _f32(-87.4, 88.5, 100),
+                                             _uni(-104.0, 88.5))))
+    ln_edges = _f32(np.nextafter(np.float32(1), np.float32(2)), np.nextafter(np.float32(1), np.float32(0)), 1, 1e-12,
+                    np.nextafter(np.float32(1e-12), np.float32(1)), np.nextafter(np.float32(1e-12), np.float32(0)), F32_MAX,
+                    1e-20, 1e-40, 0.0, -0.0, -1, -F32_MAX)
+    for k, op in enumerate(("LN", "LOG")):
+        cases.append(MathCase(op, 0.0, _table(81 + k, ln_edges, ln_edges[[1, 5, 11]], _logu(1e-12, 3e38), lambda rng, n: 1.0 + rng.uniform(-1e-3, 1e-3, n))))
+    cases.append(MathCase("TANH", 0.0, _table(83, _f32(9.01, -9.01, 20, -20, 0.0, -0.0), _f32(-9.01, 20, -0.0), _uni(-12.0, 12.0), _logu(1e-38, 1e-2, True))))
+    cases.append(MathCase("SIGM", 0.0, _table(84, _f32(88.7, -88.7, 89, -89), _f32(-88.7, 89, -89), _uni(-104.0, 104.0))))
+    cases.append(MathCase("SQRT", 0.0, _table(85, _f32(-0.0, -F32_MAX, 0.0, SUB_MIN, SUB_MAX, F32_MIN, F32_MAX, -1, -1e-40), _f32(-0.0, -F32_MAX, SUB_MIN),
+                                              _logu(1e-45, 3e38), _logu(1e-45, 3e38), _logu(1e-45, 3e38), lambda rng, n: -_logu(1e-45, 3e38)(rng, n))))
+    cases.append(MathCase("RCP", 0.0, _table(86, _f32(0.0, -0.0, SUB_MIN, -SUB_MAX, F32_MAX, -3e38, 1, -1), _f32(0.0, -0.0, SUB_MIN),
+                                             _logu(1e-45, 3e38, True), true=lambda x: 1.0 / x)))
+    # single IEEE operations: normal-scale values, subnormals, and magnitudes whose product / quotient with v goes subnormal or overflows
+    # (v = 1.5: 3e38 x 1.5 overflows, 1e-38 / 1.5 is subnormal; v = 2^-100: 1e-8 x v is subnormal, 1e9 / v overflows; v = -0: x / v = -+inf, 0 / v = NaN)
+    ew_edges = _f32(0.0, -0.0, SUB_MIN, -SUB_MIN, SUB_MAX, -SUB_MAX, F32_MIN, -F32_MIN, 3e38, -3e38, 1e-39, -1e-39, 1e-8, -1e-8, 1e9, -1e9, 1e-38, 1.5e-38,
+                    1, -1, 0.5, 2.5e38)
+    for k, op in enumerate(("ABS", "NEG", "RELU", "SAT")):
+        cases.append(MathCase(op, 0.0, _table(87 + k, ew_edges, _f32(-0.0, -SUB_MAX, 3e38), lambda rng, n: rng.standard_normal(n) * 3.0, _logu(1e-45, 3e38, True))))
+    for k, op in enumerate(("FILL", "SCALE", "ADD", "SUB", "MUL", "DIV")):
+        for q, v in enumerate(MATH_V):
+            vd = float(np.float32(v))
+            true = {"FILL": lambda x: x * 0 + vd, "ADD": lambda x: x + vd, "SUB": lambda x: x - vd, "DIV": lambda x: x / vd}.get(op, lambda x: x * vd)
+            cases.append(MathCase(op, v, _table(100 + 3 * k + q, ew_edges, _f32(-0.0, -SUB_MAX, 3e38), lambda rng, n: rng.standard_normal(n) * 3.0,
+                                                _logu(1e-45, 3e38, True), true=true), tag="v%g" % v))
+    # bases whose 7th power and whose -2.5th power overflow and underflow, in every table
+    pow_edges = _f32(1e-17, 1e-16, 2e-6, 5e5, 1e6, 1e16, 1e17, 1)
+    for q, v in enumerate(POW_V):
+        edges = np.concatenate([pow_edges, _f32(0.0) if v in POW_ZERO_V else _f32()])
+        parts = [_logu(1e-6, 1e6)] * (3 if v in POW_NEG_V else 1) + ([lambda rng, n: -_logu(1e-6, 1e6)(rng, n)] if v in POW_NEG_V else [])
+        cases.append(MathCase("POW", v, _table(120 + q, edges, _f32(1e-17, 1e17, 5e5), *parts, true=lambda x, v=v: np.power(x, v)), tag="v%g" % v))
+    # the fp32 neighbours of k pi / 2, k = 0 .. 8 (k = 0: 0 and the smallest subnormals)
+    hp = np.array([np.float32(k * np.pi / 2) for k in range(9)], np.float32)
+    near = np.concatenate([hp, np.nextafter(hp, np.float32(100)), np.nextafter(hp, np.float32(-100))])
+    for k, op in enumerate(("SIN", "COS")):
+        cases.append(MathCase(op, 0.0, _table(130 + k, near, near[[1, 2, 12]], _uni(-8.0, 8.0), _uni(-1e3, 1e3), _uni(-1e5, 1e5), _uni(-1e8, 1e8), _uni(-3e38, 3e38),
+                                              _logu(1e-38, 1e-3, True))))
+    for n, v in GFILL_CASES:
+        cases.append(MathCase("GFILL", v, None, n=n, tag="n%d-v%g" % (n, v)))
+    return tuple(cases)
+
+
+MATH_DOMAIN = _math_domain()
+ACT_DOMAIN = np.concatenate([np.linspace(-104.0, 104.0, MATH_N - 3).astype(np.float32), _f32(-104, 88.7, -0.0)])   # k_activate: the rows today stop near |x| = 15
