@@ -572,6 +572,26 @@ int t4k_upsample_fwd(int method, const float *I, float *O, int N, int H1, int W1
  * same bits on every run, every element of DX stored exactly once.  The forward input is not read: DX may be its buffer (the in-place convention of
  * t4k_pool_geo_bwd); DY must not overlap DX.  One launch; no allocation, no synchronisation. */
 int t4k_upsample_bwd(int method, const float *DY, float *DX, int N, int H1, int W1, int C, int H0, int W0, int K, t4k_stream_t s);
+/* group / layer / instance norm on NHWC fp32 (csrc/groupnorm.hip): torch.nn.functional.group_norm(x, G, W, B, eps) with 1 <= G <= C,
+ * C % G == 0, Cg = C / G, E = HW Cg; the group of channel c is c / Cg.  G = 1 is layer norm over (H, W, C) with a per-channel affine, G = C instance norm.
+ * The reference has no such layer.  mean and the BIASED variance are per (sample, group); the variance is a sum of squared deviations from the group's own
+ * computed mean (Chan's merge of (count, mean, M2) where a group is cut into parts), never E[x^2] - mean^2; rstd = 1 / sqrt(var + eps), eps INSIDE the root.
+ * Admission and the plan, on the host alone (no device needed; the entries call the same function).  An extent below 1, NULL out or ws_bytes < 0: T4K_ERR_ARG;
+ * G < 1, C % G != 0, N HW C or N G at or above 2^31, or partial slabs that do not fit ws_bytes: T4K_ERR_UNSUPPORTED; out is untouched then.
+ * out = { rung (1 wave, 2 workgroup, 3 stream, 4 split), load path (4 = 16 bytes per lane, 1 = dwords), groups per workgroup, parts per group,
+ *         forward launches, dW | dB slices, fold kind (1 fold_add, 2 df_fold), backward launches with train != 0 };
+ * aligned != 0: every pointer of the call on 16 bytes; the 16-byte path also needs Cg % 4 == 0 */
+int t4k_groupnorm_plan(int N, int HW, int C, int G, int aligned, long ws_bytes, int out[8]);
+/* the forward: XH = (I - mean) rstd, O = XH W[c] + B[c]; STAT (4 N G floats: mean | rstd | s1 | s2, each N G long) receives mean and rstd.
+ * O and XH are written once per element; O may be I.  eps <= 0 or a NULL tensor: T4K_ERR_ARG.  One launch (two on the split rung); no atomics, the same bits
+ * on every call; no allocation, no synchronisation.  A refusal leaves a t4k_last_error text and writes nothing. */
+int t4k_groupnorm_fwd(const float *I, float *O, float *XH, const float *W, const float *B, float *STAT,
+                      int N, int HW, int C, int G, float eps, t4k_stream_t s);
+/* its backward, the textbook one: t = W[c] DY, s1 = mean_g t, s2 = mean_g (t XH), DX = rstd (t - s1 - XH s2); STAT's rstd is read, its s1 | s2 written.
+ * train != 0: DW[c] += sum_{n,h,w} DY XH and DB[c] += sum DY (SUMS), through per-slice slab rows in the stream's workspace and a fold launch; train == 0
+ * leaves both untouched and both may be NULL.  DX is written once per element and may be DY. */
+int t4k_groupnorm_bwd(const float *W, const float *DY, const float *XH, float *STAT, float *DX,
+                      float *DW, float *DB, int N, int HW, int C, int G, int train, t4k_stream_t s);
 /* k_sgd nmath.cu:419: dg=DG/Nw; beta~0: G-=lr*dg else M=b*M+(1-b)*dg, G-=lr*M; DG=0 */
 int t4k_sgd(float *G, float *DG, float *M, int Nw, float lr, float beta, long n, t4k_stream_t s);
 /* k_adam nmath.cu:438 (no bias correction, eps outside sqrt): zeroes DG */

@@ -101,6 +101,20 @@ Model &Model::add(int fn, uint32_t n, DU bias, uint16_t *opt) {
     } break;
     case T4K_L_BATCHNM: {                               // _ibatchnorm model.cpp:276-292 (dW/dB zeroed here)
         const int C = in.C();
+        if (opt) {
+            // the vector form `vector{ G } batchnorm` is a group norm over G groups of C / G channels per sample (the reference has none):
+            // G = 1 layer norm, G = C instance norm.  gamma, beta, their gradients and xhat as for batchnorm; mtum[4] holds mean | rstd | s1 | s2 per (sample, group)
+            const int G = opt[0];
+            if (G < 1 || C % G) { hprintf("nn#ibatchnorm groups=%d? channels=%d\n", G, C); return *this; }
+            in.grad[0] = &VEC(C).map(T4K_FILL, 1.0f); in.grad[2] = &VEC(C).zeros();
+            in.grad[1] = &VEC(C).zeros();             in.grad[3] = &VEC(C).zeros();
+            in.grad[4] = &T4(in.N(), in.H(), in.W(), in.C());
+            in.mtum[4] = &VEC((uint64_t)4 * in.N() * G).zeros();
+            in.iparm = G;                               // batchnorm uses iparm for nothing: 0 stays the reference's layer, >= 1 marks this one
+            in.xparm = 0;
+            layer.push_back(&T4(in.N(), in.H(), in.W(), in.C()));
+            break;
+        }
         in.grad[0] = &VEC(C).map(T4K_FILL, 1.0f); in.grad[2] = &VEC(C).zeros();
         in.grad[1] = &VEC(C).zeros();             in.grad[3] = &VEC(C).zeros();
         in.grad[4] = &T4(in.N(), in.H(), in.W(), in.C());
@@ -212,6 +226,24 @@ static int up_geo_bwd(Tensor &in, Tensor &out, const float *dy, t4k_stream_t s) 
     const int K = in.stride[0];
     if (!t4k_upsample_bwd) { hprintf("nn#bupsample failed: nn#bupsample size=%d method=%d not supported\n", K, in.iparm); return T4K_ERR_UNSUPPORTED; }
     return chk(t4k_upsample_bwd(in.iparm, dy, in.data, in.N(), in.H(), in.W(), in.C(), out.H(), out.W(), K, s), "nn#bupsample");
+}
+// ---- group / layer / instance norm, `vector{ G } batchnorm`.  ONE predicate decides the route at every reader of T4K_L_BATCHNM: such a layer runs
+// t4k_groupnorm_fwd / _bwd, joins no conv + batch-norm epilogue, run, stack or block, has no running statistics and never exchanges across ranks
+// (dp_bn_mode does not concern it).  The entries are referenced weakly: over a C-ABI without them (the CPU oracle) the layer is admitted, shaped and
+// printed, and forward / backprop refuse it - there is no host-side fallback.
+#pragma weak t4k_groupnorm_fwd
+#pragma weak t4k_groupnorm_bwd
+static const float NORM_GRP_EPS = 1.0e-5f;
+bool norm_grp(const Tensor &in) { return in.grad_fn == T4K_L_BATCHNM && in.iparm >= 1; }
+static int norm_grp_fwd(Tensor &in, Tensor &out, const float *x, t4k_stream_t s) {
+    if (!t4k_groupnorm_fwd) { hprintf("nn#fbatchnorm failed: nn#fbatchnorm groups=%d not supported\n", in.iparm); return T4K_ERR_UNSUPPORTED; }
+    return chk(t4k_groupnorm_fwd(x, out.data, in.grad[4]->data, in.grad[0]->data, in.grad[1]->data, in.mtum[4]->data,
+                                 out.N(), out.H() * out.W(), out.C(), in.iparm, NORM_GRP_EPS, s), "nn#fbatchnorm");
+}
+static int norm_grp_bwd(Tensor &in, const float *dy, int train, t4k_stream_t s) {        // dX over x, as batchnorm leaves it
+    if (!t4k_groupnorm_bwd) { hprintf("nn#bbatchnorm failed: nn#bbatchnorm groups=%d not supported\n", in.iparm); return T4K_ERR_UNSUPPORTED; }
+    return chk(t4k_groupnorm_bwd(in.grad[0]->data, dy, in.grad[4]->data, in.mtum[4]->data, in.data, in.grad[2]->data, in.grad[3]->data,
+                                 in.N(), in.H() * in.W(), in.C(), in.iparm, train, s), "nn#bbatchnorm");
 }
 
 Model *Model::current = nullptr;
@@ -554,7 +586,7 @@ void Model::run_forward(Tensor &input) {
             t4k_stack_head hd;
             const bool head = stack && use_stack_head && j + 1 < L && lin_kind(j) == 1, rider = head && fill_stack_head(j, input, hd);
             const Run *r1 = (i + 2 < L && run_of_[i + 1] >= 0) ? &runs_[run_of_[i + 1]] : nullptr;       // the element-wise run behind the conv, behind conv + batch-norm
-            const Run *r2 = (i + 3 < L && out.grad_fn == T4K_L_BATCHNM && run_of_[i + 2] >= 0) ? &runs_[run_of_[i + 2]] : nullptr;
+            const Run *r2 = (i + 3 < L && out.grad_fn == T4K_L_BATCHNM && !norm_grp(out) && run_of_[i + 2] >= 0) ? &runs_[run_of_[i + 2]] : nullptr;
             float *F = in.grad[0]->data, *B = in.grad[1]->data;
             const int N = out.N(), H1 = in.H(), W1 = in.W(), C1 = in.C(), H0 = out.H(), W0 = out.W(), C0 = out.C(), K = in.grad[0]->H(), S = in.stride[0], P = in.stride[2];
             int last = -1;                              // the last op the launch covers
@@ -572,7 +604,7 @@ void Model::run_forward(Tensor &input) {
                 chk(t4k_conv2d_bn_block_fwd(x, cp, out.data, F, B, N, H1, W1, C1, H0, W0, C0, K, S, P, at(i + 2).data, out.grad[4]->data, out.grad[0]->data, out.grad[1]->data,
                                             out.mtum[4]->data, &r2->blk, r2->H0, r2->W0, stream()), "nn#fconv+batchnorm+run");
                 last = i + 1 + r2->count;
-            } else if (i + 2 < L && out.grad_fn == T4K_L_BATCHNM) {   // conv + batch-norm: the statistics ride in the conv's epilogue where its kernel carries them
+            } else if (i + 2 < L && out.grad_fn == T4K_L_BATCHNM && !norm_grp(out)) {   // conv + batch-norm: the statistics ride in the conv's epilogue where its kernel carries them
                 chk(t4k_conv2d_bn_fwd(x, cp, out.data, F, B, N, H1, W1, C1, H0, W0, C0, K, S, P, at(i + 2).data, out.grad[4]->data, out.grad[0]->data, out.grad[1]->data,
                                       out.mtum[4]->data, stream()), "nn#fconv+batchnorm");
                 last = i + 1;
@@ -621,6 +653,7 @@ const float *Model::fstep(Tensor &in, Tensor &out, const float *x) {
         if (pool_geo(in)) { pool_geo_fwd(in, out, x, s); break; }
         chk(t4k_pool(fn, x, out.data, out.N(), in.H(), in.W(), out.H(), out.W(), out.C(), in.stride[0], s), "nn#fpool"); break;
     case T4K_L_BATCHNM:
+        if (norm_grp(in)) { norm_grp_fwd(in, out, x, s); break; }
         chk(t4k_batchnorm_fwd(x, out.data, in.grad[4]->data, in.grad[0]->data, in.grad[1]->data, in.mtum[4]->data,
                               out.N(), out.H() * out.W(), out.C(), s), "nn#fbatchnorm"); break;
     case T4K_L_USAMPLE:                                 // nearest: broadcast each cell to a kxk tile
@@ -983,6 +1016,7 @@ Model::Back Model::bstep(int i, Tensor &in, Tensor &out, const float *dy, bool l
         if (pool_geo(in)) { pool_geo_bwd(in, out, dy, s); break; }
         chk(t4k_dpool(fn, in.data, dy, out.N(), in.H(), in.W(), out.H(), out.W(), out.C(), in.stride[0], s), "nn#bpool"); break;
     case T4K_L_BATCHNM:
+        if (norm_grp(in)) { norm_grp_bwd(in, dy, train, s); break; }
         chk(t4k_batchnorm_bwd(in.grad[0]->data, dy, in.grad[4]->data, in.data, in.grad[2]->data, in.grad[3]->data,
                               in.mtum[4]->data, in.N(), in.H() * in.W(), in.C(), train, s), "nn#bbatchnorm"); break;
     case T4K_L_USAMPLE:                                 // gradient of nearest upsampling = sum over the tile = k*k * avgpool
@@ -1164,7 +1198,7 @@ Model &Model::adamw(DU lr, DU wd, DU b1, DU b2) { return gradient("adamw", OPTI_
 
 // ---------------------------------------------------------------- persistence (.t4 model file, aio_model.cpp)
 // Layout written by the reference: a `\\ tensorForth v4.0 model` line, one `<params><layer name>` line per layer, a blank
-// line, then for every conv / linear (w, b) and batchnorm (w) tensor a `--- w.<layer>` marker line followed by the raw
+// line, then for every conv / linear (w, b), batchnorm (w) and group-norm (w, b: `vector{ G } batchnorm`) tensor a `--- w.<layer>` marker line followed by the raw
 // fp32 values, and a closing `---`.  Loading into an already built model skips the layer section and reads the blobs in
 // layer order (the reference's own reload of the layer section is unfinished: `_parm` text is not Forth source).
 int model_save(Model &m, const char *fname) {
@@ -1181,7 +1215,7 @@ int model_save(Model &m, const char *fname) {
     for (int i = 0; i + 1 < L; i++) {
         Tensor &in = m.at(i); const int fn = in.grad_fn;
         if ((fn == T4K_L_CONV || fn == T4K_L_LINEAR || fn == T4K_L_DCONV) && in.grad[0] && in.grad[1]) { dump('w', LAYER_NAME[fn], *in.grad[0]); dump('b', LAYER_NAME[fn], *in.grad[1]); }   // (the reference skips dconv2d blobs, aio_model.cpp:170: a net it cannot run)
-        else if (fn == T4K_L_BATCHNM && in.grad[0]) dump('w', LAYER_NAME[fn], *in.grad[0]);
+        else if (fn == T4K_L_BATCHNM && in.grad[0]) { dump('w', LAYER_NAME[fn], *in.grad[0]); if (norm_grp(in)) dump('b', LAYER_NAME[fn], *in.grad[1]); }   // batchnorm proper saves gamma alone, as the reference does
     }
     fprintf(f, "\n---\n");
     fclose(f);
@@ -1209,7 +1243,7 @@ int model_load(Model &m, const char *fname) {
     for (int i = 0; i + 1 < L && !err; i++) {
         Tensor &in = m.at(i); const int fn = in.grad_fn;
         if ((fn == T4K_L_CONV || fn == T4K_L_LINEAR || fn == T4K_L_DCONV) && in.grad[0] && in.grad[1]) { rd(*in.grad[0]); if (!err) rd(*in.grad[1]); }
-        else if (fn == T4K_L_BATCHNM && in.grad[0]) rd(*in.grad[0]);
+        else if (fn == T4K_L_BATCHNM && in.grad[0]) { rd(*in.grad[0]); if (!err && norm_grp(in)) rd(*in.grad[1]); }
     }
     if (!err) {                                          // the blob list must end here: a closing `---` line and nothing else
         while (getline_(line) && !line.length()) {}

@@ -107,7 +107,10 @@ static std::string parm_s(Tensor &in, Tensor &out) {     // aio_model.cpp:103-14
     case T4K_L_AVGPOOL: case T4K_L_MAXPOOL: case T4K_L_MINPOOL: o << S << "x" << S;
         if (in.iparm == 1) o << ", S=" << in.stride[1] << ", P=" << in.stride[2];      // the vector form says its stride and padding; every other line is the reference's
         break;
-    case T4K_L_BATCHNM: o << "mtum=" << p; break;
+    case T4K_L_BATCHNM:
+        if (norm_grp(in)) o << "G=" << in.iparm << ", eps=1e-05";          // the vector form, a group norm; every other line is the reference's
+        else o << "mtum=" << p;
+        break;
     case T4K_L_USAMPLE: { const char *nm[] = {"nearest", "linear", "bilinear", "cubic"}; o << S << "x" << S << " " << nm[in.iparm & 3]; } break;
     default: break;
     }

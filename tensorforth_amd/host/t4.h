@@ -377,6 +377,7 @@ std::string fmt_tensor(Tensor &t, int thres = 0);                      // src/io
 std::string fmt_model(Model &m);                        // src/io/aio_model.cpp:65-141
 std::string fmt_dump(Tensor &t);                        // Tensor::_dump of a parameter tensor (optimizer trace, gradient.cu:70-74)
 std::string fmt_show(Tensor &t, bool dump);              // Tensor::show src/mu/tensor.cu:587-684 (trace levels 1 / 2)
+bool norm_grp(const Tensor &in);                        // model.cpp: a T4K_L_BATCHNM layer of the vector form, `vector{ G } batchnorm` (group norm)
 std::string fmt_parm(Tensor &in, Tensor &out);          // src/io/aio_model.cpp:103-141 (layer parameter text)
 int model_save(Model &m, const char *fname);            // src/io/aio_model.cpp:16-35,143-181 (.t4 model file)
 int model_load(Model &m, const char *fname);            // src/io/aio_model.cpp:38-60,206-238 (parameter section)

@@ -443,6 +443,17 @@ void VM::nnop(int op) {
         MTOS().add(op, opt[0], 0, opt);
         return;
     }
+    // beyond the reference ( N V -- N ): a vector{ G } on top of a model makes `batchnorm` a group norm over G groups of channels per sample - G = 1 layer
+    // norm, G = C instance norm; further cells are ignored.  The reference prints "( N n -- ) one param required!" here
+    if (op == T4K_L_BATCHNM && TOS1T() && TTOS().rank == 1 && SP() > 0 && is_m(SS(-1))) {
+        Tensor &t = TTOS();
+        std::vector<float> vo; t.to_host(vo, std::min<uint64_t>(t.numel, 1));
+        DU x = POP(); DROP(x);                           // the vector is dropped and freed, as the pool branch does
+        uint16_t opt[4] = {0, 0, 0, 0};
+        if (!vo.empty()) opt[0] = (uint16_t)(int)vo[0];
+        MTOS().add(op, 0, 0, opt);
+        return;
+    }
     if (TOS1T()) {                                       // tensor ops (destructive)
         Tensor &t = TTOS();
         switch (op) {
