@@ -596,14 +596,41 @@ __device__ __forceinline__ void head_prefetch(const FwdArgs &p, float *L, int im
 // for.  A row's own chain - six dependent cross-lane exchanges through the LDS crossbar, ~110 cycles each - is unchanged, so every sum keeps its order and
 // its bits; done row after row, the 13 rows of a wave's share of W1 were 78 exchange latencies in a chain (8.6 k of the matvec's 10.2 k cycles, and the
 // reason neither a prefetch of W1 nor a warm L2 ever changed it); side by side they are 6.
+// Since round 9 the steps themselves run on the vector ALUs (lane_ops.h, in front of this text: lane swaps and DPP, the same pairs i <-> i ^ off in the same
+// order, so the same bits) and no step waits for the LDS counter.  CS_LANES_XBAR (lab builds: T4K_STACK_LANES_XBAR=1) selects the crossbar form for the stamped
+// timeline.  Either form reads lanes whatever EXEC says or needs them all: every call site below is wave-uniform with 64 live lanes.
+#ifndef CS_LANES_XBAR
+#define CS_LANES_XBAR 0
+#endif
 template <int NR> __device__ __forceinline__ void lanes_sum(float (&a)[NR]) {
+    if constexpr (CS_LANES_XBAR == 0) lanes_sum_valu(a);
+    else {
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        float t[NR];
+        for (int off = 32; off > 0; off >>= 1) {
+            float t[NR];
 #pragma unroll
-        for (int r = 0; r < NR; r++) t[r] = __shfl_xor(a[r], off, 64);
+            for (int r = 0; r < NR; r++) t[r] = __shfl_xor(a[r], off, 64);
 #pragma unroll
-        for (int r = 0; r < NR; r++) a[r] += t[r];
+            for (int r = 0; r < NR; r++) a[r] += t[r];
+        }
+    }
+}
+__device__ __forceinline__ float lanes_max1(float v) {
+    if constexpr (CS_LANES_XBAR == 0) { float a[1] = {v}; lanes_max_valu(a); return a[0]; }
+    else {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+        return v;
+    }
+}
+__device__ __forceinline__ void lanes_argmax1(float &bm, int &bi) {      // largest value, lowest index among its holders (k_hit's first-arg-max rule)
+    if constexpr (CS_LANES_XBAR == 0) { float m[1] = {bm}; int i[1] = {bi}; lanes_argmax_valu(m, i); bm = m[0]; bi = i[0]; }
+    else {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const float m2 = __shfl_xor(bm, off, 64); const int i2 = __shfl_xor(bi, off, 64);
+            if (m2 > bm || (m2 == bm && i2 < bi)) { bm = m2; bi = i2; }
+        }
     }
 }
 __device__ __forceinline__ void head_fwd(const FwdArgs &p, float *L, int img, int band) {
@@ -620,6 +647,21 @@ __device__ __forceinline__ void head_fwd(const FwdArgs &p, float *L, int img, in
     // lanes' sums (lanes_sum above: they were most of it while they ran row after row).
     constexpr bool V4 = head_v4_ok();
     CS_STAMP(11);
+    // The collector's later operands depend on nothing computed here: their loads leave in front of the first trip's W1 loads, in the same round trip (issued
+    // behind the matvec they were a round trip of their own in front of the second linear layer).  The sched_barrier behind the W1 load loops keeps them there.
+    constexpr int NR2 = (EB + CS_WAVES - 1) / CS_WAVES, NE2 = (EA + 63) / 64;
+    float w2v[NR2][NE2], b1v = 0.f, b2v[NR2];
+    u32 lbl = 0;                                                  // the image's label, when the one-hot row and the hit flag ride along (HeadArgs)
+    if (CS_SPLIT == 1 || band == CS_SPLIT - 1) {
+#pragma unroll
+        for (int r = 0; r < NR2; r++) {
+#pragma unroll
+            for (int q = 0; q < NE2; q++) { const int j = wave + r * CS_WAVES, e = lane + q * 64; w2v[r][q] = (j < EB && e < EA) ? h.W2[(long)j * EA + e] : 0.f; }
+            const int j = wave + r * CS_WAVES; b2v[r] = (h.B2 && j < EB) ? h.B2[j] : 0.f;
+        }
+        if (tid < EA && h.B1) b1v = h.B1[tid];
+        if (h.hit_flag && (u32)img < h.n_label) lbl = h.label[img];
+    }
 #if CS_H_GRP
     {
         static_assert(head_v4_ok(), "group head: 16-byte row geometry");
@@ -763,20 +805,6 @@ __device__ __forceinline__ void head_fwd(const FwdArgs &p, float *L, int img, in
     }
 #endif
     CS_STAMP(12);
-    // the collector's later operands do not depend on anything computed here: fetch them now, under the exchange
-    constexpr int NR2 = (EB + CS_WAVES - 1) / CS_WAVES, NE2 = (EA + 63) / 64;
-    float w2v[NR2][NE2], b1v = 0.f, b2v[NR2];
-    u32 lbl = 0;                                                  // the image's label, when the one-hot row and the hit flag ride along (HeadArgs)
-    if (CS_SPLIT == 1 || band == CS_SPLIT - 1) {
-#pragma unroll
-        for (int r = 0; r < NR2; r++) {
-#pragma unroll
-            for (int q = 0; q < NE2; q++) { const int j = wave + r * CS_WAVES, e = lane + q * 64; w2v[r][q] = (j < EB && e < EA) ? h.W2[(long)j * EA + e] : 0.f; }
-            const int j = wave + r * CS_WAVES; b2v[r] = (h.B2 && j < EB) ? h.B2[j] : 0.f;      // with W2: behind the matvec it would be one more dependent round trip
-        }
-        if (tid < EA && h.B1) b1v = h.B1[tid];
-        if (h.hit_flag && (u32)img < h.n_label) lbl = h.label[img];
-    }
     lds_barrier();
 #if CS_H_GRP
     if (band < CS_SPLIT - 1) return;                              // every band's partial sums are on their way to the collectors
@@ -793,6 +821,14 @@ __device__ __forceinline__ void head_fwd(const FwdArgs &p, float *L, int img, in
         const long z = (long)img * EA + tid;
         float y = 0.f;
         constexpr int NPUB = CS_H_GRP ? CS_SPLIT : CS_SPLIT - 1;      // group head: the collector's own band arrives through the words as well (from its group)
+        // the dropout draw is a function of the position alone: its ten Philox rounds run here, in front of the poll, and only u01 and act1 stay behind it.
+        // (The empty asm takes the words as operands: they exist at this point, whatever the compiler would rather sink behind the poll loop.)
+        u32 rz = 0;
+        if (MID == L_DROPOUT) {
+            u32 r[4]; philox4x32_10(h.base + (u64)(z >> 2), h.seed, r);
+            rz = r[z & 3];
+            asm volatile("" : "+v"(rz));
+        }
         if (NPUB > 0) {
 #pragma unroll
             for (int b = 0; b < NPUB; b++) {
@@ -810,17 +846,17 @@ __device__ __forceinline__ void head_fwd(const FwdArgs &p, float *L, int img, in
                 y += __uint_as_float((u32)v);
             }
         }
+        CS_STAMP(15);
         if (!CS_H_GRP) y += part[tid];
         y += b1v;
         h.Y1[z] = y;
         float o = y, f = 1.f;
         if (MID) {
-            u32 r[4] = {0, 0, 0, 0};
-            if (MID == L_DROPOUT) philox4x32_10(h.base + (u64)(z >> 2), h.seed, r);
-            act1<MID>(y, MID == L_DROPOUT ? u01(r[z & 3]) : 0.f, CS_H_ALPHA, o, f);
+            act1<MID>(y, MID == L_DROPOUT ? u01(rz) : 0.f, CS_H_ALPHA, o, f);
             h.Fm[z] = f; h.Am[z] = o;
         }
         x2[tid] = o;
+        CS_STAMP(16);
     }
     lds_barrier();
     CS_STAMP(13);
@@ -833,28 +869,24 @@ __device__ __forceinline__ void head_fwd(const FwdArgs &p, float *L, int img, in
         a2[r] = a;
     }
     lanes_sum(a2);
+    CS_STAMP(17);
 #pragma unroll
     for (int r = 0; r < NR2; r++) { const int j = wave + r * CS_WAVES; if (lane == 0 && j < EB) y2[j] = a2[r] + b2v[r]; }
     lds_barrier();
     if (tid < 64) {                                               // softmax over the EB outputs (k_softmax's arithmetic, as k_linsmall_fwd)
         const bool live = tid < EB;
         const float v = live ? y2[tid] : -3.402823466e+38f;
-        float mx = v;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
+        const float mx = lanes_max1(v);
+        CS_STAMP(18);
         const float e = live ? __expf(v - mx) : 0.f;
-        float sm_ = e;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) sm_ += __shfl_xor(sm_, off, 64);
-        const float pv = e / sm_;
+        float sm1[1] = {e};
+        lanes_sum(sm1);
+        CS_STAMP(19);
+        const float pv = e / sm1[0];
         if (live) { h.Y2[(long)img * EB + tid] = v; if (h.P) h.P[(long)img * EB + tid] = pv; }
         if (h.hit_flag) {                                         // Model::onehot(Dataset&) + hit (loss.cpp:47-72, forward.cu:57-60; k_hit's first-arg-max rule) for this image
             float bm = live ? pv : -3.402823466e+38f; int bi = live ? tid : 0x7fffffff;
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                const float m2 = __shfl_xor(bm, off, 64); const int i2 = __shfl_xor(bi, off, 64);
-                if (m2 > bm || (m2 == bm && i2 < bi)) { bm = m2; bi = i2; }
-            }
+            lanes_argmax1(bm, bi);
             const bool lab = (u32)img < h.n_label;
             const int m = lbl < (u32)EB ? (int)lbl : 0;
             if (lab && live) h.hot[(long)img * EB + tid] = tid == m ? 1.0f : 0.0f;

@@ -78,6 +78,25 @@ int main(int argc, char **argv) {
                 for (int k = 1; k < 32; k++) if (cnt[k]) printf(" %d:%.0f", k, sum[k] / cnt[k]);
                 if (c1112) printf("  | 11->12 avg %.0f max %.0f (%d workgroups)", d1112 / c1112, mx1112, c1112);
                 printf("\n");
+                // the head's collector band (the only one that writes stamps 13 .. 19), link by link: 12 matvec done -> [barrier, poll] -> 15 -> [+ B1, Y1 store,
+                // draw, act1, x2 to LDS] -> 16 -> [barrier] -> 13 -> [layer 2 dot products, lane sums] -> 17 -> [y2 to LDS, barrier, softmax max] -> 18 ->
+                // [exp, softmax sum] -> 19 -> [divide, stores, hit rider] -> 14
+                static const int chain[] = {12, 15, 16, 13, 17, 18, 19, 14};
+                double lk[8] = {0}; int nc = 0;
+                for (int b = 0; b < N * split; b++) {
+                    const unsigned long long *s = &h[(size_t)b * 32];
+                    const int w = b / split + N * (b % split);
+                    if ((w >= cus) != (late != 0) || !s[0]) continue;
+                    bool all = true; for (int k : chain) all = all && s[k] != 0;
+                    if (!all) continue;
+                    for (int i = 1; i < 8; i++) lk[i] += (double)(long long)(s[chain[i]] - s[chain[i - 1]]);
+                    nc++;
+                }
+                if (nc) {
+                    printf("    head collector (%d workgroups):", nc);
+                    for (int i = 1; i < 8; i++) printf(" %d->%d:%.0f", chain[i - 1], chain[i], lk[i] / nc);
+                    printf("  | 12->14 %.0f\n", (lk[1] + lk[2] + lk[3] + lk[4] + lk[5] + lk[6] + lk[7]) / nc);
+                }
             }
         }
         // banded backward: the two wave roles of every stage (stamps 3 / 4 + 8 S: dF role, thread 0; 24 / 25 + 2 S: dX role, first lane of wave 8;
