@@ -21,7 +21,8 @@ namespace {
 //   4. one barrier, then the K loop proper: B fragments from the wave's DMA slots, A fragments from the dY1 tile, k-groups meet in LDS, epilogue as
 //      gemm_s32_body's (in-place dX1 behind the epoch-tagged arrival slots of the dW1 readers).
 // The tiles' dY1 comes from an MFMA sum, the riders' stored dY1 from the oracle's fmaf chain: the two differ by rounding only (1e-7 relative to the
-// largest term), far inside the 1e-4 bar of dW1 / dX1; every tensor the reference materialises is the riders' (bit-equal to the two-launch path).
+// largest term), far inside the 1e-4 bar of dW1 / dX1; every tensor the reference materialises is the riders' (P, Y2, dX2, dY1 and, from EB = 5, dW2 bit-equal to the two-launch path;
+// dB2 and dB1 add row groups where that path adds sample by sample).
 struct HeadBwd {
     const float *P, *T, *W2, *MASK;     // softmax output [N][EB], target, W2 [EB][EA], derivative mask of the layer between the linear layers [N][EA]
     float *X2, *DW2, *DB2, *Y1, *Y2;    // head input [N][EA] (receives dX2), gradients, dY1 tensor (= dX2 * mask), second copy of out - target
@@ -32,8 +33,48 @@ struct HeadBwd {
     const float *Z;                     // 4 KiB of zeros: source of DMA lanes past the K range / the matrix edge
 #ifdef T4K_LAB
     int lab;                            // LAB build only: timing ablations (wrong results), the bits of T4K_HB_LAB, read at run time
+    unsigned long long *prof;           // LAB build only: role stamps, HB_PROF_WORDS per workgroup (T4K_HB_PROF_PTR, tools/experiments/head_bwd_lab.py); nullptr: none
 #endif
 };
+// ---- role stamps (LAB build only; the release build compiles every HB_* macro below to nothing).  Wave 0 of a workgroup reads the shader clock at the
+// links of its role's chain and KEEPS the readings in scalar registers; thread 0 stores them once, behind the role's last store, so no stamp adds a
+// memory operation or a wait to the chain it measures.  Words of a workgroup's record: [0, 14) s_memtime at the role's links (see the HB_STAMP calls),
+// 14 | 15 the 100 MHz clock (one for all XCDs) at the start | end, 16 spins of the role's wait, 17 role (0 dW1 tile, 1 dX1 tile, 2 store rider, 3 column
+// rider), 18 HW_ID, 19 XCC_ID.
+#ifdef T4K_LAB
+constexpr int HB_PROF_WORDS = 32;
+__device__ __forceinline__ unsigned long long hb_clock() {
+    unsigned long long t;
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    return t;
+}
+__device__ __forceinline__ unsigned long long hb_wallclock() {
+    unsigned long long t;
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    return t;
+}
+#define HB_STAMP(k) do { if (hb.prof) hb_ts[k] = hb_clock(); } while (0)
+#define HB_WALL(k) do { if (hb.prof) hb_ts[k] = hb_wallclock(); } while (0)
+#define HB_LABX(...) __VA_ARGS__
+// behind the role's last store: wait for the stores (word n - 1 is `drained`), then thread 0 writes the record
+#define HB_FLUSH(n, role) do { if (hb.prof) { \
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); hb_ts[(n) - 1] = hb_clock(); hb_ts[15] = hb_wallclock(); \
+        if (tid == 0) { \
+            unsigned long long *rec_ = hb.prof + (long)bx * HB_PROF_WORDS; \
+            _Pragma("unroll") for (int k_ = 0; k_ < 16; k_++) if (k_ < (n) || k_ >= 14) rec_[k_] = hb_ts[k_]; \
+            rec_[16] = (unsigned long long)hb_spins; rec_[17] = (role); \
+            rec_[18] = __builtin_amdgcn_s_getreg(4 | (31 << 11)); rec_[19] = __builtin_amdgcn_s_getreg(20 | (31 << 11)); \
+        } } } while (0)
+#else
+#define HB_STAMP(k) do {} while (0)
+#define HB_WALL(k) do {} while (0)
+#define HB_LABX(...)
+#define HB_FLUSH(n, role) do {} while (0)
+#endif
 constexpr int HB_CW = 4;                // columns of the head's input per rider workgroup (k_linsmall_bwd_cols: LSC_CW)
 constexpr int HB_AP = 33;               // pitch of the dY1 tile in LDS
 // workgroups [0, a1): dW1 tiles (read X1, never wait) | [a1, a1 + nr): riders - the store rider, then the column riders | the rest: dX1 tiles (write X1 in place,
@@ -49,6 +90,8 @@ __global__ void __launch_bounds__(256) k_head_bwd_l32(GemmP p1, GemmP p2, int a1
     constexpr int lab = 0;              // release build: every HB_LAB branch below folds away
 #endif
     const auto HB_LAB = [=](int bit) { return (lab & bit) != 0; };
+    HB_LABX(unsigned long long hb_ts[16] = {}; int hb_spins = 0;)
+    HB_WALL(14); HB_STAMP(0);
     if (bx < a1 || bx >= a1 + nr) {
         // ---------------------------------------------------------------- GEMM tile
         if (HB_LAB(2)) return;
@@ -80,45 +123,67 @@ __global__ void __launch_bounds__(256) k_head_bwd_l32(GemmP p1, GemmP p2, int a1
                 }
             }
         }
-        // epilogue operands, requested with everything else
+        // Operand loads (round 10): straight-line code.  Every bound picks the ADDRESS - the element, or a word of the zero strip hb.Z - and no load is skipped,
+        // so the requests of a block go out together and the first MFMA waits for them once.  `ok ? P[i] - T[i] : 0.f` compiled to a branch per element with
+        // the wait for both loads INSIDE it: one memory round trip per P - T pair, five in a row at EB = 10 (profiles/LAB_NOTES.md 16).
+        const float *const Zp = hb.Z;
+        // epilogue operands, requested with everything else: what dW1 accumulates onto | the first mask behind dX1, and the second mask
         const int gn = n0 + l31;
-        float oprev[4], mk1[4], mk2[4];
+        const float *const e1p = first ? pO : hb.mc1.d1 ? hb.mc1.m1 : nullptr, *const e2p = (!first && hb.mc1.d2) ? hb.mc1.m2 : nullptr;
+        float e1[4], e2[4];
 #pragma unroll
         for (int q = 0; q < 4; q++) {
             const int r = 4 * w + q, gm = m0 + (r & 3) + 8 * (r >> 2) + 4 * h;
             const bool ok = gm < M && gn < Nn;
             const long z = (long)gm * Nn + gn;
-            oprev[q] = (first && ok) ? pO[z] : 0.f;
-            mk1[q] = (!first && hb.mc1.d1 && ok) ? hb.mc1.m1[z] : 0.f;
-            mk2[q] = (!first && hb.mc1.d2 && ok) ? hb.mc1.m2[z] : 0.f;
+            e1[q] = *(ok && e1p ? e1p + z : Zp);
+            e2[q] = *(ok && e2p ? e2p + z : Zp);
         }
         // 2. operands of the dY1 blocks this wave prepares (blocks w and w + 4 of the tile's k range), in MFMA layout
         //    dW1 tile: block = 32 samples, the tile's 32 columns e of dY1;   dX1 tile: block = 32 columns e, the tile's 32 samples
         float av[2][8], bv[2][8], mk[2][16];
 #pragma unroll
         for (int t = 0; t < 2; t++) {
-            const int blk = w + 4 * t;
-            const int arow = first ? 32 * blk + l31 : m0 + l31;      // sample of this lane's A values (P - T)
-            const int bcl = first ? m0 + l31 : 32 * blk + l31;       // column e of this lane's B values (W2)
-            const bool on = blk < nblk, aok = on && arow < N, bok = on && bcl < EA;
 #pragma unroll
-            for (int s = 0; s < 8; s++) {
-                const int j = 2 * s + h;
-                const bool jk = j < EB;
-                if (t == 1 && !first)  av[t][s] = av[0][s];          // the same 32 samples for every column block
-                else av[t][s] = (aok && jk && !HB_LAB(8)) ? hb.P[(long)arow * EB + j] - hb.T[(long)arow * EB + j] : 0.f;
-                if (t == 1 && first)   bv[t][s] = bv[0][s];
-                else bv[t][s] = (bok && jk && !HB_LAB(8)) ? hb.W2[(long)j * EA + bcl] : 0.f;
-            }
+            for (int s = 0; s < 8; s++) av[t][s] = bv[t][s] = 0.f;
 #pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const int ro = (r & 3) + 8 * (r >> 2) + 4 * h;
-                const int n = first ? 32 * blk + ro : m0 + ro, e = first ? m0 + l31 : 32 * blk + l31;
-                const bool ok = on && n < N && e < EA;
-                const long zo = (long)n * EA + e;
-                mk[t][r] = (ok && !HB_LAB(64)) ? (hb.MSKB ? hb.MASK[zo] * hb.MSKB[zo] : hb.MASK[zo]) : 0.f;
+            for (int r = 0; r < 16; r++) mk[t][r] = 0.f;
+            if (t == 0 || nblk > 4) {                                // (no wave has a second block up to K = 128)
+                const int blk = w + 4 * t;
+                const int arow = first ? 32 * blk + l31 : m0 + l31;  // sample of this lane's A values (P - T): a dX1 tile's second block reads the first one's again
+                const int bcl = first ? m0 + l31 : 32 * blk + l31;   // column e of this lane's B values (W2): a dW1 tile's likewise
+                const bool on = blk < nblk, aok = on && arow < N, bok = on && bcl < EA;
+#pragma unroll
+                for (int s = 0; s < 8; s++) {
+                    const int j = 2 * s + h;
+                    const bool jk = j < EB && !HB_LAB(8);
+                    const long ia = (long)arow * EB + j;
+                    av[t][s] = *(aok && jk ? hb.P + ia : Zp) - *(aok && jk ? hb.T + ia : Zp);
+                    bv[t][s] = *(bok && jk ? hb.W2 + (long)j * EA + bcl : Zp);
+                }
+#pragma unroll
+                for (int r = 0; r < 16; r++) {
+                    const int ro = (r & 3) + 8 * (r >> 2) + 4 * h;
+                    const int n = first ? 32 * blk + ro : m0 + ro, e = first ? m0 + l31 : 32 * blk + l31;
+                    mk[t][r] = *(on && n < N && e < EA && !HB_LAB(64) ? hb.MASK + ((long)n * EA + e) : Zp);
+                }
             }
         }
+        if (hb.MSKB) {                                               // a second mask layer: its values multiply the first one's, one more round trip
+#pragma unroll
+            for (int t = 0; t < 2; t++) {
+                const int blk = w + 4 * t;
+                if (blk < nblk) {
+#pragma unroll
+                    for (int r = 0; r < 16; r++) {
+                        const int ro = (r & 3) + 8 * (r >> 2) + 4 * h;
+                        const int n = first ? 32 * blk + ro : m0 + ro, e = first ? m0 + l31 : 32 * blk + l31;
+                        mk[t][r] *= *(n < N && e < EA ? hb.MSKB + ((long)n * EA + e) : Zp);
+                    }
+                }
+            }
+        }
+        HB_STAMP(1);                                                 // B DMA and operand loads issued
         // 3. dY1 blocks on the matrix cores -> LDS
 #pragma unroll
         for (int t = 0; t < 2; t++) {
@@ -128,7 +193,10 @@ __global__ void __launch_bounds__(256) k_head_bwd_l32(GemmP p1, GemmP p2, int a1
 #pragma unroll
                 for (int r = 0; r < 16; r++) d[r] = 0.f;
 #pragma unroll
-                for (int s = 0; s < 8; s++) if (2 * s < EB) d = __builtin_amdgcn_mfma_f32_32x32x2f32(av[t][s], bv[t][s], d, 0, 0, 0);
+                for (int s = 0; s < 8; s++) if (2 * s < EB) {
+                    d = __builtin_amdgcn_mfma_f32_32x32x2f32(av[t][s], bv[t][s], d, 0, 0, 0);
+                    if (t == 0 && s == 0) HB_STAMP(2);               // first dY1 MFMA issued: its operands have landed
+                }
 #pragma unroll
                 for (int r = 0; r < 16; r++) {
                     const int ro = (r & 3) + 8 * (r >> 2) + 4 * h;
@@ -136,22 +204,39 @@ __global__ void __launch_bounds__(256) k_head_bwd_l32(GemmP p1, GemmP p2, int a1
                 }
             }
         }
+        HB_STAMP(3);                                                 // dY1 blocks in LDS
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // the wave's DMA blocks have landed (they were requested first)
+        __builtin_amdgcn_s_waitcnt(0x0F70);                          // the same wait once more, in the form the compiler's own count of requests in flight sees (it is blind
+                                                                     // to the statement above, and waited for the dW1 tag store below before it reused a register)
+        HB_STAMP(4);
         const bool early = slots && a1 <= 128;                       // per-wave arrival slots: X1 is consumed as far as this wave is concerned
         if (first && early && lane == 0) __hip_atomic_store(slots + 4 * tile + w, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __syncthreads();
+        // in-place dX1: the first look at the arrival slots of this column's dW1 tiles goes out here, as soon as a request no longer lengthens the wait for the
+        // DMA blocks - its round trip passes under barrier 1 and the K loop (the look only reads tags; the stores at the end are what waits for them)
+        const int gsh = early ? 2 : 0, gper = 1 << gsh, gslot = (a1 / tiles_n) * gper;   // (slots per dW1 tile: a shift, the look sits in front of barrier 1)
+        const bool gated = !first && slots && w == 0 && !HB_LAB(32);
+        unsigned gv[8];                                              // the tags as they come back, compared only where the verdict is needed: a comparison beside the
+#pragma unroll                                                       // request waits for it there (the parent's look sat behind barrier 1 with its wait: a round trip in
+        for (int u = 0; u < 8; u++) gv[u] = epoch;                   // front of the K loop, not under it)
+        const auto gate_look = [&]() {
+#pragma unroll
+            for (int u = 0; u < 8; u++) {                            // a1 <= 512 slots
+                const int i = lane + 64 * u;
+                if (i < gslot) { const int e0t = i >> gsh, ww = i - e0t * gper; gv[u] = __hip_atomic_load(slots + gper * (e0t * tiles_n + tn) + ww, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+            }
+        };
+        const auto gate_open = [&]() {
+            unsigned bad = 0;
+#pragma unroll
+            for (int u = 0; u < 8; u++) bad |= gv[u] ^ epoch;
+            return __all(bad == 0);
+        };
+        if (gated) gate_look();
+        // barrier 1: the dY1 tile is in LDS.  Not __syncthreads(): its fence would wait for the look (and for a dW1 tile's tag store) to come back
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        HB_STAMP(5);                                                 // past barrier 1
         if (tid == 0 && !HB_LAB(4)) __hip_atomic_store(pslots + bx, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // P and T are in registers everywhere: `out -= target` may land as far as this workgroup is concerned
         if (HB_LAB(16)) return;
-        // in-place dX1: the first look at the arrival slots of this column's dW1 tiles goes out here - its round trip passes under the K loop
-        const int gper = early ? 4 : 1, gslot = (a1 / tiles_n) * gper;
-        unsigned gbad = 0;
-        if (!first && slots && w == 0 && !HB_LAB(32)) {
-#pragma unroll
-            for (int u = 0; u < 8; u++) {
-                const int i = lane + 64 * u;
-                if (i < gslot) { const int e0t = i / gper, ww = i - e0t * gper; gbad |= __hip_atomic_load(slots + gper * (e0t * tiles_n + tn) + ww, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ^ epoch; }
-            }
-        }
         if (first && slots && !early && tid == 0) __hip_atomic_store(slots + tile, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         // 4. K loop
         f32x16 acc0, acc1;
@@ -175,10 +260,14 @@ __global__ void __launch_bounds__(256) k_head_bwd_l32(GemmP p1, GemmP p2, int a1
                 }
             }
         }
+        HB_STAMP(6);                                                 // K loop: every MFMA issued
+        if (gated && !gate_open()) { HB_LABX(hb_spins = 1;) gate_look(); }     // the first look came too early: the second one's round trip passes under the MFMAs' drain and the meeting
         // the four k-groups meet in LDS (each wave's partial sums over its own, consumed, B slots)
 #pragma unroll
         for (int r = 0; r < 16; r++) Bs[r * 64 + lane] = acc0[r] + acc1[r];
-        if (!first && slots && w == 0 && !HB_LAB(32) && !__all(gbad == 0)) {      // the dW1 tiles of this column have consumed X1 (see gemm_s32_body gate_mode 2); a1 <= 512 slots
+        HB_STAMP(7);                                                 // meeting written
+        if (gated && !gate_open()) {                                 // the dW1 tiles of this column have consumed X1 (see gemm_s32_body gate_mode 2)
+            HB_LABX(hb_spins++;)                                     // (looks that failed, the first two included)
             for (int spin_it = 0;; spin_it++) {
                 if (spin_it > T4K_SPIN_MAX) { if (lane == 0 && g_spin_err_dev) __hip_atomic_store(g_spin_err_dev, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); break; }
                 unsigned bad = 0;
@@ -188,10 +277,13 @@ __global__ void __launch_bounds__(256) k_head_bwd_l32(GemmP p1, GemmP p2, int a1
                     bad |= __hip_atomic_load(slots + gper * (e0t * tiles_n + tn) + ww, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ^ epoch;
                 }
                 if (__all(bad == 0)) break;
+                HB_LABX(hb_spins++;)
                 __builtin_amdgcn_s_sleep(2);
             }
         }
+        HB_STAMP(8);                                                 // gate passed
         __syncthreads();
+        HB_STAMP(9);                                                 // past barrier 2
 #pragma unroll
         for (int q = 0; q < 4; q++) {
             const int r = 4 * w + q, gm = m0 + (r & 3) + 8 * (r >> 2) + 4 * h;
@@ -200,19 +292,22 @@ __global__ void __launch_bounds__(256) k_head_bwd_l32(GemmP p1, GemmP p2, int a1
             for (int g = 1; g < 4; g++) v += lds[g * 2048 + r * 64 + lane];       // k-groups in order
             if (gm < M && gn < Nn) {
                 const long z = (long)gm * Nn + gn;
-                if (first) pO[z] = v + oprev[q];                                  // dW1 accumulates (beta = 1)
+                if (first) pO[z] = v + e1[q];                                  // dW1 accumulates (beta = 1)
                 else {
                     pO[z] = v;
-                    if (hb.mc1.d1) { const float g1 = v * mk1[q]; hb.mc1.d1[z] = g1; if (hb.mc1.d2) hb.mc1.d2[z] = g1 * mk2[q]; }
+                    if (hb.mc1.d1) { const float g1 = v * e1[q]; hb.mc1.d1[z] = g1; if (hb.mc1.d2) hb.mc1.d2[z] = g1 * e2[q]; }
                 }
             }
         }
+        HB_STAMP(10);                                                // stores issued
+        HB_FLUSH(12, first ? 0 : 1);
         return;
     }
     if (bx == a1) {
         // ---------------------------------------------------------------- store rider: `out -= target` in place (+ its copy), once every other workgroup holds P and T
         const int tot = N * EB;
         for (int i = tid; i < tot; i += 256) lds[i] = hb.P[i] - hb.T[i];
+        HB_STAMP(1);                                                 // P - T in LDS
         if (w == 0 && !HB_LAB(4 | 1 | 2 | 16)) {         // (ablations that drop arrivals must drop the wait too)
             // every other workgroup tags its slot once its P / T values sit in registers / LDS: plain stores to separate words (an arrival COUNTER serialised
             // 270 agent-scope atomics on one address: +1.2 us on the launch), polled here with the 64 lanes' loads in flight together
@@ -222,12 +317,16 @@ __global__ void __launch_bounds__(256) k_head_bwd_l32(GemmP p1, GemmP p2, int a1
 #pragma unroll 4
                 for (int i = lane; i < hb.nwg; i += 64) if (i != bx) bad |= __hip_atomic_load(pslots + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ^ epoch;
                 if (__all(bad == 0)) break;
+                HB_LABX(hb_spins++;)
                 __builtin_amdgcn_s_sleep(2);
             }
         }
+        HB_STAMP(2);                                                 // poll passed
         __syncthreads();
         float *Pw = const_cast<float *>(hb.P);
         for (int i = tid; i < tot; i += 256) { const float v = lds[i]; Pw[i] = v; if (hb.Y2) hb.Y2[i] = v; }
+        HB_STAMP(3);                                                 // stored
+        HB_FLUSH(5, 2);
         return;
     }
     // -------------------------------------------------------------------- column riders: k_linsmall_bwd_cols's slice of HB_CW columns of the head's input
@@ -235,7 +334,10 @@ __global__ void __launch_bounds__(256) k_head_bwd_l32(GemmP p1, GemmP p2, int a1
     constexpr int CW = HB_CW, ZI = 8;
     const int cb = bx - a1 - 1, c0 = cb * CW, cw = min(CW, EA - c0);
     float *dys = lds, *Ws = dys + N * EB, *Xs = Ws + EB * CW, *red = Xs + N * CW;       // dY2 [N][EB], W2 slice [EB][CW], X2 slice [N][CW] (then the dY1 slice), partial sums [4][EB * CW] / [32][CW]
+    const int nout = EB * CW, G = min(4, 256 / nout);               // thread groups splitting the batch of one dW2 output (contiguous ranges, summed in order)
     float mk[ZI], mkb[ZI];
+    float odw2 = 0.f, odb1 = 0.f, odb2 = 0.f;                        // what DW2 / DB1 / DB2 hold: each element has ONE writer in the launch, so the values are requested
+                                                                     // with the staging loads and the three accumulations end in plain stores, not in round trips of their own
 #pragma unroll
     for (int k = 0; k < ZI; k++) {
         const int z = tid + k * 256, n = z / CW, c = z - n * CW;
@@ -251,6 +353,11 @@ __global__ void __launch_bounds__(256) k_head_bwd_l32(GemmP p1, GemmP p2, int a1
         if (tid < EB * CW) { const int j = tid / CW, c = tid - j * CW; pw = c < cw ? hb.W2[(long)j * EA + c0 + c] : 0.f; }
 #pragma unroll
         for (int q = 0; q < PRE; q++) { const int i = tid + q * 256, n = i / CW, c = i - n * CW; px[q] = (hb.train && i < N * CW && c < cw) ? hb.X2[(long)n * EA + c0 + c] : 0.f; }
+        if (hb.train) {
+            if (tid < nout) { const int j = tid / CW, c = tid - j * CW; if (c < cw) odw2 = hb.DW2[(long)j * EA + c0 + c]; }
+            if (tid < cw) odb1 = hb.DB1[c0 + tid];
+            if (cb == 0 && tid < EB) odb2 = hb.DB2[tid];
+        }
 #pragma unroll
         for (int q = 0; q < PRE; q++) { const int i = tid + q * 256; if (i < N * EB) dys[i] = pd[q] - pt[q]; }
         if (tid < EB * CW) Ws[tid] = pw;
@@ -263,8 +370,8 @@ __global__ void __launch_bounds__(256) k_head_bwd_l32(GemmP p1, GemmP p2, int a1
             for (int i = tid + PRE * 256; i < N * CW; i += 256) { const int n = i / CW, c = i - n * CW; Xs[i] = c < cw ? hb.X2[(long)n * EA + c0 + c] : 0.f; }
     }
     __syncthreads();
+    HB_STAMP(1);                                                     // staged
     if (tid == 0 && !HB_LAB(4)) __hip_atomic_store(pslots + bx, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // P and the target are staged here
-    const int nout = EB * CW, G = min(4, 256 / nout);               // thread groups splitting the batch of one dW2 output (contiguous ranges, summed in order)
     float dwacc = 0.f;
     if (hb.train && tid < nout * G) {
         const int g = tid / nout, t = tid - g * nout, j = t / CW, c = t - j * CW;
@@ -274,6 +381,14 @@ __global__ void __launch_bounds__(256) k_head_bwd_l32(GemmP p1, GemmP p2, int a1
         if (G > 1) red[g * nout + t] = dwacc;
     }
     __syncthreads();                                                 // the X2 slice is consumed: its place takes the dY1 slice
+    HB_STAMP(2);                                                     // dW2 loop done
+    if (hb.train && tid < nout) {                                    // the groups in order, onto what DW2 held: the store passes under the dX2 chain
+        const int j = tid / CW, c = tid - j * CW;
+        float a = dwacc;
+        for (int g = 1; g < G; g++) a += red[g * nout + tid];
+        if (c < cw) hb.DW2[(long)j * EA + c0 + c] = odw2 + a;
+    }
+    HB_STAMP(3);                                                     // DW2 accumulated
     {
         float g1v[ZI];
 #pragma unroll
@@ -292,15 +407,9 @@ __global__ void __launch_bounds__(256) k_head_bwd_l32(GemmP p1, GemmP p2, int a1
 #pragma unroll
         for (int k = 0; k < ZI; k++) { const int z = tid + k * 256; if (z < N * CW) Xs[z] = g1v[k]; }
     }
-    __syncthreads();
+    __syncthreads();                                                 // (every read of the dW2 partial sums lies in front of this barrier: red is free again)
+    HB_STAMP(4);                                                     // dX2 / dY1 stored
     if (hb.train) {
-        if (tid < nout) {
-            const int j = tid / CW, c = tid - j * CW;
-            float a = dwacc;
-            for (int g = 1; g < G; g++) a += red[g * nout + tid];
-            if (c < cw) hb.DW2[(long)j * EA + c0 + c] += a;
-        }
-        __syncthreads();                                             // red is free again
         {   // dB1[c0 + c] = sum_n dY1[n, c0 + c] (k_dlinear_db nmath.cu:274-280): 64 row groups per column, then the groups in order
             const int c = tid & (CW - 1), g = tid >> 2;
             float b = 0.f;
@@ -313,8 +422,9 @@ __global__ void __launch_bounds__(256) k_head_bwd_l32(GemmP p1, GemmP p2, int a1
             float b = 0.f;
 #pragma unroll 8
             for (int g = 0; g < 64; g++) b += red[g * CW + tid];
-            if (tid < cw) hb.DB1[c0 + tid] += b;
+            if (tid < cw) hb.DB1[c0 + tid] = odb1 + b;
         }
+        HB_STAMP(5);                                                 // DB1 accumulated
         if (cb == 0) {                                               // dB2[j] = sum_n dY2[n, j]: 16 row groups per output
             __syncthreads();
             const int j = tid & 15, g = tid >> 4;
@@ -329,10 +439,12 @@ __global__ void __launch_bounds__(256) k_head_bwd_l32(GemmP p1, GemmP p2, int a1
                 float t = 0.f;
 #pragma unroll
                 for (int g2 = 0; g2 < 16; g2++) t += red[g2 * 16 + tid];
-                hb.DB2[tid] += t;
+                hb.DB2[tid] = odb2 + t;
             }
+            HB_STAMP(6);                                             // DB2 accumulated (rider 0)
         }
     }
+    HB_FLUSH(8, 3);
 }
 
 } // namespace

@@ -124,6 +124,7 @@ int head_bwd_launch(float *X2, const float *W2, float *P, const float *TGT, floa
     HeadBwd hb = { P, TGT, W2, mc2.m1, X2, DW2, DB2, mc2.d1, Y2, DB1, N, EA, EB, train ? 1 : 0, (int)(a1 + a2 + nr), gate, mc2.m2, mc2.d2, mc1, g.d_zero };
 #ifdef T4K_LAB
     { const char *e = getenv("T4K_HB_LAB"); hb.lab = e ? atoi(e) : 0; }    // timing ablations (wrong results): see the kernel's HB_LAB bits
+    { const char *e = getenv("T4K_HB_PROF_PTR"); hb.prof = e ? reinterpret_cast<unsigned long long *>(strtoull(e, nullptr, 16)) : nullptr; }   // role stamps: a device address, hex, of HB_PROF_WORDS x 8 bytes per workgroup (tools/experiments/head_bwd_lab.py)
 #endif
     launch_lds<k_head_bwd_l32>(dim3((unsigned)(a1 + a2 + nr)), dim3(256), head_bwd_lds(N, EA, EB), hs, q1, q2, (int)a1, (int)nr, slots, pslots, epoch, hb);
     T4K_LAUNCH_CHECK();
