@@ -30,9 +30,9 @@ struct HeadBwd {
     int N, EA, EB, train, nwg; int *sync;
     const float *MSKB; float *Y1B;     // a second mask layer between the linear layers (`leakyrelu dropout`): dY1 = dX2 * MASK * MSKB, Y1 keeps the first product, Y1B the second
     MaskChain mc1;                      // mask multiplies behind the big layer's dX1 (the run in front of it), as linear_bwd_dual
-    const float *Z;                     // 4 KiB of zeros: source of DMA lanes past the K range / the matrix edge
+    const float *Z;                     // 4 KiB of zeros: source of DMA lanes past the K range / the matrix edge (the operand loads are range-checked buffer loads and need none)
 #ifdef T4K_LAB
-    int lab;                            // LAB build only: timing ablations (wrong results), the bits of T4K_HB_LAB, read at run time
+    int lab;                            // LAB build only: timing ablations (wrong results; bit 128, the other order of the roles, right ones), the bits of T4K_HB_LAB, read at run time
     unsigned long long *prof;           // LAB build only: role stamps, HB_PROF_WORDS per workgroup (T4K_HB_PROF_PTR, tools/experiments/head_bwd_lab.py); nullptr: none
 #endif
 };
@@ -77,8 +77,13 @@ __device__ __forceinline__ unsigned long long hb_wallclock() {
 #endif
 constexpr int HB_CW = 4;                // columns of the head's input per rider workgroup (k_linsmall_bwd_cols: LSC_CW)
 constexpr int HB_AP = 33;               // pitch of the dY1 tile in LDS
-// workgroups [0, a1): dW1 tiles (read X1, never wait) | [a1, a1 + nr): riders - the store rider, then the column riders | the rest: dX1 tiles (write X1 in place,
-// wait for the dW1 tiles of their column only).  slots == nullptr: a frozen layer (a1 == 0) - nothing to wait for.
+// workgroups [0, a1): dW1 tiles (read X1, never wait) | [a1, nwg - nr): dX1 tiles (write X1 in place, wait for the dW1 tiles of their column only) | the last
+// nr: riders - the store rider, then the column riders.  (T4K_HB_RIDERS_LAST 0, the order up to round 10: the riders between the two tile kinds; the LAB
+// build's bit 128 takes the other order at run time.)  Correctness does not depend on the order: admission keeps every workgroup resident, the gate reads
+// tagged slots, pslots is indexed by workgroup.  slots == nullptr: a frozen layer (a1 == 0) - nothing to wait for.
+#ifndef T4K_HB_RIDERS_LAST
+#define T4K_HB_RIDERS_LAST 1
+#endif
 __global__ void __launch_bounds__(256) k_head_bwd_l32(GemmP p1, GemmP p2, int a1, int nr, unsigned *slots, unsigned *pslots, unsigned epoch, HeadBwd hb) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     typedef __attribute__((address_space(3))) const float lds_f;
@@ -92,11 +97,14 @@ __global__ void __launch_bounds__(256) k_head_bwd_l32(GemmP p1, GemmP p2, int a1
     const auto HB_LAB = [=](int bit) { return (lab & bit) != 0; };
     HB_LABX(unsigned long long hb_ts[16] = {}; int hb_spins = 0;)
     HB_WALL(14); HB_STAMP(0);
-    if (bx < a1 || bx >= a1 + nr) {
+    // the roles over blockIdx.x, a pure function of bx: the workgroups dispatched last are the ones that double up on a CU (274 on 256 at the flagship shape)
+    const bool riders_last = (T4K_HB_RIDERS_LAST != 0) != HB_LAB(128);
+    const int r0 = riders_last ? hb.nwg - nr : a1;                   // the store rider; the column riders behind it
+    const bool first = bx < a1, is_tile = first || (riders_last ? bx < r0 : bx >= a1 + nr);
+    if (is_tile) {
         // ---------------------------------------------------------------- GEMM tile
         if (HB_LAB(2)) return;
-        const bool first = bx < a1;
-        const int tile = first ? bx : bx - a1 - nr, tiles_n = p1.tiles_n;        // both GEMMs have the same column tiling (E1)
+        const int tile = first ? bx : bx - (riders_last ? a1 : a1 + nr), tiles_n = p1.tiles_n;        // both GEMMs have the same column tiling (E1)
         const int tm = tile / tiles_n, tn = tile - tm * tiles_n, m0 = tm * 32, n0 = tn * 32;
         const int M = first ? EA : N, Nn = p2.N, K = first ? N : EA;   // dW1: M = EA, K = N;  dX1: M = N, K = EA;  both: B = [K][Nn] rows (X1 / W1)
         const float *pB = first ? p1.B : p2.B;
@@ -123,24 +131,37 @@ __global__ void __launch_bounds__(256) k_head_bwd_l32(GemmP p1, GemmP p2, int a1
                 }
             }
         }
-        // Operand loads (round 10): straight-line code.  Every bound picks the ADDRESS - the element, or a word of the zero strip hb.Z - and no load is skipped,
-        // so the requests of a block go out together and the first MFMA waits for them once.  `ok ? P[i] - T[i] : 0.f` compiled to a branch per element with
-        // the wait for both loads INSIDE it: one memory round trip per P - T pair, five in a row at EB = 10 (profiles/LAB_NOTES.md 16).
-        const float *const Zp = hb.Z;
+        // Operand loads (round 11): range-checked buffer loads.  Round 10 made them straight-line code by letting every bound pick the ADDRESS (the element,
+        // or a word of the zero strip hb.Z); the selects and the 64-bit address arithmetic of that form were ~1 300 instructions per wave in front of the
+        // first MFMA (profiles/LAB_NOTES.md 16, 17).  Here a tensor is a buffer descriptor of its logical size, built from kernel arguments and blockIdx-derived
+        // scalars only, and a lane keeps ONE 32-bit byte offset per operand family: what lies past the tensor's END reads 0.0f from the hardware's range check,
+        // and every bound that is not the tensor's end (a column bound inside a row, a block past nblk, an ablation) turns the lane's offset into HB_OOR once
+        // per family.  The range check covers the lane's offset and the instruction's immediate, NOT the scalar offset (tools/experiments/buf_lds_probe.hip),
+        // so the run-time row strides go into the lane's offset (one v_add per request) and the scalar offset stays 0.  No load is skipped: the requests of a
+        // block go out together and the first MFMA waits for them once (`ok ? P[i] - T[i] : 0.f` with the load inside the branch made one round trip per pair).
+        // HB_OOR: the lane offsets are unsigned.  Under head_bwd_ok's limits (N, EA <= 256, EB <= 16, at most 768 workgroups, so E1 is a few thousand) the largest
+        // descriptor is N E1 4 or EA E1 4 bytes, a few MiB, and what is added to a lane's offset is at most 3 erow, 15 mrow, 14 mrow or 56 bytes: 2^31 + that neither
+        // falls inside a descriptor nor wraps.  The bound rests on those admission limits - widen them and revisit it.
+        constexpr unsigned HB_OOR = 0x80000000u;
+        const auto hb_srd = [](const float *base, unsigned bytes) { return __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(base), 0, (int)(base ? bytes : 0u), 0x00020000); };   // (a null base: 0 bytes, every lane reads 0.0f)
+        const auto hb_ld = [](__amdgpu_buffer_rsrc_t rs, unsigned vo) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, (int)vo, 0, 0)); };
         // epilogue operands, requested with everything else: what dW1 accumulates onto | the first mask behind dX1, and the second mask
         const int gn = n0 + l31;
         const float *const e1p = first ? pO : hb.mc1.d1 ? hb.mc1.m1 : nullptr, *const e2p = (!first && hb.mc1.d2) ? hb.mc1.m2 : nullptr;
         float e1[4], e2[4];
+        {
+            const unsigned ebytes = (unsigned)M * (unsigned)Nn * 4u, erow = (unsigned)Nn * 4u;       // [EA][E1] (dW1's accumuland) | [N][E1] (the masks behind dX1): a row gm >= M lies past the end
+            const auto r1 = hb_srd(e1p, ebytes), r2 = hb_srd(e2p, ebytes);
+            const unsigned evo = gn < Nn ? ((unsigned)(m0 + 8 * w + 4 * h) * (unsigned)Nn + (unsigned)gn) * 4u : HB_OOR;   // row gm = m0 + q + 8 w + 4 h of the epilogue below
 #pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const int r = 4 * w + q, gm = m0 + (r & 3) + 8 * (r >> 2) + 4 * h;
-            const bool ok = gm < M && gn < Nn;
-            const long z = (long)gm * Nn + gn;
-            e1[q] = *(ok && e1p ? e1p + z : Zp);
-            e2[q] = *(ok && e2p ? e2p + z : Zp);
+            for (int q = 0; q < 4; q++) { e1[q] = hb_ld(r1, evo + q * erow); e2[q] = hb_ld(r2, evo + q * erow); }
         }
         // 2. operands of the dY1 blocks this wave prepares (blocks w and w + 4 of the tile's k range), in MFMA layout
         //    dW1 tile: block = 32 samples, the tile's 32 columns e of dY1;   dX1 tile: block = 32 columns e, the tile's 32 samples
+        const unsigned mbytes = (unsigned)N * (unsigned)EA * 4u, mrow = (unsigned)EA * 4u;
+        const auto rP = hb_srd(hb.P, (unsigned)N * (unsigned)EB * 4u), rT = hb_srd(hb.T, (unsigned)N * (unsigned)EB * 4u);
+        const auto rW = hb_srd(hb.W2, (unsigned)EB * (unsigned)EA * 4u), rM = hb_srd(hb.MASK, mbytes);
+        const int jl = EB - h;                                       // MFMA slot s of this lane is k index j = 2 s + h: a term of the sum while 2 s < jl
         float av[2][8], bv[2][8], mk[2][16];
 #pragma unroll
         for (int t = 0; t < 2; t++) {
@@ -151,35 +172,38 @@ __global__ void __launch_bounds__(256) k_head_bwd_l32(GemmP p1, GemmP p2, int a1
             if (t == 0 || nblk > 4) {                                // (no wave has a second block up to K = 128)
                 const int blk = w + 4 * t;
                 const int arow = first ? 32 * blk + l31 : m0 + l31;  // sample of this lane's A values (P - T): a dX1 tile's second block reads the first one's again
-                const int bcl = first ? m0 + l31 : 32 * blk + l31;   // column e of this lane's B values (W2): a dW1 tile's likewise
-                const bool on = blk < nblk, aok = on && arow < N, bok = on && bcl < EA;
+                const int bcl = first ? m0 + l31 : 32 * blk + l31;   // column e of this lane's B values (W2): a dW1 tile's likewise; the column of its mask values too
+                const int mr0 = first ? 32 * blk : m0;               // first sample of the block's mask values
+                const bool on = blk < nblk, lon = on && !HB_LAB(8);
+                // P / T: [N][EB], the slots 8 s bytes apart in the immediate.  A slot j >= EB of a used s (odd EB, h == 1: the next row's first element, no
+                // end of the tensor) is dropped from the VALUE below; W2 [EB][EA]: row j >= EB lies past the end
+                const unsigned avo = lon && arow < N ? ((unsigned)arow * (unsigned)EB + (unsigned)h) * 4u : HB_OOR;
+                const unsigned bvo = lon && bcl < EA ? ((unsigned)h * (unsigned)EA + (unsigned)bcl) * 4u : HB_OOR;
+                // mask: [N][EA], value r of the accumulator layout is sample mr0 + (r & 3) + 8 (r >> 2) + 4 h: a sample >= N lies past the end
+                const unsigned mvo = on && bcl < EA && !HB_LAB(64) ? ((unsigned)(mr0 + 4 * h) * (unsigned)EA + (unsigned)bcl) * 4u : HB_OOR;
 #pragma unroll
                 for (int s = 0; s < 8; s++) {
-                    const int j = 2 * s + h;
-                    const bool jk = j < EB && !HB_LAB(8);
-                    const long ia = (long)arow * EB + j;
-                    av[t][s] = *(aok && jk ? hb.P + ia : Zp) - *(aok && jk ? hb.T + ia : Zp);
-                    bv[t][s] = *(bok && jk ? hb.W2 + (long)j * EA + bcl : Zp);
+                    const float pv = hb_ld(rP, avo + 8u * s), tv = hb_ld(rT, avo + 8u * s);
+                    av[t][s] = 2 * s < jl ? pv - tv : 0.f;
+                    bv[t][s] = hb_ld(rW, bvo + 2u * s * mrow);
                 }
 #pragma unroll
-                for (int r = 0; r < 16; r++) {
-                    const int ro = (r & 3) + 8 * (r >> 2) + 4 * h;
-                    const int n = first ? 32 * blk + ro : m0 + ro, e = first ? m0 + l31 : 32 * blk + l31;
-                    mk[t][r] = *(on && n < N && e < EA && !HB_LAB(64) ? hb.MASK + ((long)n * EA + e) : Zp);
-                }
+                for (int r = 0; r < 16; r++) mk[t][r] = hb_ld(rM, mvo + (unsigned)((r & 3) + 8 * (r >> 2)) * mrow);
             }
         }
         if (hb.MSKB) {                                               // a second mask layer: its values multiply the first one's, one more round trip
+            const auto rMB = hb_srd(hb.MSKB, mbytes);
 #pragma unroll
             for (int t = 0; t < 2; t++) {
                 const int blk = w + 4 * t;
                 if (blk < nblk) {
+                    const int bcl = first ? m0 + l31 : 32 * blk + l31, mr0 = first ? 32 * blk : m0;
+                    const unsigned mvo = bcl < EA ? ((unsigned)(mr0 + 4 * h) * (unsigned)EA + (unsigned)bcl) * 4u : HB_OOR;
+                    float m2[16];
 #pragma unroll
-                    for (int r = 0; r < 16; r++) {
-                        const int ro = (r & 3) + 8 * (r >> 2) + 4 * h;
-                        const int n = first ? 32 * blk + ro : m0 + ro, e = first ? m0 + l31 : 32 * blk + l31;
-                        mk[t][r] *= *(n < N && e < EA ? hb.MSKB + ((long)n * EA + e) : Zp);
-                    }
+                    for (int r = 0; r < 16; r++) m2[r] = hb_ld(rMB, mvo + (unsigned)((r & 3) + 8 * (r >> 2)) * mrow);
+#pragma unroll
+                    for (int r = 0; r < 16; r++) mk[t][r] *= m2[r];
                 }
             }
         }
@@ -197,11 +221,11 @@ __global__ void __launch_bounds__(256) k_head_bwd_l32(GemmP p1, GemmP p2, int a1
                     d = __builtin_amdgcn_mfma_f32_32x32x2f32(av[t][s], bv[t][s], d, 0, 0, 0);
                     if (t == 0 && s == 0) HB_STAMP(2);               // first dY1 MFMA issued: its operands have landed
                 }
+                // value r of the accumulator is row (r & 3) + 8 (r >> 2) + 4 h, column l31 of the block; a dW1 tile keeps it sample-major, a dX1 tile
+                // column-major: one base and one stride (`first ? .. : ..` per element compiled to two scalar branches round every store)
+                const int abase = first ? (32 * blk + 4 * h) * HB_AP + l31 : (32 * blk + l31) * HB_AP + 4 * h, astep = first ? HB_AP : 1;
 #pragma unroll
-                for (int r = 0; r < 16; r++) {
-                    const int ro = (r & 3) + 8 * (r >> 2) + 4 * h;
-                    Ad[first ? (32 * blk + ro) * HB_AP + l31 : (32 * blk + l31) * HB_AP + ro] = d[r] * mk[t][r];
-                }
+                for (int r = 0; r < 16; r++) Ad[abase + ((r & 3) + 8 * (r >> 2)) * astep] = d[r] * mk[t][r];
             }
         }
         HB_STAMP(3);                                                 // dY1 blocks in LDS
@@ -303,7 +327,7 @@ __global__ void __launch_bounds__(256) k_head_bwd_l32(GemmP p1, GemmP p2, int a1
         HB_FLUSH(12, first ? 0 : 1);
         return;
     }
-    if (bx == a1) {
+    if (bx == r0) {
         // ---------------------------------------------------------------- store rider: `out -= target` in place (+ its copy), once every other workgroup holds P and T
         const int tot = N * EB;
         for (int i = tid; i < tot; i += 256) lds[i] = hb.P[i] - hb.T[i];
@@ -332,7 +356,7 @@ __global__ void __launch_bounds__(256) k_head_bwd_l32(GemmP p1, GemmP p2, int a1
     // -------------------------------------------------------------------- column riders: k_linsmall_bwd_cols's slice of HB_CW columns of the head's input
     if (HB_LAB(1)) return;
     constexpr int CW = HB_CW, ZI = 8;
-    const int cb = bx - a1 - 1, c0 = cb * CW, cw = min(CW, EA - c0);
+    const int cb = bx - r0 - 1, c0 = cb * CW, cw = min(CW, EA - c0);
     float *dys = lds, *Ws = dys + N * EB, *Xs = Ws + EB * CW, *red = Xs + N * CW;       // dY2 [N][EB], W2 slice [EB][CW], X2 slice [N][CW] (then the dY1 slice), partial sums [4][EB * CW] / [32][CW]
     const int nout = EB * CW, G = min(4, 256 / nout);               // thread groups splitting the batch of one dW2 output (contiguous ranges, summed in order)
     float mk[ZI], mkb[ZI];

@@ -126,6 +126,7 @@ int head_bwd_launch(float *X2, const float *W2, float *P, const float *TGT, floa
     { const char *e = getenv("T4K_HB_LAB"); hb.lab = e ? atoi(e) : 0; }    // timing ablations (wrong results): see the kernel's HB_LAB bits
     { const char *e = getenv("T4K_HB_PROF_PTR"); hb.prof = e ? reinterpret_cast<unsigned long long *>(strtoull(e, nullptr, 16)) : nullptr; }   // role stamps: a device address, hex, of HB_PROF_WORDS x 8 bytes per workgroup (tools/experiments/head_bwd_lab.py)
 #endif
+    // a1 dW1 tiles, a2 dX1 tiles, then the nr riders (the kernel maps blockIdx.x to the roles: gemm_head_bwd.h, T4K_HB_RIDERS_LAST)
     launch_lds<k_head_bwd_l32>(dim3((unsigned)(a1 + a2 + nr)), dim3(256), head_bwd_lds(N, EA, EB), hs, q1, q2, (int)a1, (int)nr, slots, pslots, epoch, hb);
     T4K_LAUNCH_CHECK();
     return T4K_OK;

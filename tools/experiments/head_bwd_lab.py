@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Time t4k_mlp_head_bwd (k_head_bwd_l32) alone, with the LAB build's ablation bits (T4K_HB_LAB, wrong results - timing only):
    T4K_LIB=tensorforth_amd/libt4hip_lab.so T4K_HB_LAB=1 python tools/experiments/head_bwd_lab.py [N E1 EA EB]
-   bits: 1 no column riders, 2 no tiles, 4 no target-store counter, 8 tiles skip P/T/W2 loads, 64 tiles skip mask loads, 16 tiles stop behind the prologue, 32 no in-place gate
+   bits: 1 no column riders, 2 no tiles, 4 no target-store counter, 8 tiles skip P/T/W2 loads, 64 tiles skip mask loads, 16 tiles stop behind the prologue, 32 no in-place gate,
+         128 the OTHER order of the roles over blockIdx.x (right results: riders between the tile kinds where the library puts them last, and the reverse)
 and print the stamped timeline of one launch of a back-to-back train (LAB build; csrc/gemm_head_bwd.h, HB_STAMP):
    T4K_LIB=tensorforth_amd/libt4hip_lab.so python tools/experiments/head_bwd_lab.py --stamps [--r09] [N E1 EA EB]
 (--r09: the record layout of the round-9 kernel with the stamps added - its riders stored dX2 / dY1 before they accumulated DW2)
@@ -61,8 +62,12 @@ cu_key = [(int(rec[i, 19]) & 15, (int(rec[i, 18]) >> 8) & 0xff) for i in range(n
 share = {}
 for i, c in enumerate(cu_key): share.setdefault(c, []).append(i)
 shared = {i for v in share.values() if len(v) > 1 for i in v}
+# a workgroup's role is word 17 of its record (0 dW1 tile, 1 dX1 tile, 2 store rider, 3 column rider), its number within the role the order of
+# blockIdx.x: the tables read either order of the roles
+by_role = {r: [i for i in range(nwg) if role[i] == r] for r in range(4)}
+rank = {i: n for idx in by_role.values() for n, i in enumerate(idx)}
 def name_of(i):
-    return "dW1 tile %d" % i if i < a1 else "store rider" if i == a1 else "column rider %d" % (i - a1 - 1) if i < a1 + nr else "dX1 tile %d" % (i - a1 - nr)
+    return ("dW1 tile %d", "dX1 tile %d", "store rider", "column rider %d")[int(role[i])].replace("%d", str(rank[i]))
 def table(title, idx, links):
     idx = list(idx)
     if not idx: return
@@ -78,13 +83,16 @@ def table(title, idx, links):
         print("  %-36s %9.0f %9.0f %9.0f" % ("-> " + links[j], d.mean(), d.max(), (r[:, j] - r[:, 0]).mean()))
     sp = rec[idx, 16]
     if sp.any() or title.startswith(("dX1", "store")): print("  failed looks of the wait: avg %.2f, max %d, workgroups with any %d" % (sp.mean(), sp.max(), (sp > 0).sum()))
-print("k_head_bwd_l32 stamped: N=%d E1=%d EA=%d EB=%d, %d workgroups (%d dW1 tiles, %d riders, %d dX1 tiles) on %d CUs, %d of them on a CU that holds two or more" % (
-    N, E1, EA, EB, nwg, a1, nr, a2, len(share), len(shared)))
-print("launch, first start to last end on the 100 MHz clock: %.2f us" % end_us.max())
-tiles1, tiles2 = range(0, a1), range(a1 + nr, nwg)
-table("dW1 tiles", tiles1, LINKS["tile"]); table("dX1 tiles", tiles2, LINKS["tile"])
-table("store rider", [a1], LINKS["store rider"])
-table("column riders 1 ..", range(a1 + 2, a1 + nr), LINKS["column rider"]); table("column rider 0 (carries dB2)", [a1 + 1], LINKS["column rider"])
+# the order of the roles, from where the store rider's record sits (no such record, as under an ablation that drops it: not known)
+riders_last = None if not by_role[2] else by_role[2][0] == nwg - nr
+counts = "%d dW1 tiles, %d dX1 tiles, %d riders" % (a1, a2, nr) if riders_last else "%d dW1 tiles, %d riders, %d dX1 tiles" % (a1, nr, a2)
+print("k_head_bwd_l32 stamped: N=%d E1=%d EA=%d EB=%d, %d workgroups (%s) on %d CUs, %d of them on a CU that holds two or more" % (
+    N, E1, EA, EB, nwg, counts, len(share), len(shared)))
+print("launch, first start to last end on the 100 MHz clock: %.2f us; roles over blockIdx.x: %s" % (
+    end_us.max(), "not known (no store rider's record)" if riders_last is None else "riders last" if riders_last else "riders between the tile kinds"))
+table("dW1 tiles", by_role[0], LINKS["tile"]); table("dX1 tiles", by_role[1], LINKS["tile"])
+table("store rider", by_role[2], LINKS["store rider"])
+table("column riders 1 ..", by_role[3][1:], LINKS["column rider"]); table("column rider 0 (carries dB2)", by_role[3][:1], LINKS["column rider"])
 order = sorted(range(nwg), key=lambda i: -end_us[i])
 print("\nlast to end:")
 for i in order[:8]:
