@@ -795,7 +795,11 @@ int t4k_opt_chunked(int kind, const t4k_param_rec *tab_dev, int n_tensors, int n
  * optimizer inside the same launch - t4k_conv_stack_bwd(train | 4) leaves its per-workgroup dF | dB partial rows unfolded, and when
  * t4k_opt_step is the next entry point the fold rides in the update (one launch instead of two, bit-identical).  Any OTHER entry point
  * called in between runs the stand-alone fold first, so a caller that reads the gradient tensors, accumulates a second backward or
- * all-reduces the slab before the optimizer sees what the undeferred path leaves.  tab_host: the caller's host copy of tab_dev. */
+ * all-reduces the slab before the optimizer sees what the undeferred path leaves.  tab_host: the caller's host copy of tab_dev.
+ * The fold rides only when every pending segment is a whole DG tensor of the table (same pointer, same n), tab_host is given, the table has at most
+ * 64 records and `s` is the backward's stream; otherwise the stand-alone fold runs first, on the BACKWARD's stream, and the plain step follows on `s`.
+ * THE CALLER'S OBLIGATION: call it on the stream of the backward that deferred the fold.  On another stream the fold and the update are two launches on
+ * two streams and nothing in the library orders them. */
 int t4k_opt_step(int kind, const t4k_param_rec *tab_dev, const t4k_param_rec *tab_host, int n_tensors, int n_chunks,
                  float lr, float b1, float b2, float wd, t4k_stream_t s);
 /* the data-parallel form: with the one-shot exchange connected (t4k_xchg_connect, world > 1) every gradient element is summed over all

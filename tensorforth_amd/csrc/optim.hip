@@ -12,7 +12,9 @@ namespace {
 // the order of the reference's expressions as the oracle evaluates them (k_sgd / k_adam / k_adamw, nmath.cu:419-472; oracle built with
 // -ffp-contract=off).  Left to the compiler (-ffp-contract=fast) the same source contracted differently in different kernels - the fold-inside-
 // optimizer launch and the chunked launch must agree bit for bit (tests/test_gpu_deferred.py) - and differently from the oracle; spelled out,
-// every kernel that updates a parameter produces the oracle's bits.
+// every kernel that updates a parameter produces the oracle's bits.  The root is __builtin_sqrtf, which the compiler expands to the correctly rounded
+// sequence (v_sqrt_f32 plus its correction step); __fsqrt_rn is, without OCML_BASIC_ROUNDED_OPERATIONS, the bare v_sqrt_f32 - one ulp off now and then,
+// which Adam's weights showed where v' is small and the quotient cancels against the weight (tests/test_gpu_optim_sweep.py pins the bits).
 __device__ __forceinline__ void sgd1(float &g, float &dg, float &m, int Nw, float lr, float b, bool mom) {
     const float d = __fdiv_rn(dg, (float)Nw);              // Nw = parameter tensor's N, not batch (quirk a-19)
     if (!mom) g = __fsub_rn(g, __fmul_rn(lr, d));
@@ -23,14 +25,14 @@ __device__ __forceinline__ void adam1(float &g, float &dg, float &m, float &v, f
     const float d = dg;
     m = __fadd_rn(__fmul_rn(b1, m), __fmul_rn(__fsub_rn(1.0f, b1), d));
     v = __fadd_rn(__fmul_rn(b2, v), __fmul_rn(__fmul_rn(__fsub_rn(1.0f, b2), d), d));
-    g = __fsub_rn(g, __fdiv_rn(__fmul_rn(lr, m), __fadd_rn(__fsqrt_rn(v), DU_EPS)));   // no bias correction, eps outside sqrt
+    g = __fsub_rn(g, __fdiv_rn(__fmul_rn(lr, m), __fadd_rn(__builtin_sqrtf(v), DU_EPS)));   // no bias correction, eps outside sqrt
     dg = 0.0f;
 }
 __device__ __forceinline__ void adamw1(float &g, float &dg, float &m, float &v, float lr, float b1, float b2, float wd) {
     const float d = dg;
     m = __fadd_rn(__fmul_rn(b1, m), __fmul_rn(__fsub_rn(1.0f, b1), d));
     v = __fadd_rn(__fmul_rn(b2, v), __fmul_rn(__fmul_rn(__fsub_rn(1.0f, b2), d), d));
-    g = __fsub_rn(g, __fmul_rn(lr, __fsub_rn(__fdiv_rn(m, __fadd_rn(__fsqrt_rn(v), DU_EPS)), __fmul_rn(wd, d))));
+    g = __fsub_rn(g, __fmul_rn(lr, __fsub_rn(__fdiv_rn(m, __fadd_rn(__builtin_sqrtf(v), DU_EPS)), __fmul_rn(wd, d))));
     dg = 0.0f;
 }
 
