@@ -92,9 +92,27 @@ unsigned long long t4k_launch_count(void);
  * GEMM sweep asserts it for every shape of its table.  "l32/w8/rst", "pair", "nn_plain", "plain_any", "plain_ragk", "plain128", "plain128/ragk",
  * "plain128/bk32", "plain256", "glds8<128>", "glds8<64,ragk>", "mfma<128,128,32,vec,full>", "mfma<64,64,64,vec,skew>", "mfma<64,64,32>", "k0"
  * (K = 0: O = beta O), "none" (M or N = 0); "xN" behind it for N split-K slabs and "+fold" when the fold launch followed them.  Valid until the
- * next call of this function.  Plain, unsynchronised stores by the launch wrappers of gemm.hip: read it on the thread that issued the product, right
- * behind the call - a product issued from a second host thread, or a later entry that reaches the same wrappers, overwrites it. */
+ * next call of this function.  gemm_launch keeps the rung, N and the fold of the plan it ran in one plain, unsynchronised store: read it on the thread
+ * that issued the product, right behind the call - a product issued from a second host thread, or a later entry that reaches gemm_launch, overwrites it. */
 const char *t4k_gemm_last_plan(void);
+/* The plan gemm_launch makes for one product, on the host alone: the same planner (csrc/gemm.hip gemm_plan), nothing launched, no device and no
+ * t4k_init needed.  flags says what the planner cannot see from the extents: */
+enum { T4K_GP_A16 = 1, T4K_GP_B16 = 2,   /* A, B on 16 bytes */
+       T4K_GP_EPILOGUE = 4,              /* (alpha, beta) != (1, 0) */
+       T4K_GP_BIAS = 8,                  /* a bias row */
+       T4K_GP_RIDER = 16,                /* an activation epilogue or a rider of the last launch is asked for (the linear layers) */
+       T4K_GP_DEFER = 32,                /* the caller folds split-K slabs itself (t4k_mlp_head_fwd) */
+       T4K_GP_LANE = 64,                 /* a stream other than the default one */
+       T4K_GP_CAPTURING = 128,           /* the stream is being captured into a graph */
+       T4K_GP_GATES_OFF = 256 };         /* t4k_gates_enable(0) */
+/* cs_rows != 0: a column-sum request over that many rows (the bias gradient offered to a weight-gradient product); cu: the CU count to plan for, 0 = the
+ * library's current one (256 before t4k_init); ws_bytes: the stream's workspace, 0 = the library's (64 MiB).  The zero block and the tickets of an
+ * initialised library are taken as present.
+ * text: what t4k_gemm_last_plan() reports after that call, byte for byte;
+ * out = { split-K slabs, K depth of a slab (of a sliver workgroup; K itself on the lean kernels; 0 for "none" and "k0"), kernel launches,
+ *         a rider would ride (in the product's launch or in its fold), the column sums ride, the slabs are left to the caller }.
+ * NULL text or out, cu < 0 or ws_bytes < 0: T4K_ERR_ARG; a negative extent or C < 1: T4K_ERR_ARG as t4k_gemm. */
+int t4k_gemm_plan(int M, int N, int K, int C, int tA, int tB, unsigned flags, int cs_rows, int cu, long ws_bytes, char text[64], int out[6]);
 /* The engine decisions of the last convolution entry of this process (t4k_conv2d_fwd / _fwd2 / _bn_fwd / _bn_block_fwd / _block_fwd / _bwd / _bwd2,
  * t4k_dconv2d_fwd / _bwd), in launch order, as one static string of blank-separated tokens: test hook - the conv sweep asserts it for every row
  * of its table.  Forward: "few<G,CH,VW>", "thin" ("+copy": the layer-0 copy leaves from the same launch, "+stat": the batch-norm sums ride),

@@ -36,6 +36,44 @@
 namespace {
 
 // ------------------------------------------------------------------------------------------
+// planner -> plan -> launch.  gemm_plan (in front of gemm_launch, below) answers a GemmAsk in a GemmEnv with a GemmPlan and launches nothing;
+// gemm_launch and the launch wrappers read the plan and decide nothing.  GemmRung is the one list of rungs: a value per string of
+// t4k_gemm_last_plan, in the order of rung_text[].
+enum GemmRung : int { GR_UNSET = 0, GR_NONE, GR_K0, GR_L32_W4, GR_L32_W4_RST, GR_L32_W8, GR_L32_W8_RST, GR_PAIR, GR_NN_PLAIN, GR_PLAIN_ANY, GR_PLAIN_RAGK,
+                      GR_PLAIN128, GR_PLAIN128_RAGK, GR_PLAIN128_BK32, GR_PLAIN256, GR_GLDS8_128, GR_GLDS8_64, GR_GLDS8_128_RAGK, GR_GLDS8_64_RAGK,
+                      GR_MFMA128_FULL, GR_MFMA128_SKEW, GR_MFMA128, GR_MFMA64_32, GR_MFMA64_FULL, GR_MFMA64_SKEW, GR_COUNT };
+const char *const rung_text[GR_COUNT] = { "", "none", "k0", "l32/w4", "l32/w4/rst", "l32/w8", "l32/w8/rst", "pair", "nn_plain", "plain_any", "plain_ragk",
+                      "plain128", "plain128/ragk", "plain128/bk32", "plain256", "glds8<128>", "glds8<64>", "glds8<128,ragk>", "glds8<64,ragk>",
+                      "mfma<128,128,32,vec,full>", "mfma<128,128,32,vec,skew>", "mfma<128,128,32>", "mfma<64,64,32>", "mfma<64,64,64,vec,full>", "mfma<64,64,64,vec,skew>" };
+// the question: one product as its caller describes it
+struct GemmAsk {
+    int M, N, K, C, tA, tB;
+    bool a16, b16;          // A, B on 16 bytes
+    bool plain;             // (alpha, beta) == (1, 0)
+    bool bias;
+    bool riders;            // an activation epilogue or a FoldRider is asked for
+    bool defer;             // the caller folds split slabs itself
+    bool cs; int cs_rows, cs_E;   // a column-sum request and its extents
+};
+// what gemm_launch reads from State and the stream
+struct GemmEnv { int cu; size_t ws_bytes; bool d_zero, d_sync, gates; int lane; bool capturing; };
+enum { RIDE_NONE = 0, RIDE_LAUNCH, RIDE_FOLD };
+struct GemmPlan {
+    GemmRung rung = GR_NONE;
+    int tiles_m = 0, tiles_n = 0;
+    unsigned gx = 0, gy = 1, gz = 1;     // the grid of the product's launch, column-sum workgroups included (a sliver's copy rider adds its own at launch)
+    int nsplit = 1, kchunk = 0;
+    bool w8 = false, rst = false;        // slivers: 8 waves (k-groups) per workgroup; a wave walks more than two blocks
+    int xmap = 0;
+    bool pow2 = false, swap = false;     // k_gemm_nn_plain: shift / mask tile prologue; tile order with M and N exchanged
+    bool epi = false;                    // lean kernels: alpha / beta / bias epilogue
+    bool cs_rides = false; unsigned cs_wgs = 0;
+    int riders = RIDE_NONE;              // where an activation / mask-chain / copy rider is applied: the product's launch, the fold, nowhere
+    bool deferred = false, fold = false;
+    int launches = 0;
+};
+
+// ------------------------------------------------------------------------------------------
 // 64x64 interior tiles, direct-to-LDS staging: global_load_lds_dwordx4 (LDS-DMA, no VGPR round
 // trip, no ds_write pass), 3 LDS stage buffers, loads two stages ahead, counted vmcnt waits and
 // raw s_barrier so the DMA of later stages stays in flight across barriers.  The DMA writes LDS
@@ -509,29 +547,25 @@ __global__ void __launch_bounds__(512) k_gemm_nn_plain(PlainP p) {
     }
 }
 template <bool AKC, bool BKC, bool EPI, bool PAIR = false, bool RAGK = false>
-void launch_plain_(const PlainP &q, int tmq, int tnq, unsigned gx, hipStream_t s) {
+void launch_plain_(const PlainP &q, const GemmPlan &pl, hipStream_t s) {
     constexpr size_t lds_bytes = (size_t)2 * 128 * 128 * sizeof(float);
-    const bool pow2 = gemm_lab().fastpro && (tmq & (tmq - 1)) == 0 && (tnq & (tnq - 1)) == 0 && tmq >= 4 && (tmq * tnq) % 32 == 0;
-    const dim3 grid(gx, PAIR ? 2 : 1);
-    if (pow2) launch_lds<k_gemm_nn_plain<true, AKC, BKC, EPI, PAIR, RAGK>>(grid, dim3(512), lds_bytes, s, q);
-    else      launch_lds<k_gemm_nn_plain<false, AKC, BKC, EPI, PAIR, RAGK>>(grid, dim3(512), lds_bytes, s, q);
+    const dim3 grid(pl.gx, PAIR ? 2 : 1);
+    if (pl.pow2) launch_lds<k_gemm_nn_plain<true, AKC, BKC, EPI, PAIR, RAGK>>(grid, dim3(512), lds_bytes, s, q);
+    else         launch_lds<k_gemm_nn_plain<false, AKC, BKC, EPI, PAIR, RAGK>>(grid, dim3(512), lds_bytes, s, q);
 }
-void launch_nn_plain(const GemmP &p, dim3 grid, hipStream_t s) {
+void launch_nn_plain(const GemmP &p, const GemmPlan &pl, hipStream_t s) {
     PlainP q{ p.A, p.B, p.O, p.M, p.N, p.K, 1.0f, 0.0f, nullptr, nullptr, nullptr };
-    st().gemm_plan = "nn_plain";
-    launch_plain_<true, false, false>(q, p.M / 64, p.N / 64, grid.x, s);
+    launch_plain_<true, false, false>(q, pl, s);
 }
-// any layout, alpha / beta / bias: interior tiles, K % 128 == 0, unsplit - or, pair = true, K % 256 == 0 and two workgroups per tile (the caller checks)
-void launch_plain_any(const GemmP &p, dim3 grid, int tA, int tB, hipStream_t s, bool pair = false, bool ragk = false) {
+// any layout, alpha / beta / bias: interior tiles, K % 128 == 0, unsplit (GR_PLAIN_ANY) - or a K tail (GR_PLAIN_RAGK) - or K % 256 == 0 and two workgroups per tile (GR_PAIR)
+void launch_plain_any(const GemmP &p, const GemmPlan &pl, int tA, int tB, hipStream_t s) {
     PlainP q{ p.A, p.B, p.O, p.M, p.N, p.K, p.alpha, p.beta, p.bias, p.sync, p.part };
-    q.swap = (gemm_lab().tt_swap && tA && tB) ? 1 : 0;
-    const int tmq = p.M / 64, tnq = p.N / 64;
-    st().gemm_plan = ragk ? "plain_ragk" : pair ? "pair" : "plain_any";
+    q.swap = pl.swap ? 1 : 0;
     with_layout(tA, tB, [&](auto akc, auto bkc, auto epi) {
-        if (ragk)      launch_plain_<akc(), bkc(), epi(), false, true>(q, tmq, tnq, grid.x, s);
-        else if (pair) launch_plain_<akc(), bkc(), epi(), true>(q, tmq, tnq, grid.x, s);
-        else           launch_plain_<akc(), bkc(), epi()>(q, tmq, tnq, grid.x, s);
-    }, p.alpha != 1.0f || p.beta != 0.0f || p.bias);
+        if (pl.rung == GR_PLAIN_RAGK) launch_plain_<akc(), bkc(), epi(), false, true>(q, pl, s);
+        else if (pl.rung == GR_PAIR)  launch_plain_<akc(), bkc(), epi(), true>(q, pl, s);
+        else                          launch_plain_<akc(), bkc(), epi()>(q, pl, s);
+    }, pl.epi);
 }
 
 // Large outputs (>= ~3/4 of the CUs in 128x128 tiles): the lean pipeline on a 128x128 tile.  Same 8 waves = 2 k-groups x 2x2 waves, but every
@@ -727,8 +761,8 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(BK_ ==
         }
 }
 template <bool AKC, bool BKC, bool EPI, bool RAGK = false, int BK_ = 64>
-void launch_plain128_(const PlainP &q, hipStream_t s) {
-    launch_lds<k_gemm_plain128<AKC, BKC, EPI, RAGK, BK_>>(dim3((unsigned)((q.M / 128) * (q.N / 128))), dim3(512), (size_t)2 * 256 * BK_ * sizeof(float), s, q);
+void launch_plain128_(const PlainP &q, unsigned gx, hipStream_t s) {
+    launch_lds<k_gemm_plain128<AKC, BKC, EPI, RAGK, BK_>>(dim3(gx), dim3(512), (size_t)2 * 256 * BK_ * sizeof(float), s, q);
 }
 
 // 256 x 256 tile, 16 waves (round 5): for outputs of at least one such tile per CU (4096^2 and up).  The 128 x 128 kernel pays its stage barrier once per 8 192 MFMA
@@ -853,42 +887,23 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4, 4)
         }
 }
 template <bool AKC, bool BKC, bool EPI>
-void launch_plain256_(const PlainP &q, hipStream_t s) {
-    launch_lds<k_gemm_plain256<AKC, BKC, EPI>>(dim3((unsigned)((q.M / 256) * (q.N / 256))), dim3(1024), (size_t)2 * 512 * 32 * sizeof(float), s, q);
+void launch_plain256_(const PlainP &q, unsigned gx, hipStream_t s) {
+    launch_lds<k_gemm_plain256<AKC, BKC, EPI>>(dim3(gx), dim3(1024), (size_t)2 * 512 * 32 * sizeof(float), s, q);
 }
-void launch_plain128(const GemmP &p, int tA, int tB, hipStream_t s) {
+void launch_plain128(const GemmP &p, const GemmPlan &pl, int tA, int tB, hipStream_t s) {
     PlainP q{ p.A, p.B, p.O, p.M, p.N, p.K, p.alpha, p.beta, p.bias, nullptr, nullptr };
-    const bool epi = p.alpha != 1.0f || p.beta != 0.0f || p.bias, ragk = p.K % 64 != 0;
-    {   // one 256 x 256 tile or more per CU: the 16-wave kernel (T4K_GEMM_PLAIN256: 0 off, 1 default, 2 any grid of whole 256-tiles)
-        const int p256 = gemm_lab().plain256;
-        const long t256 = (long)(p.M / 256) * (p.N / 256), t128 = 4 * t256, cu = st().cu_count;
-        // wave quantisation (ADVICE r5): 4352^2 is 289 tiles of 256^2 - two rounds, the second 13 % full - but 1156 tiles of 128^2 at 90 % fill; the 256-tile pipeline is worth ~4 % per FLOP
-        auto fill_of = [](long tiles_, long cu_) { return (double)tiles_ / (double)(((tiles_ + cu_ - 1) / cu_) * cu_); };
-        if (p256 && p.M % 256 == 0 && p.N % 256 == 0 && p.K % 32 == 0 && p.K >= 64 && (p256 >= 2 || (t256 >= cu && fill_of(t256, cu) * 1.04 > fill_of(t128, cu))) &&
-            (long)p.M * p.K < (1L << 30) && (long)p.N * p.K < (1L << 30)) {
-            st().gemm_plan = "plain256";
-            with_layout(tA, tB, [&](auto akc, auto bkc, auto e) { launch_plain256_<akc(), bkc(), e()>(q, s); }, epi);
-            return;
-        }
-    }
-    // Two co-resident workgroups per CU on 32-deep stages once every CU gets at least two tiles (4096^2 x 1024: 261 -> 254 us, 8192 x 4096 x 512: 282 -> 264 us;
-    // with one tile per CU the doubled barrier count loses: 2048^3 129.5 -> 135.4 us).  K in whole 32s is unragged for this form.  T4K_GEMM_PLAIN128_BK32 = 0 / 1 / 2 (always).
-    const int bk32 = gemm_lab().plain128_bk32;
-    const long tiles = (long)(p.M / 128) * (p.N / 128);
-    const bool two = bk32 && p.K % 32 == 0 && (bk32 >= 2 || tiles >= 2L * st().cu_count);
-    st().gemm_plan = two ? "plain128/bk32" : ragk ? "plain128/ragk" : "plain128";
     with_layout(tA, tB, [&](auto akc, auto bkc, auto e) {
-        if (two)       launch_plain128_<akc(), bkc(), e(), false, 32>(q, s);
-        else if (ragk) launch_plain128_<akc(), bkc(), e(), true>(q, s);
-        else           launch_plain128_<akc(), bkc(), e()>(q, s);
-    }, epi);
+        if (pl.rung == GR_PLAIN256)           launch_plain256_<akc(), bkc(), e()>(q, pl.gx, s);
+        else if (pl.rung == GR_PLAIN128_BK32) launch_plain128_<akc(), bkc(), e(), false, 32>(q, pl.gx, s);
+        else if (pl.rung == GR_PLAIN128_RAGK) launch_plain128_<akc(), bkc(), e(), true>(q, pl.gx, s);
+        else                                  launch_plain128_<akc(), bkc(), e()>(q, pl.gx, s);
+    }, pl.epi);
 }
 
 // RAGK: K with a partial last stage
 template <int BK, bool RAGK = false>
 void launch_glds8(const GemmP &p, dim3 grid, int tA, int tB, hipStream_t s) {
     constexpr size_t lds_bytes = (size_t)((BK >= 128) ? 2 : 3) * 128 * BK * sizeof(float);
-    st().gemm_plan = BK >= 128 ? (RAGK ? "glds8<128,ragk>" : "glds8<128>") : (RAGK ? "glds8<64,ragk>" : "glds8<64>");
     with_layout(tA, tB, [&](auto akc, auto bkc) { launch_lds<k_gemm_glds8<BK, akc(), bkc(), false, RAGK>>(grid, dim3(512), lds_bytes, s, p); });
 }
 
@@ -947,18 +962,14 @@ __global__ void __launch_bounds__(BLK) k_gemm_f64(const float *__restrict__ A, c
 
 template <int BM, int BN, int BK, bool VEC, bool SKEW, bool FULL>
 void launch_variant(const GemmP &p, dim3 grid, int tA, int tB, hipStream_t s) {
-    st().gemm_plan = BM == 128 ? (FULL ? "mfma<128,128,32,vec,full>" : VEC ? "mfma<128,128,32,vec,skew>" : "mfma<128,128,32>")
-                   : BK == 32  ? "mfma<64,64,32>" : (FULL ? "mfma<64,64,64,vec,full>" : "mfma<64,64,64,vec,skew>");
     with_layout(tA, tB, [&](auto akc, auto bkc) {
         launch_lds<k_gemm_mfma<BM, BN, BK, akc(), bkc(), VEC, SKEW, FULL>>(grid, dim3(256), (size_t)2 * (BM + BN) * BK * sizeof(float), s, p);
     });
 }
 
-// the column-sum rider (GemmP::cs_*) goes with a launch whose every tile is written by one workgroup; returns the rider workgroups to add to the grid
-unsigned take_colsum(GemmP &p, ColSum *cs, bool one_writer) {
-    if (!cs || !one_writer || cs->rows <= 0 || cs->rows > 4096 || cs->E <= 0) return 0;
+// the column-sum rider (GemmP::cs_*) goes with a launch whose every tile is written by one workgroup (GemmPlan::cs_rides; its cs_wgs workgroups are in the plan's grid)
+void take_colsum(GemmP &p, ColSum *cs) {
     p.cs_X = cs->X; p.cs_out = cs->out; p.cs_rows = cs->rows; p.cs_E = cs->E; cs->done = true;
-    return (unsigned)((cs->E + 63) / 64);
 }
 // The riders of a GEMM's last launch - the sliver kernel's epilogue or the split-K fold: the activation behind a linear layer (ep), a second
 // stage behind it (fr.ep2), the mask chain and the layer-0 copy, the latter on at most cp_max extra workgroups of cp_per elements per thread.
@@ -1004,109 +1015,95 @@ void launch_batched(const GemmP &p, dim3 grid, int tA, int tB, long sA, long sB,
     });
 }
 
-} // namespace
-
-namespace t4k {
-
-int gemm_launch(const float *A, const float *B, float *O, const float *bias, float alpha, float beta,
-                int tA, int tB, int M, int N, int K, int C, t4k_stream_t s, const ActEpi *epi, bool *epi_done,
-                ColSum *cs, XFold *defer, FoldRider *rider) {
-    if (epi_done) *epi_done = false;
-    if (defer) defer->part = nullptr;
-    if (!A || !B || !O || M < 0 || N < 0 || K < 0 || C < 1) return fail(T4K_ERR_ARG, "t4k_gemm: bad argument");
-    st().gemm_slabs = 1; st().gemm_fold = false;
-    if (M == 0 || N == 0) { st().gemm_plan = "none"; return T4K_OK; }
+// ------------------------------------------------------------------------------------------
+// The dispatch ladder as a pure function: no launch, no HIP call, no global state beyond gemm_lab().  Every product in it is formed in long / size_t.
+GemmPlan gemm_plan(const GemmAsk &q, const GemmEnv &e) {
     const GemmLab &lab = gemm_lab();
-    const int cu = st().cu_count;
-    hipStream_t hs = S(s);
-    GemmP p;
-    p.A = A; p.B = B; p.O = O; p.bias = bias; p.part = ws_for(s);
-    p.M = M; p.N = N; p.K = K; p.C = C; p.alpha = alpha; p.beta = beta; p.sync = st().d_sync;
+    const int M = q.M, N = q.N, K = q.K, C = q.C, tA = q.tA, tB = q.tB, cu = e.cu;
+    const long Kl = K;                                   // the round-ups of K are formed in long: K + 63 may pass INT_MAX
+    GemmPlan pl;
+    if (M == 0 || N == 0) return pl;                     // GR_NONE: nothing to launch
+    pl.launches = 1;
     if (K == 0) {
         // an empty product: O = alpha 0 + beta O (+ bias) on the fold kernel with no slab to add.  The ladder below would reach a K-loop kernel, and the lean
         // ones (k_gemm_nn_plain, which a large plain product takes at K % 128 == 0) issue their first stage's DMA before they look at the stage count:
         // 64 rows of an operand that has no byte to read
-        const long e = (long)M * N * C;
-        st().gemm_plan = "k0";
-        T4K_LAUNCH(k_splitk_fold, dim3(grid_for(e)), dim3(BLK), 0, hs, p.part, O, e, 0, alpha, beta, bias, N, ActEpi{0, 0.f, nullptr, nullptr, RngArg{0, 0, nullptr}}, FoldRider{});
-        T4K_LAUNCH_CHECK();
-        return T4K_OK;
+        pl.rung = GR_K0; pl.gx = (unsigned)grid_for((long)M * N * C);
+        return pl;
     }
+    const bool aligned = q.a16 && q.b16;
+    const bool cs_ok = q.cs && q.cs_rows > 0 && q.cs_rows <= 4096 && q.cs_E > 0;
+    const unsigned cs_wgs = cs_ok ? (unsigned)((q.cs_E + 63) / 64) : 0;      // the column-sum rider's workgroups, where a launch carries it
+    pl.epi = !q.plain || q.bias;
 
     // 16-byte loads need: C == 1, aligned bases, contiguous extents divisible by 4
     const int a_contig = tA ? M : K, b_contig = tB ? K : N;
-    const bool vec = (C == 1) && aligned16(A) && aligned16(B) && (a_contig % 4 == 0) && (b_contig % 4 == 0);
+    const bool vec = (C == 1) && aligned && (a_contig % 4 == 0) && (b_contig % 4 == 0);
 
-    const long t128 = (long)((M + 127) / 128) * ((N + 127) / 128);
-    const bool big = t128 >= (long)cu * 3 / 4;
+    const bool big = gemm_big(M, N, cu);
     const int BMv = big ? 128 : 64;
-    p.tiles_m = (M + BMv - 1) / BMv; p.tiles_n = (N + BMv - 1) / BMv;
-    const long tiles = (long)p.tiles_m * p.tiles_n;
-    const long mn = (long)M * N;
+    pl.tiles_m = (M + BMv - 1) / BMv; pl.tiles_n = (N + BMv - 1) / BMv;
+    const long tiles = (long)pl.tiles_m * pl.tiles_n;
     const bool dma32 = span32(M, N, K);                  // the LDS-DMA kernels' 32-bit lane offsets reach both operands
     const bool interior64 = M % 64 == 0 && N % 64 == 0;  // no ragged 64x64 tile
+    // the lean 64x64 kernel's tile prologue and tile order (k_gemm_nn_plain<POW2>, PlainP::swap)
+    const int tmq = M / 64, tnq = N / 64;
+    pl.pow2 = lab.fastpro && (tmq & (tmq - 1)) == 0 && (tnq & (tnq - 1)) == 0 && tmq >= 4 && ((long)tmq * tnq) % 32 == 0;
+    pl.swap = lab.tt_swap && tA && tB;
 
     // Slivers (the output gives at most half the CUs a 64x64 tile, K moderate): 32x32 tiles, K split over the waves, operand blocks through
     // LDS-DMA, the whole epilogue (bias, activation riders, mask chain, layer-0 copy, column sums) in the same launch - no fold
     {
         const bool akc = !tA, bkc = tB != 0;
-        const bool al = (!akc || (K % 4 == 0 && aligned16(A))) && (!bkc || (K % 4 == 0 && aligned16(B)));
+        const bool al = (!akc || (K % 4 == 0 && q.a16)) && (!bkc || (K % 4 == 0 && q.b16));
         const long t32 = (long)((M + 31) / 32) * ((N + 31) / 32);
-        int ns = 1, kc = ((K + 7) / 8) * 8;
-        if (defer && alpha == 1.0f && beta == 0.0f && K >= 256) {               // a consumer folds the slabs anyway: spread K over idle CUs
+        int ns = 1, kc = (int)((Kl + 7) / 8 * 8);
+        if (q.defer && q.plain && K >= 256) {               // a consumer folds the slabs anyway: spread K over idle CUs
             int want = (int)((cu + t32 - 1) / t32); if (want > K / 128) want = K / 128; if (want > 16) want = 16;
-            if (want > 1) { kc = (((K + want - 1) / want) + 7) / 8 * 8; ns = (K + kc - 1) / kc; }
-            if ((size_t)ns * M * N * sizeof(float) > st().ws_bytes / 2) { ns = 1; kc = ((K + 7) / 8) * 8; }
+            if (want > 1) { kc = (int)((((Kl + want - 1) / want) + 7) / 8 * 8); ns = (int)((Kl + kc - 1) / kc); }
+            if ((size_t)ns * M * N * sizeof(float) > e.ws_bytes / 2) { ns = 1; kc = (int)((Kl + 7) / 8 * 8); }
         }
         // operands through LDS-DMA blocks: every 16-byte DMA lane aligned and whole (other shapes: the 64x64 kernels below)
-        const bool dma_ok = st().d_zero && aligned16(A) && aligned16(B) && (akc ? K % 4 == 0 : M % 4 == 0) && (bkc ? K % 4 == 0 : N % 4 == 0);
-        if (lab.s32 && C == 1 && !big && tiles * 2 <= cu && K >= 1 && kc <= lab.s32_maxk && al && dma_ok && !capturing(hs)) {   // kc: depth one workgroup walks
-            p.tiles_m = (M + 31) / 32; p.tiles_n = (N + 31) / 32;
-            p.kchunk = kc; p.nsplit = ns;
-            unsigned gx = (unsigned)t32 + take_colsum(p, cs, ns == 1);
+        const bool dma_ok = e.d_zero && aligned && (akc ? K % 4 == 0 : M % 4 == 0) && (bkc ? K % 4 == 0 : N % 4 == 0);
+        if (lab.s32 && C == 1 && !big && tiles * 2 <= cu && K >= 1 && kc <= lab.s32_maxk && al && dma_ok && !e.capturing) {   // kc: depth one workgroup walks
+            pl.tiles_m = (M + 31) / 32; pl.tiles_n = (N + 31) / 32;
+            pl.kchunk = kc; pl.nsplit = ns;
             const bool last = ns == 1;                 // this launch finishes the product and carries its riders; split slabs (a deferred fold) carry none
-            const Riders r = make_riders(hs, mn, last ? epi : nullptr, epi_done, last ? rider : nullptr, 16, 128);
-            if (last) gx += (unsigned)r.fr.cp_blocks;
-            else { defer->part = p.part; defer->nsplit = ns; defer->mn = mn; }
-            p.Z = st().d_zero;
-            p.xmap = (lab.xmap && t32 >= 16) ? (N >= M ? 2 : 1) : 0;       // XCD-aware tile order: an XCD's L2 pulls its own slice of the wider operand only
+            pl.cs_rides = cs_ok && last; pl.cs_wgs = pl.cs_rides ? cs_wgs : 0;
+            pl.gx = (unsigned)t32 + pl.cs_wgs; pl.gy = (unsigned)ns;
+            pl.riders = last ? RIDE_LAUNCH : RIDE_NONE; pl.deferred = !last;
+            pl.xmap = (lab.xmap && t32 >= 16) ? (N >= M ? 2 : 1) : 0;       // XCD-aware tile order: an XCD's L2 pulls its own slice of the wider operand only
             const int nblk = (kc + 31) / 32;
             // waves per workgroup (= k-groups) and whether a wave walks more than two blocks (RST: blocks 2, 3 wait in registers)
-            const bool w8 = nblk > 16 || (nblk >= 6 && t32 * ns <= (long)cu);
-            const bool rst = nblk > (w8 ? 16 : 8);
-            st().gemm_plan = w8 ? (rst ? "l32/w8/rst" : "l32/w8") : (rst ? "l32/w4/rst" : "l32/w4"); st().gemm_slabs = ns;
-            with_layout(tA, tB, [&](auto a, auto b, auto w, auto rs) { launch_l32<a(), b(), w() ? 8 : 4, rs()>(p, r.ep, r.fr, dim3(gx, (unsigned)ns), hs); }, w8, rst);
-            T4K_LAUNCH_CHECK();
-            return T4K_OK;
+            pl.w8 = nblk > 16 || (nblk >= 6 && t32 * ns <= (long)cu);
+            pl.rst = nblk > (pl.w8 ? 16 : 8);
+            pl.rung = pl.w8 ? (pl.rst ? GR_L32_W8_RST : GR_L32_W8) : (pl.rst ? GR_L32_W4_RST : GR_L32_W4);
+            return pl;
         }
     }
     // 65..128 interior tiles, K in whole 256s: two workgroups per tile on the lean kernel, combined in its epilogue (k_gemm_nn_plain<.., PAIR>) -
     // 512 x 1024 x 1024: one launch instead of split-K slabs + a fold launch.  Tickets are per tile: default stream only.
-    if (lab.plain_pair && gates_ok() && !big && vec && C == 1 && interior64 && K % 256 == 0 && K >= 512 &&
-        tiles * 2 <= cu && tiles * 3 > cu && tiles <= 2048 && !defer && !(epi && epi->layer) && !rider && !cs &&
-        st().d_sync && lane_of(hs) == 0 && (size_t)tiles * 4096 * sizeof(float) <= st().ws_bytes / 2 && dma32) {
-        p.kchunk = K;
-        launch_plain_any(p, dim3((unsigned)tiles), tA, tB, hs, true);
-        T4K_LAUNCH_CHECK();
-        return T4K_OK;
+    if (lab.plain_pair && e.gates && !big && vec && C == 1 && interior64 && K % 256 == 0 && K >= 512 &&
+        tiles * 2 <= cu && tiles * 3 > cu && tiles <= 2048 && !q.defer && !q.riders && !q.cs &&
+        e.d_sync && e.lane == 0 && (size_t)tiles * 4096 * sizeof(float) <= e.ws_bytes / 2 && dma32) {
+        pl.rung = GR_PAIR; pl.kchunk = K; pl.gx = (unsigned)tiles;
+        return pl;
     }
     // split K when the output alone cannot fill the chip (granularity = the deepest stage, 64)
     constexpr int KG = 64;
-    int nsplit = 1, kchunk = ((K + KG - 1) / KG) * KG; if (kchunk == 0) kchunk = KG;
-    if (!big && C == 1 && tiles * 2 <= cu && K >= 4 * KG) {
+    int nsplit = 1, kchunk = (int)((Kl + KG - 1) / KG * KG); if (kchunk == 0) kchunk = KG;
+    if (!big && C == 1 && gemm_splits(tiles, K, cu)) {
         int want = (int)((cu + tiles - 1) / tiles);
         int maxs = K / (lab.split_div * KG); if (want > maxs) want = maxs; if (want > 64) want = 64;
         if (want > 1) {
-            kchunk = (((K + want - 1) / want) + KG - 1) / KG * KG;
-            nsplit = (K + kchunk - 1) / kchunk;
-            if ((size_t)nsplit * M * N * sizeof(float) > st().ws_bytes / 2) { nsplit = 1; kchunk = ((K + KG - 1) / KG) * KG; }
+            kchunk = (int)((((Kl + want - 1) / want) + KG - 1) / KG * KG);
+            nsplit = (int)((Kl + kchunk - 1) / kchunk);
+            if ((size_t)nsplit * M * N * sizeof(float) > e.ws_bytes / 2) { nsplit = 1; kchunk = (int)((Kl + KG - 1) / KG * KG); }
         }
     }
-    p.kchunk = kchunk; p.nsplit = nsplit;
-    st().gemm_slabs = nsplit;
+    pl.kchunk = kchunk; pl.nsplit = nsplit;
     const bool whole_k = kchunk % 64 == 0 && K % kchunk == 0;   // every K slice is whole 64-deep stages
 
-    dim3 grid((unsigned)tiles, (unsigned)nsplit, (unsigned)C);
     // ragged M / N with whole K stages on the 8-wave LDS-DMA kernel (clamped source rows, predicated stores) when the K loop is long enough
     // to matter: unsplit products (N = 1000 classes: 1024 x 1000 x 4096 122 -> measured below) - split slivers stay with the skewed kernel
     const bool ragged8 = lab.ragged_dma && !big && vec && C == 1 && nsplit == 1 && !interior64 && whole_k && M >= 4 && N >= 4 && dma32;
@@ -1117,59 +1114,131 @@ int gemm_launch(const float *A, const float *B, float *O, const float *bias, flo
     {   // column-sum rider: only the generic kernel carries it, and only when one workgroup per tile writes the output
         const bool full64 = !big && vec && interior64 && whole_k;
         const bool generic = big || !vec || !(full64 || ragged8 || ragk);
-        grid.x += take_colsum(p, cs, generic && nsplit == 1 && C == 1);
+        pl.cs_rides = cs_ok && generic && nsplit == 1 && C == 1; pl.cs_wgs = pl.cs_rides ? cs_wgs : 0;
     }
+    pl.gx = (unsigned)tiles + pl.cs_wgs; pl.gy = (unsigned)nsplit; pl.gz = (unsigned)C;      // the grid of the generic and the split kernels
+    pl.deferred = nsplit > 1 && q.defer && q.plain;      // the consumer folds the slabs (fused head)
+    pl.fold = nsplit > 1 && !pl.deferred;
+    if (pl.fold) { pl.riders = RIDE_FOLD; pl.launches = 2; }
     auto fill_of = [](long tiles_, long cu_) { return (double)tiles_ / (double)(((tiles_ + cu_ - 1) / cu_) * cu_); };
-    const long t128i = (long)(M / 128) * (N / 128), t64i = (long)((M + 63) / 64) * ((N + 63) / 64);
-    const dim3 g64i((unsigned)((M / 64) * (N / 64)));     // interior 64x64 tiles, one workgroup each
-    const bool lean = vec && C == 1 && nsplit == 1 && !p.cs_X && dma32;   // what every lean LDS-DMA kernel asks for besides its tile shape and K stages
+    const long t128i = (long)(M / 128) * (N / 128), t64i = gemm_tiles64(M, N);
+    const unsigned g64i = (unsigned)((long)(M / 64) * (N / 64));     // interior 64x64 tiles, one workgroup each
+    auto one_launch = [&](GemmRung r, unsigned gx) { pl.rung = r; pl.gx = gx; pl.gy = pl.gz = 1; pl.kchunk = K; pl.nsplit = 1; };   // the lean rungs: unsplit, a tile per workgroup
+    const bool lean = vec && C == 1 && nsplit == 1 && !pl.cs_rides && dma32;   // what every lean LDS-DMA kernel asks for besides its tile shape and K stages
     if (lab.plain128 > 0 && lean && M % 128 == 0 && N % 128 == 0 && (K % 64 == 0 || (lab.plain128_ragk && lab.ragged_k && K % 4 == 0)) && K >= 256 &&
         (lab.plain128 >= 2 || (t128i >= cu && fill_of(t128i, cu) * 1.035 > fill_of(t64i, cu)))) {
-        p.kchunk = K;
-        launch_plain128(p, tA, tB, hs);
+        // one 256 x 256 tile or more per CU: the 16-wave kernel (T4K_GEMM_PLAIN256: 0 off, 1 default, 2 any grid of whole 256-tiles)
+        const int p256 = lab.plain256;
+        const long t256 = (long)(M / 256) * (N / 256), t128 = 4 * t256;
+        // Two co-resident workgroups per CU on 32-deep stages once every CU gets at least two tiles (4096^2 x 1024: 261 -> 254 us, 8192 x 4096 x 512: 282 -> 264 us;
+        // with one tile per CU the doubled barrier count loses: 2048^3 129.5 -> 135.4 us).  K in whole 32s is unragged for this form.  T4K_GEMM_PLAIN128_BK32 = 0 / 1 / 2 (always).
+        const int bk32 = lab.plain128_bk32;
+        // wave quantisation (ADVICE r5): 4352^2 is 289 tiles of 256^2 - two rounds, the second 13 % full - but 1156 tiles of 128^2 at 90 % fill; the 256-tile pipeline is worth ~4 % per FLOP
+        if (p256 && M % 256 == 0 && N % 256 == 0 && K % 32 == 0 && K >= 64 && (p256 >= 2 || (t256 >= cu && fill_of(t256, cu) * 1.04 > fill_of(t128, cu))) &&
+            (long)M * K < (1L << 30) && (long)N * K < (1L << 30)) one_launch(GR_PLAIN256, (unsigned)t256);
+        else if (bk32 && K % 32 == 0 && (bk32 >= 2 || t128i >= 2L * cu)) one_launch(GR_PLAIN128_BK32, (unsigned)t128i);
+        else one_launch(K % 64 != 0 ? GR_PLAIN128_RAGK : GR_PLAIN128, (unsigned)t128i);
     } else if (lab.plain_ragk && lab.ragged_k && lean && interior64 && K > 128 && K % 128 != 0 && (lab.plain_ragk >= 2 || K % 64 != 0)) {
         // interior tiles, unsplit, K >= 128 with a partial last stage: the lean kernel with a tail (any size of output)
-        p.kchunk = K;
-        launch_plain_any(p, g64i, tA, tB, hs, false, true);
-    } else if (big && lab.plain_big && vec && C == 1 && !tA && !tB && alpha == 1.0f && beta == 0.0f && !bias && !p.cs_X && interior64 && K % 128 == 0 && dma32) {
-        launch_nn_plain(p, g64i, hs);      // large plain products on the 64x64 LDS-DMA kernel, several tiles per CU
+        one_launch(GR_PLAIN_RAGK, g64i);
+    } else if (big && lab.plain_big && vec && C == 1 && !tA && !tB && q.plain && !q.bias && !pl.cs_rides && interior64 && K % 128 == 0 && dma32) {
+        pl.rung = GR_NN_PLAIN; pl.gx = g64i; pl.gy = pl.gz = 1;     // large plain products on the 64x64 LDS-DMA kernel, several tiles per CU
     } else if (big && lab.plain_any >= 2 && lean && interior64 && K % 128 == 0) {
-        launch_plain_any(p, g64i, tA, tB, hs);      // large interior products of every layout on the lean kernel (2048^2 x 1024 linear + bias: 86 -> 72 us vs the 128x128 register-staged kernel)
-    } else if (big && lab.big_dma != 0 && gates_ok() && lean && K % 64 == 0 && K >= 2048 && M >= 4 && N >= 4) {   // deep K only: at K = 1024 the 128x128 kernel's fewer, fatter tiles win (292 vs 318 us at 4096 x 4096 x 1024)
+        pl.rung = GR_PLAIN_ANY; pl.gx = g64i; pl.gy = pl.gz = 1;    // large interior products of every layout on the lean kernel (2048^2 x 1024 linear + bias: 86 -> 72 us vs the 128x128 register-staged kernel)
+    } else if (big && lab.big_dma != 0 && e.gates && lean && K % 64 == 0 && K >= 2048 && M >= 4 && N >= 4) {   // deep K only: at K = 1024 the 128x128 kernel's fewer, fatter tiles win (292 vs 318 us at 4096 x 4096 x 1024)
         // every other large product (transposed operands, alpha / beta / bias: the linear layers of an MLP) on the 8-wave LDS-DMA kernel too,
         // 64x64 tiles, several per CU, ragged edges clamped (the 128x128 register-staged kernel: 69-78 % of peak)
-        p.tiles_m = (M + 63) / 64; p.tiles_n = (N + 63) / 64; p.kchunk = K; p.nsplit = 1;
-        const dim3 g64((unsigned)(p.tiles_m * p.tiles_n), 1, 1);
-        if (K % 128 == 0) launch_glds8<128>(p, g64, tA, tB, hs); else launch_glds8<64>(p, g64, tA, tB, hs);
+        pl.tiles_m = (M + 63) / 64; pl.tiles_n = (N + 63) / 64;
+        one_launch(K % 128 == 0 ? GR_GLDS8_128 : GR_GLDS8_64, (unsigned)(pl.tiles_m * pl.tiles_n));
     } else if (big) {
         // whole K stages are enough for the predicate-free pipeline: ragged M / N edges are clamped source rows + predicated stores
         const bool full = vec && kchunk % 32 == 0 && K % kchunk == 0 && M >= 4 && N >= 4 && (lab.big_fullk || (M % 128 == 0 && N % 128 == 0));
-        if (full)     launch_variant<128, 128, 32, true, true, true>(p, grid, tA, tB, hs);
-        else if (vec) launch_variant<128, 128, 32, true, true, false>(p, grid, tA, tB, hs);
-        else          launch_variant<128, 128, 32, false, false, false>(p, grid, tA, tB, hs);
+        pl.rung = full ? GR_MFMA128_FULL : vec ? GR_MFMA128_SKEW : GR_MFMA128;
     } else if (!vec) {
-        launch_variant<64, 64, 32, false, false, false>(p, grid, tA, tB, hs);
+        pl.rung = GR_MFMA64_32;
     } else if (ragk) {
-        if (K >= 128 && (nsplit == 1 || kchunk % 128 == 0)) launch_glds8<128, true>(p, grid, tA, tB, hs); else launch_glds8<64, true>(p, grid, tA, tB, hs);
+        pl.rung = (K >= 128 && (nsplit == 1 || kchunk % 128 == 0)) ? GR_GLDS8_128_RAGK : GR_GLDS8_64_RAGK;
     } else if (ragged8) {
-        if (kchunk % 128 == 0) launch_glds8<128>(p, grid, tA, tB, hs); else launch_glds8<64>(p, grid, tA, tB, hs);
+        pl.rung = kchunk % 128 == 0 ? GR_GLDS8_128 : GR_GLDS8_64;
     } else if (interior64 && whole_k) {
-        if (!dma32) launch_variant<64, 64, 64, true, false, true>(p, grid, tA, tB, hs);          // operands of 4 GiB and more: the register-staged kernel (64-bit addresses)
-        else if (kchunk % 128 == 0 && !tA && !tB && nsplit == 1 && alpha == 1.0f && beta == 0.0f && !bias) launch_nn_plain(p, grid, hs);   // `matmul`
-        else if (lab.plain_any != 0 && kchunk % 128 == 0 && nsplit == 1) launch_plain_any(p, grid, tA, tB, hs);   // the other layouts, alpha / beta / bias: the same lean kernel
-        else if (kchunk % 128 == 0) launch_glds8<128>(p, grid, tA, tB, hs);   // split-K slabs of whole 128-deep stages
-        else launch_glds8<64>(p, grid, tA, tB, hs);
+        if (!dma32) pl.rung = GR_MFMA64_FULL;          // operands of 4 GiB and more: the register-staged kernel (64-bit addresses)
+        else if (kchunk % 128 == 0 && !tA && !tB && nsplit == 1 && q.plain && !q.bias) pl.rung = GR_NN_PLAIN;   // `matmul`
+        else if (lab.plain_any != 0 && kchunk % 128 == 0 && nsplit == 1) pl.rung = GR_PLAIN_ANY;   // the other layouts, alpha / beta / bias: the same lean kernel
+        else pl.rung = kchunk % 128 == 0 ? GR_GLDS8_128 : GR_GLDS8_64;   // split-K slabs of whole 128-deep stages, or 64-deep
     } else {
         const int am = tA ? M : K, bn = tB ? K : N;     // the contiguous extents hold at least one 16-byte group (vec) - the clamp needs M, N >= 4 on the non-K-contiguous side
-        if (lab.fullk && whole_k && M >= 4 && N >= 4 && am >= 4 && bn >= 4) launch_variant<64, 64, 64, true, false, true>(p, grid, tA, tB, hs);   // ragged M / N, whole K stages
-        else launch_variant<64, 64, 64, true, true, false>(p, grid, tA, tB, hs);
+        pl.rung = (lab.fullk && whole_k && M >= 4 && N >= 4 && am >= 4 && bn >= 4) ? GR_MFMA64_FULL : GR_MFMA64_SKEW;   // ragged M / N, whole K stages: the full form
     }
-    if (nsplit > 1 && defer && alpha == 1.0f && beta == 0.0f) {      // the consumer folds the slabs (fused head)
-        defer->part = p.part; defer->nsplit = nsplit; defer->mn = mn;
-    } else if (nsplit > 1) {
+    return pl;
+}
+void plan_text(char *text, size_t n, int rung, int nsplit, bool fold) {       // t4k_gemm_last_plan / t4k_gemm_plan: "rung", "xN" for N split-K slabs, "+fold"
+    int k = snprintf(text, n, "%s", rung_text[rung >= 0 && rung < GR_COUNT ? rung : 0]);
+    if (nsplit > 1 && k < (int)n) k += snprintf(text + k, n - k, "x%d", nsplit);
+    if (fold && k < (int)n) snprintf(text + k, n - k, "+fold");
+}
+
+} // namespace
+
+namespace t4k {
+
+int gemm_launch(const float *A, const float *B, float *O, const float *bias, float alpha, float beta,
+                int tA, int tB, int M, int N, int K, int C, t4k_stream_t s, const ActEpi *epi, bool *epi_done,
+                ColSum *cs, XFold *defer, FoldRider *rider) {
+    if (epi_done) *epi_done = false;
+    if (defer) defer->part = nullptr;
+    if (!A || !B || !O || M < 0 || N < 0 || K < 0 || C < 1) return fail(T4K_ERR_ARG, "t4k_gemm: bad argument");
+    // 1. the environment
+    State &g = st();
+    hipStream_t hs = S(s);
+    const GemmEnv env{ g.cu_count, g.ws_bytes, g.d_zero != nullptr, g.d_sync != nullptr, gates_ok(), lane_of(hs), capturing(hs) };
+    const GemmAsk ask{ M, N, K, C, tA, tB, aligned16(A), aligned16(B), alpha == 1.0f && beta == 0.0f, bias != nullptr,
+                       (epi && epi->layer) || rider, defer != nullptr, cs != nullptr, cs ? cs->rows : 0, cs ? cs->E : 0 };
+    // 2. the plan
+    const GemmPlan pl = gemm_plan(ask, env);
+    g.gemm_last = { pl.rung, pl.nsplit, pl.fold };
+    if (pl.rung == GR_NONE) return T4K_OK;
+    // 3. run it
+    const long mn = (long)M * N;
+    const ActEpi no_epi{0, 0.f, nullptr, nullptr, RngArg{0, 0, nullptr}};
+    GemmP p;
+    p.A = A; p.B = B; p.O = O; p.bias = bias; p.part = ws_for(s);
+    p.M = M; p.N = N; p.K = K; p.C = C; p.alpha = alpha; p.beta = beta; p.sync = g.d_sync;
+    p.tiles_m = pl.tiles_m; p.tiles_n = pl.tiles_n; p.kchunk = pl.kchunk; p.nsplit = pl.nsplit; p.xmap = pl.xmap;
+    if (pl.cs_rides) take_colsum(p, cs);
+    const dim3 grid(pl.gx, pl.gy, pl.gz);
+    switch (pl.rung) {
+    case GR_K0:
+        T4K_LAUNCH(k_splitk_fold, grid, dim3(BLK), 0, hs, p.part, O, mn * C, 0, alpha, beta, bias, N, no_epi, FoldRider{});
+        break;
+    case GR_L32_W4: case GR_L32_W4_RST: case GR_L32_W8: case GR_L32_W8_RST: {
+        // the last launch of the product carries its riders; split slabs (a deferred fold) carry none
+        const bool last = pl.riders == RIDE_LAUNCH;
+        const Riders r = make_riders(hs, mn, last ? epi : nullptr, epi_done, last ? rider : nullptr, 16, 128);
+        p.Z = g.d_zero;
+        with_layout(tA, tB, [&](auto a, auto b, auto w, auto rs) { launch_l32<a(), b(), w() ? 8 : 4, rs()>(p, r.ep, r.fr, dim3(pl.gx + (unsigned)r.fr.cp_blocks, pl.gy), hs); }, pl.w8, pl.rst);
+        break;
+    }
+    case GR_PAIR: launch_plain_any(p, pl, tA, tB, hs); break;
+    case GR_PLAIN128: case GR_PLAIN128_RAGK: case GR_PLAIN128_BK32: case GR_PLAIN256: launch_plain128(p, pl, tA, tB, hs); break;
+    case GR_PLAIN_RAGK: case GR_PLAIN_ANY: launch_plain_any(p, pl, tA, tB, hs); break;
+    case GR_NN_PLAIN:        launch_nn_plain(p, pl, hs); break;
+    case GR_GLDS8_128:       launch_glds8<128>(p, grid, tA, tB, hs); break;
+    case GR_GLDS8_64:        launch_glds8<64>(p, grid, tA, tB, hs); break;
+    case GR_MFMA128_FULL:    launch_variant<128, 128, 32, true, true, true>(p, grid, tA, tB, hs); break;
+    case GR_MFMA128_SKEW:    launch_variant<128, 128, 32, true, true, false>(p, grid, tA, tB, hs); break;
+    case GR_MFMA128:         launch_variant<128, 128, 32, false, false, false>(p, grid, tA, tB, hs); break;
+    case GR_MFMA64_32:       launch_variant<64, 64, 32, false, false, false>(p, grid, tA, tB, hs); break;
+    case GR_GLDS8_128_RAGK:  launch_glds8<128, true>(p, grid, tA, tB, hs); break;
+    case GR_GLDS8_64_RAGK:   launch_glds8<64, true>(p, grid, tA, tB, hs); break;
+    case GR_MFMA64_FULL:     launch_variant<64, 64, 64, true, false, true>(p, grid, tA, tB, hs); break;
+    case GR_MFMA64_SKEW:     launch_variant<64, 64, 64, true, true, false>(p, grid, tA, tB, hs); break;
+    default: return fail(T4K_ERR_ARG, "t4k_gemm: no launch for rung %d", (int)pl.rung);
+    }
+    if (pl.deferred) {                                   // the consumer folds the slabs (fused head)
+        defer->part = p.part; defer->nsplit = pl.nsplit; defer->mn = mn;
+    } else if (pl.fold) {
         const Riders r = make_riders(hs, mn, epi, epi_done, rider, 4, 1024);
-        st().gemm_fold = true;
-        T4K_LAUNCH(k_splitk_fold, dim3(grid_for(mn) + r.fr.cp_blocks), dim3(BLK), 0, hs, p.part, O, mn, nsplit, alpha, beta, bias, N, r.ep, r.fr);
+        T4K_LAUNCH(k_splitk_fold, dim3(grid_for(mn) + r.fr.cp_blocks), dim3(BLK), 0, hs, p.part, O, mn, pl.nsplit, alpha, beta, bias, N, r.ep, r.fr);
     }
     T4K_LAUNCH_CHECK();
     return T4K_OK;
@@ -1215,6 +1284,28 @@ int t4k_gemm(const float *A, const float *B, float *O, float alpha, float beta,
              int tA, int tB, int M, int N, int K, int C, t4k_stream_t s) {
     T4K_REQUIRE_INIT();
     return gemm_launch(A, B, O, nullptr, alpha, beta, tA, tB, M, N, K, C, s);
+}
+
+const char *t4k_gemm_last_plan(void) {
+    static char text[96];
+    const State::GemmLast last = st().gemm_last;
+    plan_text(text, sizeof(text), last.rung, last.nsplit, last.fold);
+    return text;
+}
+
+int t4k_gemm_plan(int M, int N, int K, int C, int tA, int tB, unsigned flags, int cs_rows, int cu, long ws_bytes, char text[64], int out[6]) {
+    if (!text || !out || cu < 0 || ws_bytes < 0) return fail(T4K_ERR_ARG, "t4k_gemm_plan: bad argument");
+    if (M < 0 || N < 0 || K < 0 || C < 1) return fail(T4K_ERR_ARG, "t4k_gemm: bad argument");
+    const State &g = st();
+    // the environment of an initialised library: the zero block and the tickets exist
+    const GemmEnv env{ cu ? cu : g.cu_count, ws_bytes ? (size_t)ws_bytes : g.ws_bytes ? g.ws_bytes : WS_BYTES, true, true, !(flags & T4K_GP_GATES_OFF),
+                       (flags & T4K_GP_LANE) ? 1 : 0, (flags & T4K_GP_CAPTURING) != 0 };
+    const GemmAsk ask{ M, N, K, C, tA, tB, (flags & T4K_GP_A16) != 0, (flags & T4K_GP_B16) != 0, !(flags & T4K_GP_EPILOGUE), (flags & T4K_GP_BIAS) != 0,
+                       (flags & T4K_GP_RIDER) != 0, (flags & T4K_GP_DEFER) != 0, cs_rows != 0, cs_rows, 1 };
+    const GemmPlan pl = gemm_plan(ask, env);
+    plan_text(text, 64, pl.rung, pl.nsplit, pl.fold);
+    out[0] = pl.nsplit; out[1] = pl.kchunk; out[2] = pl.launches; out[3] = pl.riders != RIDE_NONE; out[4] = pl.cs_rides; out[5] = pl.deferred;
+    return T4K_OK;
 }
 
 int t4k_gemm_f64acc(const float *A, const float *B, float *O, float alpha, float beta,

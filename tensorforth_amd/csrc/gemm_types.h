@@ -99,6 +99,12 @@ struct GemmLab {
 };
 inline const GemmLab &gemm_lab() { static const GemmLab v; return v; }
 
+// The first inequalities of the ladder, shared by gemm_plan (gemm.hip) and the callers that decline what it would split (linear_bwd_dual, linear.hip)
+inline long gemm_tiles64(int m, int n)  { return (long)((m + 63) / 64) * ((n + 63) / 64); }
+inline long gemm_tiles128(int m, int n) { return (long)((m + 127) / 128) * ((n + 127) / 128); }
+inline bool gemm_big(int m, int n, int cu) { return gemm_tiles128(m, n) >= (long)cu * 3 / 4; }        // 128x128 tiles for >= ~3/4 of the CUs
+inline bool gemm_splits(long tiles, int k, int cu) { return tiles * 2 <= cu && k >= 256; }            // the output alone cannot fill the chip and K holds four 64-deep stages
+
 // the LDS-DMA kernels address their operands with 32-bit lane offsets: both must span less than 4 GiB
 inline bool span32(int M, int N, int K) { return (size_t)M * K * sizeof(float) < ((size_t)1 << 32) && (size_t)K * N * sizeof(float) < ((size_t)1 << 32); }
 inline bool capturing(hipStream_t hs) { hipStreamCaptureStatus st_ = hipStreamCaptureStatusNone; return hipStreamIsCapturing(hs, &st_) == hipSuccess && st_ != hipStreamCaptureStatusNone; }   // a replayed graph would repeat the epoch argument

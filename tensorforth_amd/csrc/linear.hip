@@ -27,15 +27,12 @@ bool linear_bwd_dual(const float *X, const float *W, const float *DY, float *DX,
     int *gate = gate_for(hs, 1);                             // nullptr: unknown stream, the two GEMMs go out as separate launches
     if (!dual_on() || !g.d_sync || !gate || (E0 & 3) || (E1 & 3) || !aligned16(DY) || !aligned16(X) || !aligned16(W) || N < 1) return false;
     const int cu = g.cu_count;
-    auto tiles = [](int m, int n) { return (long)((m + 63) / 64) * ((n + 63) / 64); };
-    auto big = [&](int m, int n) { return (long)((m + 127) / 128) * ((n + 127) / 128) >= (long)cu * 3 / 4; };
-    auto splits = [&](int m, int n, int k) { return tiles(m, n) * 2 <= cu && k >= 256; };
     auto full = [](int m, int n, int k) { return m % 64 == 0 && n % 64 == 0 && k % 64 == 0; };
+    const long t1 = gemm_tiles64(E0, E1), t2 = gemm_tiles64(N, E1), riders = (E0 + 63) / 64;
     // deep-K shapes would go split-K + fold (2 launches per GEMM); up to K = 1024 the single dual launch, unsplit, is faster (GAN round 0.318 ms of GPU time; with T4K_GEMM_DUAL_MAXK=256: 0.341)
-    const bool sp = splits(E0, E1, N) || splits(N, E1, E0);
-    if (big(E0, E1) || big(N, E1) || (sp && (N > lab.dual_maxk || E0 > lab.dual_maxk))) return false;
+    const bool sp = gemm_splits(t1, N, cu) || gemm_splits(t2, E0, cu);
+    if (gemm_big(E0, E1, cu) || gemm_big(N, E1, cu) || (sp && (N > lab.dual_maxk || E0 > lab.dual_maxk))) return false;
     if (!lab.dual_full && (full(E0, E1, N) || full(N, E1, E0))) return false;
-    const long t1 = tiles(E0, E1), t2 = tiles(N, E1), riders = (E0 + 63) / 64;
     if (t1 + riders + t2 > cu || N > 4096) return false;
     const bool alias = (const float *)DX == X || (const float *)DX == DY || (const float *)DX == W;   // only an in-place dX needs the arrival gate
     const MaskChain mc = mcp ? *mcp : MaskChain{nullptr, nullptr, nullptr, nullptr};

@@ -84,7 +84,7 @@ int t4k_init(int device) {
     g.cu_count = prop.multiProcessorCount;
     if (!g.stream) { T4K_HIP(hipStreamCreateWithFlags(&g.stream, hipStreamNonBlocking)); g.own_stream = true; }
     if (!g.ws) {
-        g.ws_bytes = (size_t)64 << 20;                 // 64 MiB: reductions, split-K slabs, linalg
+        g.ws_bytes = WS_BYTES;                         // 64 MiB: reductions, split-K slabs, linalg
         T4K_HIP(hipMalloc(&g.ws, g.ws_bytes));
         T4K_HIP(hipMemsetAsync(g.ws, 0, g.ws_bytes, g.stream));
     }
@@ -118,14 +118,6 @@ int t4k_gates_enabled(void) { return st().gates_off ? 0 : 1; }
 const char *t4k_last_error(void)  { return st().err; }
 unsigned long long t4k_launch_count(void) { return st().launches; }
 const char *t4k_backend_name(void) { return "hip-gfx950"; }
-const char *t4k_gemm_last_plan(void) {
-    static char text[96];
-    const State &g = st();
-    int n = snprintf(text, sizeof(text), "%s", g.gemm_plan);
-    if (g.gemm_slabs > 1 && n < (int)sizeof(text)) n += snprintf(text + n, sizeof(text) - n, "x%d", g.gemm_slabs);
-    if (g.gemm_fold && n < (int)sizeof(text)) snprintf(text + n, sizeof(text) - n, "+fold");
-    return text;
-}
 const char *t4k_conv_last_plan(void) {
     static char text[sizeof(State::conv_plan)];
     memcpy(text, st().conv_plan, sizeof(text));

@@ -15,6 +15,7 @@ constexpr int WAVE   = 64;
 constexpr int BLK    = 256;            // default workgroup: 4 waves, one per SIMD
 constexpr int MAX_WG = 2048;           // 256 CUs x 8 resident blocks: grid-stride above this
 constexpr float DU_EPS = 1.0e-6f;      // reference src/ten4_types.h:85
+constexpr size_t WS_BYTES = (size_t)64 << 20;   // a stream's workspace (t4k_init, t4k_stream_create)
 
 struct State {
     bool        ready   = false;
@@ -44,9 +45,7 @@ struct State {
     int         cu_count = 256;
     unsigned    slot_epoch[16] = {};  // per stream lane: launch count of the kernels that tag the arrival slots (next_slot_epoch)
     unsigned long long launches = 0;  // kernels launched by the library since t4k_init (t4k_launch_count)
-    const char *gemm_plan = "";       // the rung the last gemm_launch took (t4k_gemm_last_plan): set by the launch_* wrappers of gemm.hip, a literal each
-    int         gemm_slabs = 1;       // ... its split-K slabs and whether a fold launch followed them
-    bool        gemm_fold = false;
+    struct GemmLast { int rung = 0, nsplit = 1; bool fold = false; } gemm_last;   // the plan of the last gemm_launch (t4k_gemm_last_plan): its rung (GemmRung, gemm.hip), split-K slabs, whether a fold launch followed them
     char        conv_plan[256] = {0}; // the engine decisions of the last conv entry in launch order (t4k_conv_last_plan): appended by the launch wrappers and dispatch functions of the conv units
     int         conv_plan_len = 0, conv_plan_depth = 0;   // ... its length, and how many conv entries are open (t4k_dconv2d_* call t4k_conv2d_*: the outermost one starts the string)
     bool        gates_off = false;    // no kernel that makes workgroups wait for each other is chosen any more (t4k_gates_enable(0), or set by spin_check() after a timed-out wait)

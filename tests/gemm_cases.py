@@ -1,7 +1,7 @@
 """Cases of the GEMM sweep and a Python mirror of the dispatch ladder they are chosen against - shared by the GPU sweep
 (tests/test_gpu_gemm_sweep.py) and its CPU self-test (tests/test_gemm_cases.py), the arrangement of linear_cases.py.
 
-The mirror restates gemm_launch and launch_plain128 (tensorforth_amd/csrc/gemm.hip) inequality by inequality, with every GemmLab switch at
+The mirror restates gemm_plan, the planner gemm_launch runs (tensorforth_amd/csrc/gemm.hip), inequality by inequality, with every GemmLab switch at
 its release default (gemm_types.h).  It returns the string t4k_gemm_last_plan() reports and the launch count; the GPU sweep asserts both
 for every row, so a heuristic that moves a shape to another kernel fails the sweep instead of leaving it green on the wrong kernel.
 Everything is sized for the MI355X's 256 CUs; the sweep passes the device's count and FAILS a row that no longer reaches its label.
@@ -88,9 +88,9 @@ def ladder(M, N, K, tA, tB, C=1, cu=CU, aligned=True, alpha=1.0, beta=0.0, bias=
     t128i, t64i = (M // 128) * (N // 128), cdiv(M, 64) * cdiv(N, 64)
     lean = vec and C == 1 and nsplit == 1 and not cs and dma32
     if lean and M % 128 == 0 and N % 128 == 0 and (K % 64 == 0 or K % 4 == 0) and K >= 256 and t128i >= cu and _fill(t128i, cu) * 1.035 > _fill(t64i, cu):
-        base = plain128(M, N, K, cu)
+        base = plain128(M, N, K, cu); kchunk = K         # the lean kernels walk K itself, tail and all (GemmP::kchunk = K)
     elif lean and interior64 and K > 128 and K % 128 != 0:
-        base = "plain_ragk"
+        base = "plain_ragk"; kchunk = K
     elif big and vec and C == 1 and not tA and not tB and plain and not bias and not cs and interior64 and K % 128 == 0 and dma32:
         base = "nn_plain"
     elif big and lean and interior64 and K % 128 == 0:
@@ -131,6 +131,26 @@ def plain128(M, N, K, cu=CU):
     if K % 32 == 0 and (M // 128) * (N // 128) >= 2 * cu:
         return "plain128/bk32"
     return "plain128/ragk" if K % 64 != 0 else "plain128"
+
+
+# ----------------------------------------------------------------------------- the planner itself
+GP_A16, GP_B16, GP_EPILOGUE, GP_BIAS, GP_RIDER, GP_DEFER, GP_LANE, GP_CAPTURING, GP_GATES_OFF = (1 << i for i in range(9))      # T4K_GP_* (include/t4k.h)
+
+
+def plan_entry(lib, M, N, K, C, tA, tB, flags, cs_rows=0, cu=CU, ws=0):
+    """t4k_gemm_plan: what gemm_launch's own planner answers on the host, in ladder()'s terms -
+    (plan, launches, nsplit, kchunk, riders_ride, cs_ride, deferred)"""
+    import ctypes
+    text, out = ctypes.create_string_buffer(64), (ctypes.c_int * 6)()
+    rc = lib.t4k_gemm_plan(M, N, K, C, tA, tB, flags, cs_rows, cu, ws, text, out)
+    assert rc == 0, (M, N, K, C, tA, tB, flags, cs_rows, cu, ws, rc)
+    return (text.value.decode(), out[2], out[0], out[1], bool(out[3]), bool(out[4]), bool(out[5]))
+
+
+def plan_flags(a_ptr, b_ptr, alpha=1.0, beta=0.0, lane=0, capturing=False, more=0):
+    """the flags word of a call as it is made: the real alignment of A and B, its epilogue, its stream and capture state"""
+    return ((GP_A16 if a_ptr % 16 == 0 else 0) | (GP_B16 if b_ptr % 16 == 0 else 0) | (0 if (alpha, beta) == (1.0, 0.0) else GP_EPILOGUE) |
+            (GP_LANE if lane else 0) | (GP_CAPTURING if capturing else 0) | more)
 
 
 def gemm_kernel_plan(M, N, K, tA, tB, C=1, cu=CU, aligned=True, alpha=1, beta=0, lane=0, capturing=False):

@@ -49,6 +49,11 @@ def cu_count(t4k):
     return cu.value
 
 
+def entry_plan(t4k, r, a_ptr, b_ptr, alpha, beta, lane=0, capturing=False):
+    """t4k_gemm_plan's text for the call as it was made: the device's CU count, the real alignment of A and B, the stream and capture state"""
+    return gc.plan_entry(t4k.lib, r.M, r.N, r.K, r.C, r.tA, r.tB, gc.plan_flags(a_ptr, b_ptr, alpha, beta, lane, capturing), cu=cu_count(t4k))[0]
+
+
 def call(t4k, name, *a):
     """t4k.call; a HIP error (a fault on the device) ends the session there: nothing more is started on a device that has faulted"""
     try:
@@ -127,6 +132,7 @@ def run_row(t4k, dev, r, exact, passes=None, stream=None, lane=0, oskew=0, check
         l0 = launches(t4k)
         call(t4k, "t4k_gemm", bA.ptr, bB.ptr, bO.ptr, alpha, beta, r.tA, r.tB, r.M, r.N, r.K, r.C, stream)
         n, plan = launches(t4k) - l0, last_plan(t4k)
+        assert entry_plan(t4k, r, bA.ptr, bB.ptr, alpha, beta, lane) == plan, "%s: t4k_gemm_plan() does not say what the launch did, %s" % (name, plan)
         if check_plan:
             assert plan == want, "%s: t4k_gemm_last_plan() says %s, the mirror %s" % (name, plan, want)
             assert n == want_n, "%s: %d launches, the plan %s makes %d" % (name, n, want, want_n)
@@ -227,8 +233,10 @@ def test_streams_and_capture(t4k, dev):
             l0 = launches(t4k)
             rc = t4k.lib.t4k_gemm(bA.ptr, bB.ptr, bO.ptr, 1.0, 0.0, r.tA, r.tB, r.M, r.N, r.K, r.C, s)
             n, plan = launches(t4k) - l0, last_plan(t4k)
+            during = entry_plan(t4k, r, bA.ptr, bB.ptr, 1.0, 0.0, lane=1, capturing=True)
             t4k.call("t4k_graph_end", s, ctypes.byref(g))
             assert rc == 0 and plan == want and n == want_n, (r.id, rc, plan, want, n, want_n)
+            assert during == plan and entry_plan(t4k, r, bA.ptr, bB.ptr, 1.0, 0.0, lane=1).startswith("l32"), (r.id, during, plan)   # the capture alone moved it
             t4k.call("t4k_graph_launch", g, s)
             got = bO.get(r.id + " captured", shape, s)
             gc.hold(r.id + " captured", got, prod, 1.0, 0.0, O0, True, "captured")

@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 import f64_witness as wt
+import gemm_cases as gc
 import linear_cases as lc
 from test_gpu_parity import Dev, PoolBlock, p
 
@@ -72,6 +73,14 @@ def assert_label(t4k, case, want=None, **over):
     return n
 
 
+def assert_gemm_entry(t4k, tag, M, N, K, tA, tB, a_ptr, b_ptr, more=0):
+    """behind an entry whose last product went through gemm_launch: t4k_gemm_plan, asked with the device's CU count, the real alignment of the
+    product's A and B and what the entry hands gemm_launch (`more`: GP_BIAS, GP_RIDER), gives the text t4k_gemm_last_plan() reports"""
+    want = t4k.lib.t4k_gemm_last_plan().decode()
+    got = gc.plan_entry(t4k.lib, M, N, K, 1, tA, tB, gc.plan_flags(a_ptr, b_ptr, more=more), cu=cu_count(t4k))[0]
+    assert got == want, "%s: t4k_gemm_plan() says %s, the launch took %s" % (tag, got, want)
+
+
 def draws(oracle, sizes):
     """uniform draws of the dropout stages, in call order, from the oracle's stream; the offset behind them"""
     o = oracle.lib(); o.t4o_rand_init(SEED); o.t4o_rand_set_offset(OFFSET)
@@ -121,6 +130,9 @@ def run_fwd(t4k, dev, oracle, case, exact, want_label=None, check_plan=True, cor
             blk.post_layer, blk.post_alpha, blk.post_mask, blk.post_out = layer_id(oracle, stages[1]), ALPHA[stages[1]], sb[1][0].ptr, sb[1][1].ptr
         t4k.call("t4k_linear_block_fwd", bX.ptr, bC.ptr if copy else None, bW.ptr, bB.ptr, bY.ptr, ctypes.byref(blk) if stages else None, N, E0, E1, None)
     n = launches(t4k) - l0; off = int(t4k.lib.t4k_rand_offset())
+    if not head and not lc.small_ok(E0, E1):                # Y = X W^T + B on gemm_launch: an activation epilogue or the block's rider is asked for
+        asked = c.entry == "linear_block_fwd" or (c.entry == "linear_act_fwd" and bool(stages))
+        assert_gemm_entry(t4k, tag, N, E0, E1, 0, 1, bX.ptr, bW.ptr, gc.GP_BIAS | (gc.GP_RIDER if asked else 0))
     assert t4k.lib.t4k_sync(None) == 0, tag
     got = {"Y": bY.get(dev, tag + " Y"), "X": bX.get(dev, "X"), "W": bW.get(dev, "W"), "B": bB.get(dev, "B")}
     for i, (f, a) in enumerate(sb):
@@ -172,6 +184,11 @@ def run_bwd(t4k, dev, oracle, case, exact, in_place, want_label=None, check_plan
         t4k.call("t4k_linear_block_bwd", X, W, DY, T if tgt else None, bDY2.ptr if tgt else None, bDX.ptr, ctypes.byref(blk),
                  bD[-1].ptr, pDW, pDB, N, E0, E1, train, None)
     n = launches(t4k) - l0
+    lab = want_label or c.label
+    if "dx_only" in lab:                                    # dX = dY W on gemm_launch with the mask chain as its rider
+        assert_gemm_entry(t4k, tag, N, E1, E0, 0, 0, DY, W, gc.GP_RIDER)
+    elif "+dx_" in lab or lab.startswith("dx_"):            # the separate launches: dX = dY W is the last product
+        assert_gemm_entry(t4k, tag, N, E1, E0, 0, 0, DY, W)
     assert t4k.lib.t4k_sync(None) == 0, tag
     got = {"DX": bDX.get(dev, tag + " DX"), "DW": b["DW0"].get(dev, tag + " DW"), "DB": b["DB0"].get(dev, tag + " DB"), "DY": b["DY"].get(dev, tag + " DY"),
            "W": b["W"].get(dev, "W"), "T": b["T"].get(dev, "T"), "X": b["X"].get(dev, "X")}
