@@ -702,6 +702,10 @@ int t4k_conv_stack_ok(const t4k_conv_stage *st, int n_stage, int N);           /
  * workgroup while every band keeps a row of every grid and the LDS plan fits).  Returns 1 and fills both, or 0 (nothing written) when the
  * stack does not qualify (t4k_conv_stack_ok == 0). */
 int t4k_conv_stack_plan(const t4k_conv_stage *st, int n_stage, int N, int *split, int *bsplit);
+/* read-only, no device needed: the preamble the run-time compiled device source is specialised with for this stack at `split` forward and `bsplit`
+ * backward bands (1 - 4 each), and the file name of its code object in the disk cache - the hash of preamble + source + options, so two plans that
+ * differ in any define never share an object.  Returns 1 and both strings, or 0 when the shapes do not qualify or a buffer is too small. */
+int t4k_conv_stack_key(const t4k_conv_stage *st, int n_stage, int split, int bsplit, char *preamble, int preamble_cap, char *name, int name_cap);
 int t4k_conv_stack_selftest(void);   /* the stack kernels are compiled at run time (hipRTC) for the model's shapes: this compiles two reference
                                       * shape sets for gfx950 - no device needed - and returns 0, or an error with the compiler log in t4k_last_error() */
 /* The stack AND the classifier head behind its flatten in ONE launch: [conv + run] x n, flatten, linear E1 -> E0a, one element-wise layer

@@ -20,6 +20,9 @@
 #define CS_H_MID 10
 #define CS_H_ALPHA 0.5f
 #define CS_H_PF 6
+#ifndef CS_STREAM_DEAD          // (the Makefile compiles this check twice: -DCS_STREAM_DEAD=0 is the second)
+#define CS_STREAM_DEAD 1
+#endif
 #endif
 
 #ifndef CS_VALU_FWD
@@ -133,11 +136,84 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 #else
 #define CS_LAST_STORES(S) true
 #endif
-template <int VW> __device__ __forceinline__ void gstore(float *p, const float *v) {
-    if (VW == 4)      *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1 % VW], v[2 % VW], v[3 % VW]);
-    else if (VW == 2) *reinterpret_cast<float2 *>(p) = make_float2(v[0], v[1 % VW]);
-    else              *p = v[0];
+// ---- store policy of a global store site.  Under the BANDED plan (CS_BSPLIT > 1) most of what the two large kernels store is read by no launch of the step: the
+// banded backward reads the forward's saves instead of the layer tensors, and the next forward overwrites every dX.  Left to plain stores those lines stay dirty
+// in the L2s until the kernel ends and are written back at the boundary, in front of the next launch; a STREAMING store hands them to the memory side while the
+// body still runs.  A policy changes no value, order or address - only the cache bits of the store instruction.
+//   ST_PLAIN  global_store_*                the default; every LIVE site, every site of a one-band module, all of cs_bwd
+//   ST_NT     global_store_* ... nt         __builtin_nontemporal_store: what cs_bwd_b's dead sites take
+//   ST_WT     global_store_* ... sc0 sc1    write-through (the form of the group head's slice stores below): what cs_fwd's dead sites take
+// LIVE = read by a later launch of the step; DEAD = everything else (the host, t4k_conv_stack_dx0 on demand and a whole-image backward behind a banded forward
+// still read them correctly: the policy is a hint, not a scope).  Bytes per image: the LeNet front end at batch 128.
+//   kernel     site                                   tensor                          B/image  class  reader
+//   cs_fwd     image rows                             X0 (layer-0 copy of the batch)    3 136  dead
+//   cs_fwd     image rows                             save_x[0]                         3 136  LIVE   cs_bwd_b (stage_bwd_b: X window of the dF rows)
+//   cs_fwd     stage_fwd, conv-output copy            O                        31 360 + 15 680  dead   (the LAST tensor of a stack without flatten - O, P, Q or R
+//   cs_fwd     run_fwd, pre                           P                                15 680  dead    of the last stage - is LIVE: the layer behind the stack)
+//   cs_fwd     run_fwd, pre                           Fpre                             15 680  LIVE   cs_bwd_b (run_bwd: mask multiply)
+//   cs_fwd     run_fwd, pool                          Q                         7 840 + 3 920  dead
+//   cs_fwd     run_fwd, pool                          save_am                   1 960 +   980  LIVE   cs_bwd_b (run_bwd<S, true>: the pool's winning cell)
+//   cs_fwd     run_fwd, post                          R                         7 840 + 3 920  dead
+//   cs_fwd     run_fwd, post                          Fpost                     7 840 + 3 920  LIVE   cs_bwd_b (run_bwd: mask multiply)
+//   cs_fwd     run_fwd, flatten                       R2                                3 920  LIVE   k_head_bwd_l32 (dW1 = dY1^T x), the layer behind the stack
+//   cs_fwd     run_fwd, next conv's input             save_x[1]                         7 840  LIVE   cs_bwd_b (stage_bwd_b)
+//   cs_fwd     head_fwd                               Y1 Fm Am Y2 P hot hit slots       2 121  LIVE   k_head_bwd_l32; the collector band (slots)
+//   cs_bwd_b   run_bwd, flatten / post / pool / pre   R, Q, P, O (dX of each layer)    78 400  dead   (stage 0's O holds the dO t4k_conv_stack_dx0 reads ON DEMAND)
+//   cs_bwd_b   stage_bwd_b, dX copy-out               X, DXS of stages >= 1    7 840 + 7 840  dead   (X is the R of the stage in front, counted there)
+//   cs_bwd_b   stage_bwd_b, dX copy-out               X, DXS of stage 0         3 136 + 3 136  LIVE   the backward of the layer in front of the stack, when there is one
+//   cs_bwd_b   df_fold                                partial rows (2 bands)           15 360  LIVE   k_opt_step / k_cs_fold
+//   cs_bwd_b   kernel end                             f0_save                    (360 once)    LIVE   t4k_conv2d_bwd2 (t4k_conv_stack_dx0)
+// CS_STREAM_DEAD (preamble, conv_stack.hip: written for CS_BSPLIT > 1 only, part of the cache key) turns the dead sites' policy on; CS_STREAM_FWD / CS_STREAM_BWD are
+// the policy each kernel's dead sites then take - the defaults are what measured fastest (profiles/LAB_NOTES.md 19: write-through took 0.9 us off a cs_fwd launch where
+// nt took 0.15, nt 0.75 us off cs_bwd_b where write-through ADDED 1.9), lab builds override them (T4K_STACK_STREAM_FWD / _BWD).
+#define ST_PLAIN 0
+#define ST_NT 1
+#define ST_WT 2
+#ifndef CS_STREAM_DEAD
+#define CS_STREAM_DEAD 0
+#endif
+#ifndef CS_STREAM_FWD
+#define CS_STREAM_FWD ST_WT
+#endif
+#ifndef CS_STREAM_BWD
+#define CS_STREAM_BWD ST_NT
+#endif
+constexpr int ST_FWD = (CS_STREAM_DEAD && CS_BSPLIT > 1) ? CS_STREAM_FWD : ST_PLAIN;      // dead sites of cs_fwd
+constexpr int ST_BWD = (CS_STREAM_DEAD && CS_BSPLIT > 1) ? CS_STREAM_BWD : ST_PLAIN;      // dead sites of cs_bwd_b
+typedef float v2f __attribute__((ext_vector_type(2)));
+// The write-through forms are inline asm: the compiler does not look inside the string, so each ends with the wait states (s_nop 1) that keep whatever instruction
+// follows from overwriting the data registers before the store has read them, and each is a compiler memory barrier ("memory"), so no access of the
+// compiler's own is moved across a store it cannot see.
+template <int POL> __device__ __forceinline__ void gstore4(float *p, const float4 &t) {      // 16 bytes (the copy loops hand their LDS read over as it is)
+    if constexpr (POL == ST_NT)      __builtin_nontemporal_store(v4f{t.x, t.y, t.z, t.w}, reinterpret_cast<v4f *>(p));
+    else if constexpr (POL == ST_WT) { const v4f u = v4f{t.x, t.y, t.z, t.w}; asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" :: "v"(p), "v"(u) : "memory"); }
+    else                             *reinterpret_cast<float4 *>(p) = t;
 }
+template <int POL> __device__ __forceinline__ void gstore2(float *p, const float2 &t) {
+    if constexpr (POL == ST_NT)      __builtin_nontemporal_store(v2f{t.x, t.y}, reinterpret_cast<v2f *>(p));
+    else if constexpr (POL == ST_WT) { const v2f u = v2f{t.x, t.y}; asm volatile("global_store_dwordx2 %0, %1, off sc0 sc1\n\ts_nop 1" :: "v"(p), "v"(u) : "memory"); }
+    else                             *reinterpret_cast<float2 *>(p) = t;
+}
+template <int POL> __device__ __forceinline__ void gstore1(float *p, const float t) {
+    if constexpr (POL == ST_NT)      __builtin_nontemporal_store(t, p);
+    else if constexpr (POL == ST_WT) asm volatile("global_store_dword %0, %1, off sc0 sc1\n\ts_nop 1" :: "v"(p), "v"(t) : "memory");
+    else                             *p = t;
+}
+template <int VW, int POL = ST_PLAIN> __device__ __forceinline__ void gstore(float *p, const float *v) {
+    if constexpr (POL == ST_PLAIN) {
+        if (VW == 4)      *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1 % VW], v[2 % VW], v[3 % VW]);
+        else if (VW == 2) *reinterpret_cast<float2 *>(p) = make_float2(v[0], v[1 % VW]);
+        else              *p = v[0];
+    } else {
+        if (VW == 4)      gstore4<POL>(p, make_float4(v[0], v[1 % VW], v[2 % VW], v[3 % VW]));
+        else if (VW == 2) gstore2<POL>(p, make_float2(v[0], v[1 % VW]));
+        else              gstore1<POL>(p, v[0]);
+    }
+}
+// the policy of a forward store to run tensor `kind` (0 = O, 1 = P, 2 = Q, 3 = R) of stage S: the stack's LAST tensor, when no flatten copies it, is the input of
+// the layer behind the stack and stays plain
+constexpr int last_kind(int s) { return SH[s].post ? 3 : (SH[s].pool ? 2 : (SH[s].pre ? 1 : 0)); }
+constexpr int st_fwd_of(int s, int kind) { return (s == CS_NS - 1 && !SH[s].flat && kind == last_kind(s)) ? ST_PLAIN : ST_FWD; }
 constexpr int vw_of(int n) { return (n & 3) == 0 ? 4 : ((n & 1) == 0 ? 2 : 1); }
 template <int CV> struct VecF { float v[CV]; };
 template <int CV> __device__ __forceinline__ VecF<CV> gload(const float *p) {
@@ -324,7 +400,7 @@ __device__ __forceinline__ void run_fwd(const FwdStage &g, float *gnext_save, fl
             if (PRE == L_DROPOUT) philox4x32_10(g.base + (u64)(a >> 2), g.seed, r);
 #pragma unroll
             for (int q = 0; q < VW; q++) act1<PRE>(e[q], PRE == L_DROPOUT ? u01(r[(a + q) & 3]) : 0.f, SH[S].a_pre, o[q], f[q]);
-            if (CS_LAST_STORES(S) && l >= o_lo && l < o_hi) { gstore<VW>(g.Fpre + a, f); gstore<VW>(g.P + a, o); }
+            if (CS_LAST_STORES(S) && l >= o_lo && l < o_hi) { gstore<VW>(g.Fpre + a, f); gstore<VW, st_fwd_of(S, 1)>(g.P + a, o); }
             lstore<VW>(Out + l, o);
         }
         lds_barrier();
@@ -363,7 +439,7 @@ __device__ __forceinline__ void run_fwd(const FwdStage &g, float *gnext_save, fl
             const long zo = abs0 + lo;
             const bool own = lo >= o_lo && lo < o_hi;
             const bool ownst = own && CS_LAST_STORES(S);
-            if (POOL && ownst) gstore<VW>(g.Q + zo, acc);
+            if (POOL && ownst) gstore<VW, st_fwd_of(S, 2)>(g.Q + zo, acc);
             if (POOL && POOL != L_AVGPOOL && ownst && g.save_am) {
                 if (VW == 4) *reinterpret_cast<u32 *>(g.save_am + zo) = (u32)am[0] | ((u32)am[1 % VW] << 8) | ((u32)am[2 % VW] << 16) | ((u32)am[3 % VW] << 24);
                 else {
@@ -377,7 +453,7 @@ __device__ __forceinline__ void run_fwd(const FwdStage &g, float *gnext_save, fl
                 if (POST == L_DROPOUT) philox4x32_10(g.base2 + (u64)(zo >> 2), g.seed, r);
 #pragma unroll
                 for (int q = 0; q < VW; q++) act1<POST>(acc[q], POST == L_DROPOUT ? u01(r[(zo + q) & 3]) : 0.f, SH[S].a_post, o[q], f[q]);
-                if (ownst) { gstore<VW>(g.Fpost + zo, f); gstore<VW>(g.R + zo, o); }
+                if (ownst) { gstore<VW>(g.Fpost + zo, f); gstore<VW, st_fwd_of(S, 3)>(g.R + zo, o); }
 #pragma unroll
                 for (int q = 0; q < VW; q++) acc[q] = o[q];
             }
@@ -462,8 +538,9 @@ __device__ __forceinline__ void stage_fwd(const FwdArgs &p, float *L, int img, i
             const int n = CS_LAST_STORES(S) ? (oh - ol) * rowC : 0;
             const float *src = Out + (ol - cl) * rowC;
             float *o = g.O + ((long)img * H + ol) * rowC;
-            if ((rowC & 3) == 0) { for (int e = threadIdx.x * 4; e < n; e += CS_THREADS * 4) *reinterpret_cast<float4 *>(o + e) = *reinterpret_cast<const float4 *>(src + e); }
-            else for (int e = threadIdx.x; e < n; e += CS_THREADS) o[e] = src[e];
+            constexpr int POL = st_fwd_of(S, 0);
+            if ((rowC & 3) == 0) { for (int e = threadIdx.x * 4; e < n; e += CS_THREADS * 4) gstore4<POL>(o + e, *reinterpret_cast<const float4 *>(src + e)); }
+            else for (int e = threadIdx.x; e < n; e += CS_THREADS) gstore1<POL>(o + e, src[e]);
         }
         run_fwd<S>(g, S + 1 < CS_NS ? p.st[S + 1 < CS_NS ? S + 1 : S].save_x : nullptr, Out, L, img, band);
         CS_STAMP(6 + 4 * S);
@@ -926,7 +1003,7 @@ extern "C" __global__ void __launch_bounds__(CS_THREADS) cs_fwd(const FwdArgs p)
             if (e < nimg) {
                 const int y = e / wc0, r = e - y * wc0;
                 L[in_off(0) + (y + ir_lo - (cl0 - P0)) * RS0 + P0 * SH[0].C1 + r] = vi[q];
-                if (x0 && e >= own_lo && e < own_hi) x0[e] = vi[q];
+                if (x0 && e >= own_lo && e < own_hi) gstore1<ST_FWD>(x0 + e, vi[q]);
                 if (xs && e >= own_lo && e < own_hi) xs[e] = vi[q];
             }
         }
@@ -1025,8 +1102,8 @@ template <int S, int NTH = CS_THREADS, int VFQ = 8> __device__ __forceinline__ v
 // of a may-alias buffer, one HBM round trip per element.
 // Pooled rows [ql, qh) are processed (dY in LDS and the dO window start at row ql), rows [pol, poh) are stored.  SAVED: the pool's winning
 // cell comes from the forward's arg-max codes instead of the forward values in the pool's input buffer (banded backward: a neighbouring
-// band overwrites those in place).
-template <int S, bool SAVED, int NTH = CS_THREADS>
+// band overwrites those in place).  POL: the store policy of every dX tensor the run writes (cs_bwd_b: ST_BWD; cs_bwd shares this routine and keeps plain stores).
+template <int S, bool SAVED, int NTH = CS_THREADS, int POL = ST_PLAIN>
 __device__ __forceinline__ void run_bwd(const BwdStage &g, const float *dY, bool dy_global, float *dOw, int img, int ql = 0, int qh = H0(S), int pol = 0, int poh = H0(S)) {
     constexpr int W = SH[S].W, C = SH[S].C0, KS = SH[S].KS, K = SH[S].K, PD = K / 2, PRE = SH[S].pre, POOL = SH[S].pool, POST = SH[S].post;
     constexpr int CV = vw_of(C), CQ = C / CV, RSO = RSOw(S), NW = POOL ? 4 : 1;
@@ -1062,11 +1139,11 @@ __device__ __forceinline__ void run_bwd(const BwdStage &g, const float *dY, bool
             if (PRE) fv[w] = gload<CV>(g.Fpre + e1 + cell[w]);
         }
         // ---- arithmetic + stores
-        if (Rb && own) gstore<CV>(Rb + zo, gq.v);
+        if (Rb && own) gstore<CV, POL>(Rb + zo, gq.v);
         if (POST) {
 #pragma unroll
             for (int q = 0; q < CV; q++) gq.v[q] *= fpost.v[q];
-            if (own) gstore<CV>(Qb + zo, gq.v);
+            if (own) gstore<CV, POL>(Qb + zo, gq.v);
         }
         int arg[CV];
 #pragma unroll
@@ -1083,11 +1160,11 @@ __device__ __forceinline__ void run_bwd(const BwdStage &g, const float *dY, bool
             float d[CV];
 #pragma unroll
             for (int q = 0; q < CV; q++) d[q] = !POOL ? gq.v[q] : (POOL == L_AVGPOOL ? gq.v[q] / 4.0f : (arg[q] == w ? gq.v[q] : 0.f));
-            if (POOL && own) gstore<CV>(Pb + e1 + cell[w], d);
+            if (POOL && own) gstore<CV, POL>(Pb + e1 + cell[w], d);
             if (PRE) {
 #pragma unroll
                 for (int q = 0; q < CV; q++) d[q] *= fv[w].v[q];
-                if (own) gstore<CV>(g.O + e1 + cell[w], d);
+                if (own) gstore<CV, POL>(g.O + e1 + cell[w], d);
             }
             const int wy = ir * KS + (w >> 1), wx = j0 * KS + (w & 1);
             lstore<CV>(dOw + (wy + PD) * RSO + (wx + PD) * C + c, d);      // one ds_write_b128 / b64 (CV scalar writes at a lane stride of CV floats are CV-way bank conflicts)
@@ -1391,7 +1468,7 @@ __device__ __forceinline__ void stage_bwd_b(const BwdArgs &p, float *L, int img,
         if (!(LAB_SKIP & 16)) for (int e = threadIdx.x * 4; e < bdo_size() + bxw_size(); e += CS_BTHREADS * 4) *reinterpret_cast<float4 *>(dOw + e) = make_float4(0.f, 0.f, 0.f, 0.f);
         lds_barrier();
         CS_STAMP(1 + 8 * S);
-        if (!(LAB_SKIP & 4)) run_bwd<S, true, CS_BTHREADS>(g, dY, dy_global, dOw, img, ql, qh, pol, poh);
+        if (!(LAB_SKIP & 4)) run_bwd<S, true, CS_BTHREADS, ST_BWD>(g, dY, dy_global, dOw, img, ql, qh, pol, poh);
         CS_STAMP(2 + 8 * S);
         // round 6: the dX-conv filters (requested in the kernel's first instructions) go to LDS HERE, behind the last stage's run backward: the first
         // consumer is that stage's dX convolution one barrier further on, and placed at the kernel's start the wait for them was a round trip of its own in
@@ -1431,12 +1508,13 @@ __device__ __forceinline__ void stage_bwd_b(const BwdArgs &p, float *L, int img,
             const int n = (ih - il) * rowX;
             const float *src = dXb + (il - xl) * rowX;
             float *x = g.X + ((long)img * H + il) * rowX, *x2 = g.DXS ? g.DXS + ((long)img * H + il) * rowX : nullptr;
+            constexpr int POL = S == 0 ? ST_PLAIN : ST_BWD;       // stage 0's dX belongs to the layer in front of the stack
             if ((rowX & 3) == 0) {
                 for (int e = threadIdx.x * 4; e < n; e += CS_BTHREADS * 4) {
                     const float4 v = *reinterpret_cast<const float4 *>(src + e);
-                    *reinterpret_cast<float4 *>(x + e) = v; if (x2) *reinterpret_cast<float4 *>(x2 + e) = v;
+                    gstore4<POL>(x + e, v); if (x2) gstore4<POL>(x2 + e, v);
                 }
-            } else for (int e = threadIdx.x; e < n; e += CS_BTHREADS) { const float v = src[e]; x[e] = v; if (x2) x2[e] = v; }
+            } else for (int e = threadIdx.x; e < n; e += CS_BTHREADS) { const float v = src[e]; gstore1<POL>(x + e, v); if (x2) gstore1<POL>(x2 + e, v); }
         }
         CS_STAMP(7 + 8 * S);
         stage_bwd_b<S - 1>(p, L, img, band, dXb, false, vf);
