@@ -171,7 +171,7 @@ __global__ void __launch_bounds__(BLK) k_u8norm(const uint8_t *__restrict__ src,
 __global__ void __launch_bounds__(BLK) k_stage_batch(const uint8_t *__restrict__ src, float *dst, long n, float mean, float scale,
                                                      const uint32_t *__restrict__ lab_src, uint32_t *lab_dst, int nlab, int vec) {
     const long t0 = (long)blockIdx.x * BLK + threadIdx.x, step = (long)gridDim.x * BLK;
-    if (t0 < nlab) lab_dst[t0] = lab_src[t0];
+    for (long z = t0; z < nlab; z += step) lab_dst[z] = lab_src[z];   // grid-strided as the pixels: the grid is capped at MAX_WG workgroups
     if (vec) {
         const long n4 = n >> 2;
         for (long z = t0; z < n4; z += step) {
@@ -283,6 +283,7 @@ int t4k_bias(const float *B, float *O, int N, int E0, t4k_stream_t s) {
 }
 int t4k_u8_normalize(const uint8_t *src, float *dst, long n, float mean, float scale, t4k_stream_t s) {
     T4K_REQUIRE_INIT(); if (n <= 0) return T4K_OK;
+    if (!src || !dst) return fail(T4K_ERR_ARG, "t4k_u8_normalize: null tensor");
     T4K_LAUNCH(k_u8norm, dim3(grid_for(n)), dim3(BLK), 0, S(s), src, dst, n, mean, scale);
     T4K_LAUNCH_CHECK(); return T4K_OK;
 }
@@ -309,6 +310,7 @@ int t4k_copy_mask(const float *T, const float *MASK, float *OUT, float *IN, long
 }
 int t4k_onehot(const uint32_t *label, float *hot, int N, int E, t4k_stream_t s) {
     T4K_REQUIRE_INIT(); if (N <= 0 || E <= 0) return T4K_OK;
+    if (!label || !hot) return fail(T4K_ERR_ARG, "t4k_onehot: null tensor");
     T4K_LAUNCH(k_onehot, dim3(grid_for((long)N * E)), dim3(BLK), 0, S(s), label, hot, N, E);
     T4K_LAUNCH_CHECK(); return T4K_OK;
 }

@@ -125,7 +125,9 @@ __global__ void __launch_bounds__(BLK) k_logsoftmax(const float *__restrict__ I,
     for (int c = 0; c < C; c++) o[c] -= ls;
 }
 
-// hit count: per-sample FIRST arg-max, then sum of hot[n, argmax]; single block, exact.  G lanes share a sample (G = 1 for class-count
+// hit count: per-sample arg-max as the reference scans for it (Model::hit nn/loss.cpp: m = o[0], i = 0, then o[e] > m) - the FIRST maximum of the
+// elements that are no NaN, -inf included (a lane starts below every value it can take, so [-inf, -FLT_MAX] picks 1 and an all -inf row keeps 0), and class 0
+// whenever o[0] is a NaN (nothing displaces it) - then sum of hot[n, argmax]; single block, exact.  G lanes share a sample (G = 1 for class-count
 // sized rows: 256 samples per pass, every thread scans its own row; wider rows take 8 or 64 lanes) - the one-wave-per-sample form this
 // replaces walked a 128 x 10 batch in 32 dependent passes (31 us, the longest kernel of a dataset-fed LeNet step).
 template <int G>
@@ -137,7 +139,7 @@ __global__ void __launch_bounds__(BLK) k_hit(const float *__restrict__ out, cons
     for (int n0 = 0; n0 < N; n0 += BLK / G) {            // uniform trip count: the shuffles below need every lane of the wave
         const int n = n0 + g; const bool live = n < N;
         const float *o = out + (long)(live ? n : 0) * E;
-        float m = -FLT_MAX; int idx = 0x7fffffff;
+        float m = -INFINITY; int idx = 0x7fffffff;
         if (live) for (int e = l; e < E; e += G) { float v = o[e]; if (v > m) { m = v; idx = e; } }   // first max within lane
 #pragma unroll
         for (int off = G >> 1; off > 0; off >>= 1) {
@@ -147,9 +149,9 @@ __global__ void __launch_bounds__(BLK) k_hit(const float *__restrict__ out, cons
         if (label) {
             uint32_t m = live ? label[n] : 0u; if (m >= (uint32_t)E) m = 0;
             if (live) for (int e = l; e < E; e += G) hot_w[(long)n * E + e] = (e == (int)m) ? 1.0f : 0.0f;
-            if (live && l == 0) { if (idx >= E) idx = 0; local += (idx == (int)m) ? 1 : 0; }
+            if (live && l == 0) { if (idx >= E || o[0] != o[0]) idx = 0; local += (idx == (int)m) ? 1 : 0; }
         } else
-        if (live && l == 0) { if (idx >= E) idx = 0; local += (int)hot[(long)n * E + idx]; }
+        if (live && l == 0) { if (idx >= E || o[0] != o[0]) idx = 0; local += (int)hot[(long)n * E + idx]; }
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) local += __shfl_xor(local, off, 64);
