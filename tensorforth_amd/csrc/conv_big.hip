@@ -12,11 +12,11 @@
 // are decomposed into (n, y, x) once.  NHWC makes every operand row a contiguous 128-byte run: all global loads are
 // coalesced 16-byte loads, out-of-image taps load nothing and stage zeros.
 // Arithmetic restates k_conv2d / k_dconv2d (src/nn/nmath.tcu:34-104, 211-338) incl. the flipped-filter dX.
-#include "conv_types.h"
+// The 4-wave dF slab pipeline of k_convbig_df lives in conv_tile.h (conv_df_tile4), shared with conv_geo.hip's k_geo_dft.
+#include "conv_tile.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 // raw buffer descriptor over [p, p + bytes): offsets are bytes, a lane offset >= bytes is out of range (loads return / the LDS-DMA stores zeros)
 __device__ __forceinline__ i32x4 buf_srd(const void *p, unsigned bytes) {
@@ -24,7 +24,6 @@ __device__ __forceinline__ i32x4 buf_srd(const void *p, unsigned bytes) {
     i32x4 r; r[0] = (int)(unsigned)a; r[1] = (int)((unsigned)(a >> 32) & 0xFFFFu); r[2] = (int)bytes; r[3] = 0x00020000;
     return r;
 }
-typedef float v4f __attribute__((ext_vector_type(4)));
 
 constexpr int BK = 32, CH = BK / 4, SW = 64 / BK, NC = BK / 8;
 
@@ -512,35 +511,14 @@ __global__ void __launch_bounds__(256) k_convbig_df(CdP p) {
         for (int pp = 0; pp < PB; pp++) *reinterpret_cast<v4f *>(b + sob[pp]) = rb[pp];
     };
     f32x16 acc0, acc1;
-#pragma unroll
-    for (int r = 0; r < 16; r++) { acc0[r] = 0.f; acc1[r] = 0.f; }
-    if (nst > 0) { load_tiles(0); store_tiles(0); }
-    __syncthreads();
-    for (int kt = 0; kt < nst; kt++) {
-        const int buf = kt & 1;
-        if (kt + 1 < nst) load_tiles(kt + 1);
-        const float *a = sA + buf * BM * BK, *b = sB + buf * BN * BK;
-        const int ra_ = wm * 32 + l31, rb_ = wn * 32 + l31;
-#pragma unroll
-        for (int ci = 0; ci < NC; ci++) {
-            float av[4], bv[4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) { av[j] = a[(ci * 8 + 4 * h + j) * BM + ra_]; bv[j] = b[(ci * 8 + 4 * h + j) * BN + rb_]; }
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[0], bv[0], acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[1], bv[1], acc1, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[2], bv[2], acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[3], bv[3], acc1, 0, 0, 0);
-        }
-        if (kt + 1 < nst) store_tiles(buf ^ 1);
-        __syncthreads();
-    }
+    conv_df_tile4(sA, sB, nst, acc0, acc1, load_tiles, store_tiles);
     // partial slab [slice][row = (ci*K+ky)*K+kx][co]  (the fold's layout, without a bias row)
     const int co = n0 + wn * 32 + l31;
     if (co < p.C0) {
         const long nrow = (long)p.C1 * KK;
 #pragma unroll
         for (int r = 0; r < 16; r++) {
-            const int ci = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+            const int ci = m0 + wm * 32 + frag_row(r, h);
             if (ci < p.C1) p.part[((long)blockIdx.x * nrow + ((long)ci * KK + tap)) * p.C0 + co] = acc0[r] + acc1[r];
         }
     }
@@ -1014,9 +992,7 @@ int launch_conv_big_df(int K, int S, int P, hipStream_t hs, const float *I, cons
         // 1: 64-pixel stages, one workgroup per CU; 2: 32-pixel stages, two per CU (twice the slices, twice the slab bytes)
         const int bkp = (lab.dfw == 2 || lab.dfw == 4) ? 32 : 64;
         const long slots = (long)st().cu_count * (bkp == 32 ? 2 : 1);
-        long ns = slots / tilesw; if (ns < 1) ns = 1;
-        long pp = (npix + ns - 1) / ns; pp = (pp + bkp - 1) / bkp * bkp; if (pp < 4 * bkp) pp = 4 * bkp;
-        ns = (npix + pp - 1) / pp;
+        const auto [pp, ns] = df_slices(npix, slots / tilesw, bkp, 4 * bkp);
         if ((size_t)ns * C1 * KK * C0 <= part_floats) {
             Cdw q = { I, DO, part, H0, W0, C1, C0, (int)pp, (int)ns, cit, ctl, kks, npix };
             conv_plan_note("dfw<%d,%d>x%d", ciw, ntw, (int)ns);
@@ -1043,9 +1019,7 @@ int launch_conv_big_df(int K, int S, int P, hipStream_t hs, const float *I, cons
         const int tp2 = (lab.df8_tp2 && C1 == 32) ? 1 : 0;   // two taps per 64-row tile
         const int kks = tp2 ? (KK + 1) / 2 : KK;
         const int tiles8 = kks * ci_tiles * co_tiles;
-        long ns = slots / tiles8; if (ns < 1) ns = 1;
-        long pp = (npix + ns - 1) / ns; pp = (pp + bkp - 1) / bkp * bkp; if (pp < 4 * bkp) pp = 4 * bkp;
-        ns = (npix + pp - 1) / pp;
+        const auto [pp, ns] = df_slices(npix, slots / tiles8, bkp, 4 * bkp);
         if ((size_t)ns * C1 * KK * C0 > part_floats) return 0;
         const int ctl = ci_tiles * co_tiles;
         Cd8 q = { I, DO, st().d_zero, part, N, H1, W1, C1, H0, W0, C0, (int)pp, ci_tiles, npix, lab.df8_dbg, (int)ns, ctl, tp2 };
@@ -1068,13 +1042,11 @@ int launch_conv_big_df(int K, int S, int P, hipStream_t hs, const float *I, cons
     }
     // the 4-wave register-staged kernel (k_convbig_df): workgroups per CU in total -> slices
     const int tiles = KK * ci_tiles * co_tiles;
-    long nslice = ((long)lab.df_wpc * st().cu_count + tiles - 1) / tiles; if (nslice < 1) nslice = 1;
-    long pps = (npix + nslice - 1) / nslice; pps = (pps + BK - 1) / BK * BK; if (pps < 8 * BK) pps = 8 * BK;
-    nslice = (npix + pps - 1) / pps;
+    auto [pps, nslice] = df_slices(npix, ((long)lab.df_wpc * st().cu_count + tiles - 1) / tiles, BK, 8 * BK);
     // Workgroups go to XCD (linear block id % 8) and the grid is slice-major: with a slice count that is a multiple of 8 every
     // tap / channel tile of one pixel slice lands on the SAME XCD, so the K*K-fold re-read of I and dO is served by that XCD's
     // L2 instead of crossing the fabric once per tap (a trailing slice may be empty: it writes a zero slab)
-    if (lab.df_xcd && nslice >= 8) { nslice = (nslice + 7) / 8 * 8; pps = (npix + nslice - 1) / nslice; pps = (pps + BK - 1) / BK * BK; }
+    if (lab.df_xcd && nslice >= 8) { nslice = (nslice + 7) / 8 * 8; pps = df_slices(npix, nslice, BK, 0).pps; }
     if ((size_t)nslice * C1 * KK * C0 > part_floats) return 0;
     conv_plan_note("dfx%d", (int)nslice);
     CdP p = { I, DO, part, N, H1, W1, C1, H0, W0, C0, (int)pps, ci_tiles };

@@ -14,17 +14,13 @@
 // A k-step is 32 channels of one tap: the A gather is one contiguous run per pixel (16-byte loads when the channel count is a multiple of 4 and the
 // tensor sits on 16 bytes, dwords otherwise), a tap outside the image or a channel past the end contributes zeros by predicate - nothing outside the
 // tensors is read.  Row / column validity of every tap is two 7-bit masks per pixel, worked out once per tile.
-#include "conv_types.h"
+// k_geo_dft's stage pipeline is conv_big.hip's k_convbig_df's, written once in conv_tile.h (conv_df_tile4); admission and the slice planner are shared with
+// conv_group.hip (conv_types.h).
+#include "conv_tile.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float v4f __attribute__((ext_vector_type(4)));
-
 constexpr int GBK = 32, GCH = GBK / 4, GSW = 64 / GBK, GNC = GBK / 8, GBM = 128;
-constexpr size_t GEO_WS_BYTES = (size_t)32 << 20;       // the dF slabs live in the first half of a stream's workspace (colsum_add owns the second): ONE slab may fill it
-constexpr size_t GEO_SLAB_AIM = (size_t)8 << 20;        // ... but the slice count shrinks until the slabs fit 8 MiB (conv.hip's ws / 8): what the fold reads back stays cache-sized
-constexpr int GEO_DF_WG = 1024;                         // workgroups the dF launch aims at
 
 struct GeoP {
     const float *X, *F, *B;            // gathered tensor (forward: I, dX: dO), filter [C1][K][K][C0], bias (forward)
@@ -211,7 +207,7 @@ __global__ void __launch_bounds__(256) k_geo(GeoP p) {
         if (kt + 1 < nst) store_tiles(buf ^ 1);
         __syncthreads();
     }
-    // epilogue: col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * h; the bias rides here (forward)
+    // epilogue: col = lane & 31, row = frag_row(r, h); the bias rides here (forward)
 #pragma unroll
     for (int mt = 0; mt < MT; mt++)
 #pragma unroll
@@ -221,7 +217,7 @@ __global__ void __launch_bounds__(256) k_geo(GeoP p) {
             const float bias = (!BWD && p.B) ? p.B[gn] : 0.f;
 #pragma unroll
             for (int r = 0; r < 16; r++) {
-                const int op = s_opix[wm * (BM / 2) + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h];
+                const int op = s_opix[wm * (BM / 2) + mt * 32 + frag_row(r, h)];
                 if (op >= 0) { const float v = acc[mt][nt][r] + bias; p.Y[(long)op * Cout + gn] = v; if (p.Y2) p.Y2[(long)op * Cout + gn] = v; }
             }
         }
@@ -332,7 +328,7 @@ __global__ void __launch_bounds__(256) k_geo_df(GeoD p) {
 
 // the same slabs for many input channels (C1 % 4 == 0, C1 >= 32, everything on 16 bytes): a tile's 64 rows are 64 channels of ONE tap, so a row of the A stage is
 // one contiguous run of the input pixel under that tap - 16-byte loads instead of the dwords of k_geo_df (conv_big.hip's k_convbig_df with the geometry in
-// arguments).  grid.y = taps x channel tiles, plus ONE tile whose first row is all ones: the bias row.
+// arguments: the same conv_df_tile4, conv_tile.h).  grid.y = taps x channel tiles, plus ONE tile whose first row is all ones: the bias row.
 __global__ void __launch_bounds__(256) k_geo_dft(GeoD p, int ci_tiles) {
     constexpr int BM = 64, BN = 64, BKP = 32;
     __shared__ __attribute__((aligned(16))) float sA[2][BKP * BM];
@@ -377,34 +373,13 @@ __global__ void __launch_bounds__(256) k_geo_dft(GeoD p, int ci_tiles) {
         }
     };
     f32x16 acc0, acc1;
-#pragma unroll
-    for (int r = 0; r < 16; r++) { acc0[r] = 0.f; acc1[r] = 0.f; }
-    if (nst > 0) { load_tiles(0); store_tiles(0); }
-    __syncthreads();
-    for (int kt = 0; kt < nst; kt++) {
-        const int buf = kt & 1;
-        if (kt + 1 < nst) load_tiles(kt + 1);
-        const float *a = sA[buf], *b = sB[buf];
-        const int ra_ = wm * 32 + l31, rb_ = wn * 32 + l31;
-#pragma unroll
-        for (int ci = 0; ci < BKP / 8; ci++) {
-            float av[4], bv[4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) { av[j] = a[(ci * 8 + 4 * h + j) * BM + ra_]; bv[j] = b[(ci * 8 + 4 * h + j) * BN + rb_]; }
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[0], bv[0], acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[1], bv[1], acc1, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[2], bv[2], acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[3], bv[3], acc1, 0, 0, 0);
-        }
-        if (kt + 1 < nst) store_tiles(buf ^ 1);
-        __syncthreads();
-    }
+    conv_df_tile4(&sA[0][0], &sB[0][0], nst, acc0, acc1, load_tiles, store_tiles);
     const int co = n0 + wn * 32 + l31;
     if (co < p.C0) {
         const long ntot = (long)(ntaps + 1) * p.C0;
 #pragma unroll
         for (int r = 0; r < 16; r++) {
-            const int m = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h, ci = m0 + m;
+            const int m = wm * 32 + frag_row(r, h), ci = m0 + m;
             if (bias_tile) { if (m == 0) p.part[(long)blockIdx.x * ntot + (long)ntaps * p.C0 + co] = acc0[r] + acc1[r]; }
             else if (ci < p.C1) p.part[(long)blockIdx.x * ntot + ((long)ci * KK + tap) * p.C0 + co] = acc0[r] + acc1[r];
         }
@@ -420,16 +395,8 @@ struct GeoPlan {
 };
 // admission (who: the entry's name for the message) and the plan.  T4K_ERR_ARG: an extent below 1; T4K_ERR_UNSUPPORTED: a geometry outside the admitted set
 int geo_plan(GeoPlan &g, const char *who, int N, int H1, int W1, int C1, int C0, int K, int S, int P, int D, bool aligned, bool db_adjacent) {
-    if (N < 1 || H1 < 1 || W1 < 1 || C1 < 1 || C0 < 1) return fail(T4K_ERR_ARG, "%s: an extent below 1 (N=%d H1=%d W1=%d C1=%d C0=%d)", who, N, H1, W1, C1, C0);
-    if (K < 1 || K > 7 || S < 1 || S > 4 || D < 1 || D > 4 || P < 0 || P > D * (K - 1))
-        return fail(T4K_ERR_UNSUPPORTED, "%s: kernel_size=%d stride=%d padding=%d dilation=%d not supported (K 1..7, S 1..4, D 1..4, 0 <= P <= D(K-1))", who, K, S, P, D);
-    const int eh = H1 + 2 * P - D * (K - 1) - 1, ew = W1 + 2 * P - D * (K - 1) - 1;
-    if (eh < 0 || ew < 0) return fail(T4K_ERR_UNSUPPORTED, "%s: the %dx%d window (dilation %d) does not fit the padded %dx%d image", who, K, K, D, H1 + 2 * P, W1 + 2 * P);
-    g.H0 = eh / S + 1; g.W0 = ew / S + 1;
-    const long np0 = (long)N * g.H0 * g.W0, np1 = (long)N * H1 * W1;
-    if (np0 >= (1L << 31) || np1 >= (1L << 31)) return fail(T4K_ERR_UNSUPPORTED, "%s: 2^31 pixels or more", who);
-    const long ntot = ((long)C1 * K * K + 1) * C0;
-    if (ntot * (long)sizeof(float) > (long)GEO_WS_BYTES) return fail(T4K_ERR_UNSUPPORTED, "%s: one dF | dB slab (%ld floats) does not fit the workspace", who, ntot);
+    const int rc = conv_geo_admit(who, N, H1, W1, C1, C0, K, S, P, D, nullptr, &g.H0, &g.W0); if (rc != T4K_OK) return rc;
+    const long np0 = (long)N * g.H0 * g.W0, np1 = (long)N * H1 * W1, ntot = ((long)C1 * K * K + 1) * C0;
     if (((long)C1 * K * K + 64) / 64 > 65535 || (C0 + 63) / 64 > 65535 ||                                  // the dF grid's y and z, the 1-D grids of forward and dX
         ((np0 + GBM - 1) / GBM) * ((C0 + 63) / 64) >= (1L << 31) || ((np1 + GBM - 1) / GBM + 16) * ((C1 + 63) / 64) >= (1L << 31))
         return fail(T4K_ERR_UNSUPPORTED, "%s: more tiles than a launch takes", who);
@@ -439,18 +406,9 @@ int geo_plan(GeoPlan &g, const char *who, int N, int H1, int W1, int C1, int C0,
     g.dx_bn = (g.dx_v && C1 > 64) ? 128 : 64;
     g.df_vb = aligned && C0 % 4 == 0;
     g.df_tap = g.df_vb && C1 % 4 == 0 && C1 >= 32;              // below 32 channels a tap fills less than half of a tile's rows: (c1, tap) rows side by side then
-    // slices: enough that ~GEO_DF_WG workgroups run, whole 32-pixel stages each, no more than the workspace holds
     const long tiles = (g.df_tap ? (long)K * K * ((C1 + 63) / 64) + 1 : ((long)C1 * K * K + 1 + 63) / 64) * ((C0 + 63) / 64);
-    long want = (GEO_DF_WG + tiles - 1) / tiles;
-    const long fit = (long)(GEO_SLAB_AIM / sizeof(float)) / ntot;
-    if (want > fit) want = fit;
-    if (want < 1) want = 1;
-    long pps = (np0 + want - 1) / want; pps = (pps + 31) / 32 * 32;
-    g.pps = (int)std::min(pps, (long)0x7fffffe0);
-    g.nslice = (int)((np0 + g.pps - 1) / g.pps);
-    // k_fold_add walks whole slabs into ONE destination: it serves up to 32 slices when DB lies right behind DF (a layer's gradient block); otherwise the
-    // wave-per-output fold splits the slab between the two
-    g.fold = (g.nslice <= 32 && db_adjacent) ? 1 : 2;
+    const SlabPlan sp = slab_plan(np0, tiles, ntot, db_adjacent, 0x7fffffe0);     // (GeoD::pps is an int)
+    g.pps = (int)sp.pps; g.nslice = sp.nslice; g.fold = sp.fold;
     return T4K_OK;
 }
 
@@ -471,8 +429,6 @@ void launch_geo(const GeoP &p, bool va, bool vb, int bn, hipStream_t hs) {
     if constexpr (BWD) with_flags([&](auto v) { launch_lds<k_geo<BWD, v.value, v.value, 64>>(grid, dim3(256), lds, hs, p); }, va);
     else               with_flags([&](auto a, auto b) { launch_lds<k_geo<BWD, a.value, b.value, 64>>(grid, dim3(256), lds, hs, p); }, va, vb);
 }
-
-bool all16(const void *a, const void *b, const void *c = nullptr, const void *d = nullptr) { return aligned16(a) && aligned16(b) && aligned16(c) && aligned16(d); }
 
 } // namespace
 
@@ -517,7 +473,7 @@ int t4k_conv2d_geo_bwd(const float *I, const float *DO, float *DX, float *DX2, c
     if (H0 != g.H0 || W0 != g.W0) return fail(T4K_ERR_ARG, "t4k_conv2d_geo_bwd: output %dx%d, the geometry gives %dx%d", H0, W0, g.H0, g.W0);
     hipStream_t hs = t4k::S(s);
     if (train && DF) {                                           // stage 1 reads I, which DX2 may overwrite: slabs, then their fold in slice order
-        if (st().ws_bytes / 2 < GEO_WS_BYTES) return fail(T4K_ERR_NOMEM, "t4k_conv2d_geo_bwd: workspace");
+        if (st().ws_bytes / 2 < CONV_WS_BYTES) return fail(T4K_ERR_NOMEM, "t4k_conv2d_geo_bwd: workspace");
         float *part = ws_for(s);
         const int ntaps = C1 * K * K, ndf = ntaps * C0, ntot = ndf + C0;
         GeoD d = { I, DO, part, N, H1, W1, C1, H0, W0, C0, K, S, P, D, g.pps };

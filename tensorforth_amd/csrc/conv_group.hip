@@ -15,9 +15,6 @@
 
 namespace {
 
-constexpr size_t GRP_WS_BYTES = (size_t)32 << 20;       // the dF slabs live in the first half of a stream's workspace, as conv_geo.hip's: ONE slab may fill it
-constexpr size_t GRP_SLAB_AIM = (size_t)8 << 20;        // ... but the slice count shrinks until the slabs fit 8 MiB
-constexpr int GRP_DF_WG = 1024;                         // workgroups the dF launch aims at
 constexpr int GRP_MAX_WG = 4096;                        // forward / dX: the grid walks the tiles with this stride at most
 
 // the load paths (the template argument of every kernel): how a thread's output channels and the input channels under them are fetched
@@ -258,21 +255,11 @@ struct GrpPlan {
     int cll, nps, nslice, fold; long pps;   // dF: log2 channel lanes, pixel sub-slices per workgroup, slices, pixels per slice, the fold (1 fold_add, 2 df_fold)
 };
 // admission (who: the entry's name for the message) and the plan.  T4K_ERR_ARG: an extent below 1; T4K_ERR_UNSUPPORTED: a geometry or a group count outside
-// the admitted set.  Every product is formed in 64 bits: the extents may be anything an int holds
+// the admitted set (conv_geo_admit, conv_types.h, shared with conv_geo.hip)
 int grp_plan(GrpPlan &g, const char *who, int N, int H1, int W1, int C1, int C0, int K, int S, int P, int D, int G, bool aligned, bool db_adjacent) {
-    if (N < 1 || H1 < 1 || W1 < 1 || C1 < 1 || C0 < 1) return fail(T4K_ERR_ARG, "%s: an extent below 1 (N=%d H1=%d W1=%d C1=%d C0=%d)", who, N, H1, W1, C1, C0);
-    if (K < 1 || K > 7 || S < 1 || S > 4 || D < 1 || D > 4 || P < 0 || P > D * (K - 1))
-        return fail(T4K_ERR_UNSUPPORTED, "%s: kernel_size=%d stride=%d padding=%d dilation=%d not supported (K 1..7, S 1..4, D 1..4, 0 <= P <= D(K-1))", who, K, S, P, D);
-    if (G < 1 || C1 % G != 0 || C0 % G != 0) return fail(T4K_ERR_UNSUPPORTED, "%s: groups=%d not supported (1 <= G, G divides C1=%d and C0=%d)", who, G, C1, C0);
-    const long eh = (long)H1 + 2 * P - D * (K - 1) - 1, ew = (long)W1 + 2 * P - D * (K - 1) - 1;
-    if (eh < 0 || ew < 0) return fail(T4K_ERR_UNSUPPORTED, "%s: the %dx%d window (dilation %d) does not fit the padded %ldx%ld image", who, K, K, D, (long)H1 + 2 * P, (long)W1 + 2 * P);
-    const long h0 = eh / S + 1, w0 = ew / S + 1, lim = 1L << 31;
-    if ((long)N * h0 >= lim || (long)N * h0 * w0 >= lim || (long)N * H1 >= lim || (long)N * H1 * W1 >= lim) return fail(T4K_ERR_UNSUPPORTED, "%s: 2^31 pixels or more", who);
-    const long np0 = (long)N * h0 * w0;
-    g.H0 = (int)h0; g.W0 = (int)w0; g.Cg1 = C1 / G; g.Cg0 = C0 / G;
-    const long rows = (long)g.Cg1 * K * K + 1;                   // (rows x C0 may pass 64 bits: divide)
-    if (rows > (long)(GRP_WS_BYTES / sizeof(float)) / C0) return fail(T4K_ERR_UNSUPPORTED, "%s: one dF | dB slab (%ld x %d floats) does not fit the workspace", who, rows, C0);
-    const long ntot = rows * C0;
+    const int rc = conv_geo_admit(who, N, H1, W1, C1, C0, K, S, P, D, &G, &g.H0, &g.W0); if (rc != T4K_OK) return rc;
+    g.Cg1 = C1 / G; g.Cg0 = C0 / G;
+    const long np0 = (long)N * g.H0 * g.W0, ntot = ((long)g.Cg1 * K * K + 1) * C0;
     g.mode = (!aligned || C0 % 4 != 0) ? GM_V1 : (g.Cg1 == 1 && g.Cg0 == 1) ? GM_DW : g.Cg0 % 4 == 0 ? GM_G4S : g.Cg1 == 1 ? GM_G4E : GM_V1;
     g.dx_v = g.mode == GM_DW;
     // dF: CL = the power of two that holds the channel groups, at most 32 (R = 256 / CL >= 8 > K - 1 rows: every tap row has a thread)
@@ -281,15 +268,8 @@ int grp_plan(GrpPlan &g, const char *who, int N, int H1, int W1, int C1, int C0,
     g.nps = (256 >> g.cll) / K;
     const long ctiles = ((long)cv + (1 << g.cll) - 1) >> g.cll;
     if (g.Cg1 > 65535 || ctiles > 65535) return fail(T4K_ERR_UNSUPPORTED, "%s: more tiles than a launch takes", who);
-    // slices: enough that ~GRP_DF_WG workgroups run, whole 32-pixel stages each, no more than the workspace holds
-    const long tiles = (long)g.Cg1 * ctiles;
-    long want = (GRP_DF_WG + tiles - 1) / tiles;
-    const long fit = (long)(GRP_SLAB_AIM / sizeof(float)) / ntot;
-    if (want > fit) want = fit;
-    if (want < 1) want = 1;
-    g.pps = ((np0 + want - 1) / want + 31) / 32 * 32;
-    g.nslice = (int)((np0 + g.pps - 1) / g.pps);
-    g.fold = (g.nslice <= 32 && db_adjacent) ? 1 : 2;           // as conv_geo.hip: k_fold_add walks whole slabs into ONE destination
+    const SlabPlan sp = slab_plan(np0, (long)g.Cg1 * ctiles, ntot, db_adjacent, 1L << 62);   // (GrpD::pps is a long: no cap)
+    g.pps = sp.pps; g.nslice = sp.nslice; g.fold = sp.fold;
     return T4K_OK;
 }
 
@@ -310,10 +290,6 @@ GrpP grp_parms(const GrpPlan &g, bool bwd, int vw, const float *X, const float *
     return p;
 }
 template <typename F> void with_mode(int mode, F &&f) { pick<GM_V1, GM_DW, GM_G4S, GM_G4E>(mode, f); }
-
-bool all16(const void *a, const void *b, const void *c = nullptr, const void *d = nullptr, const void *e = nullptr) {
-    return aligned16(a) && aligned16(b) && aligned16(c) && aligned16(d) && aligned16(e);
-}
 
 } // namespace
 
@@ -360,7 +336,7 @@ int t4k_conv2d_grp_bwd(const float *I, const float *DO, float *DX, float *DX2, c
     if (H0 != g.H0 || W0 != g.W0) return fail(T4K_ERR_ARG, "t4k_conv2d_grp_bwd: output %dx%d, the geometry gives %dx%d", H0, W0, g.H0, g.W0);
     hipStream_t hs = t4k::S(s);
     if (train && DF) {                                           // stage 1 reads I, which DX2 may overwrite: slabs, then their fold in slice order
-        if (st().ws_bytes / 2 < GRP_WS_BYTES) return fail(T4K_ERR_NOMEM, "t4k_conv2d_grp_bwd: workspace");
+        if (st().ws_bytes / 2 < CONV_WS_BYTES) return fail(T4K_ERR_NOMEM, "t4k_conv2d_grp_bwd: workspace");
         float *part = ws_for(s);
         const int ntot = (int)ndf + C0;
         GrpD d = { I, DO, part, N, H1, W1, C1, H0, W0, C0, g.Cg1, g.Cg0, K, S, P, D, g.mode == GM_V1 ? C0 : C0 / 4, g.cll, g.nps, g.pps,

@@ -1,5 +1,6 @@
-// conv_types.h - what the convolution units share (conv.hip, conv_few.hip, conv_big.hip, conv_img.hip, dconv.hip): every host function that crosses
-// a unit, declared once with its default arguments; the pending-fold block; the LAB switches.  Every kernel template is instantiated in exactly
+// conv_types.h - what the convolution units share (conv.hip, conv_few.hip, conv_big.hip, conv_geo.hip, conv_group.hip, conv_img.hip, dconv.hip): every host
+// function that crosses a unit, declared once with its default arguments; the pending-fold block; the LAB switches; the dF slice planners and the admission
+// of the run-time-geometry layers.  Every kernel template is instantiated in exactly
 // one unit - the one that launches it.
 #pragma once
 #include "launch.h"
@@ -94,5 +95,56 @@ struct ConvLab {
     int img_nt     = T4K_LAB_ENV("T4K_CONV_IMG_NT", 1);           // non-temporal stores of its full-size outputs
 };
 inline const ConvLab &conv_lab() { static const ConvLab v; return v; }
+
+// ---- host-side planning shared by the units that cut dF into pixel slices
+inline bool all16(const void *a, const void *b, const void *c = nullptr, const void *d = nullptr, const void *e = nullptr) {
+    return aligned16(a) && aligned16(b) && aligned16(c) && aligned16(d) && aligned16(e);
+}
+// `want_slices` (at least one) over npix pixels: pixels per slice in whole stages, at least min_pixels, and the slices that then cover npix
+struct DfSlices { long pps, n; };
+inline DfSlices df_slices(long npix, long want_slices, int stage_pixels, int min_pixels) {
+    if (want_slices < 1) want_slices = 1;
+    long pps = (npix + want_slices - 1) / want_slices;
+    pps = (pps + stage_pixels - 1) / stage_pixels * stage_pixels;
+    if (pps < min_pixels) pps = min_pixels;
+    return { pps, (npix + pps - 1) / pps };
+}
+
+// the run-time-geometry layers (conv_geo.hip, conv_group.hip): their dF | dB slabs live in the first half of a stream's workspace (colsum_add owns the
+// second) - ONE slab may fill it, but the slice count shrinks until the slabs fit 8 MiB (conv.hip's ws / 8): what the fold reads back stays cache-sized
+constexpr size_t CONV_WS_BYTES = (size_t)32 << 20, CONV_SLAB_AIM = (size_t)8 << 20;
+constexpr int CONV_DF_WG = 1024;                        // workgroups their dF launch aims at
+// slices: enough that ~CONV_DF_WG workgroups run (`tiles` per slice), whole 32-pixel stages each, no more than CONV_SLAB_AIM holds slabs of ntot floats;
+// pps_cap: what the kernel's pixels-per-slice argument holds.  k_fold_add walks whole slabs into ONE destination: it serves up to 32 slices when DB lies
+// right behind DF (a layer's gradient block); otherwise the wave-per-output fold splits the slab between the two (fold: 1 fold_add, 2 df_fold)
+struct SlabPlan { long pps; int nslice, fold; };
+inline SlabPlan slab_plan(long np0, long tiles, long ntot, bool db_adjacent, long pps_cap) {
+    const long want = std::min((CONV_DF_WG + tiles - 1) / tiles, (long)(CONV_SLAB_AIM / sizeof(float)) / ntot);
+    SlabPlan s;
+    s.pps = std::min(df_slices(np0, want, 32, 0).pps, pps_cap);
+    s.nslice = (int)((np0 + s.pps - 1) / s.pps);
+    s.fold = (s.nslice <= 32 && db_adjacent) ? 1 : 2;
+    return s;
+}
+// what both admit alike (who: the entry's name for the message; groups: the group count, null for the layer without groups).  T4K_ERR_ARG: an extent below 1;
+// T4K_ERR_UNSUPPORTED: a geometry or a group count outside the admitted set, 2^31 pixels, a slab beyond the workspace.  Every product is formed in 64
+// bits: the extents may be anything an int holds.  *H0, *W0: the output grid
+inline int conv_geo_admit(const char *who, int N, int H1, int W1, int C1, int C0, int K, int S, int P, int D, const int *groups, int *H0, int *W0) {
+    if (N < 1 || H1 < 1 || W1 < 1 || C1 < 1 || C0 < 1) return fail(T4K_ERR_ARG, "%s: an extent below 1 (N=%d H1=%d W1=%d C1=%d C0=%d)", who, N, H1, W1, C1, C0);
+    if (K < 1 || K > 7 || S < 1 || S > 4 || D < 1 || D > 4 || P < 0 || P > D * (K - 1))
+        return fail(T4K_ERR_UNSUPPORTED, "%s: kernel_size=%d stride=%d padding=%d dilation=%d not supported (K 1..7, S 1..4, D 1..4, 0 <= P <= D(K-1))", who, K, S, P, D);
+    const int G = groups ? *groups : 1;
+    if (G < 1 || C1 % G != 0 || C0 % G != 0) return fail(T4K_ERR_UNSUPPORTED, "%s: groups=%d not supported (1 <= G, G divides C1=%d and C0=%d)", who, G, C1, C0);
+    const long eh = (long)H1 + 2 * P - D * (K - 1) - 1, ew = (long)W1 + 2 * P - D * (K - 1) - 1;
+    if (eh < 0 || ew < 0) return fail(T4K_ERR_UNSUPPORTED, "%s: the %dx%d window (dilation %d) does not fit the padded %ldx%ld image", who, K, K, D, (long)H1 + 2 * P, (long)W1 + 2 * P);
+    const long h0 = eh / S + 1, w0 = ew / S + 1, lim = 1L << 31;
+    if ((long)N * h0 >= lim || (long)N * h0 * w0 >= lim || (long)N * H1 >= lim || (long)N * H1 * W1 >= lim) return fail(T4K_ERR_UNSUPPORTED, "%s: 2^31 pixels or more", who);
+    *H0 = (int)h0; *W0 = (int)w0;
+    const long rows = (long)(C1 / G) * K * K + 1;       // (rows x C0 may pass 64 bits: divide)
+    if (rows > (long)(CONV_WS_BYTES / sizeof(float)) / C0)
+        return groups ? fail(T4K_ERR_UNSUPPORTED, "%s: one dF | dB slab (%ld x %d floats) does not fit the workspace", who, rows, C0)
+                      : fail(T4K_ERR_UNSUPPORTED, "%s: one dF | dB slab (%ld floats) does not fit the workspace", who, (long)((unsigned long)rows * (unsigned long)C0));
+    return T4K_OK;
+}
 
 }

@@ -44,7 +44,7 @@ def main():
     args = ap.parse_args()
     import torch
     from tensorforth_amd.lib import load
-    h = load(); h.init(0)
+    h = load(os.environ.get("T4K_LIB") or None); h.init(0)                # T4K_LIB: another build of the library, for A/B runs
     h.lib.t4k_launch_count.restype = ctypes.c_ulonglong
     h.lib.t4k_conv_last_plan.restype = ctypes.c_char_p
     N = args.batch
