@@ -52,7 +52,8 @@ enum {
     T4K_L_NONE = 0, T4K_L_CONV, T4K_L_LINEAR, T4K_L_FLATTEN, T4K_L_RELU, T4K_L_TANH,
     T4K_L_SIGMOID, T4K_L_SELU, T4K_L_LEAKYRL, T4K_L_ELU, T4K_L_DROPOUT, T4K_L_SOFTMAX,
     T4K_L_LOGSMAX, T4K_L_AVGPOOL, T4K_L_MAXPOOL, T4K_L_MINPOOL, T4K_L_BATCHNM,
-    T4K_L_USAMPLE, T4K_L_DCONV
+    T4K_L_USAMPLE, T4K_L_DCONV,
+    T4K_L_ATTN                         /* beyond the reference's list (appended, no value moves): multi-head attention, `vector{ heads causal } linear` */
 };
 /* rand_opt: reference src/util.h:22-25 */
 enum { T4K_UNIFORM = 0, T4K_NORMAL = 1 };
@@ -610,6 +611,29 @@ int t4k_groupnorm_fwd(const float *I, float *O, float *XH, const float *W, const
  * leaves both untouched and both may be NULL.  DX is written once per element and may be DY. */
 int t4k_groupnorm_bwd(const float *W, const float *DY, const float *XH, float *STAT, float *DX,
                       float *DW, float *DB, int N, int HW, int C, int G, int train, t4k_stream_t s);
+/* multi-head scaled-dot-product attention on NHWC fp32 tokens (csrc/attention.hip): torch's scaled_dot_product_attention(q, k, v, is_causal)
+ * on qkv.reshape(B, L, 3, heads, d).  The reference has no such layer (its README lists "Transformer: developing" for v5.0).  QKV is [N, L, 3E], E = heads d, a
+ * token's channels [ Q(E) | K(E) | V(E) ], head h owning channels h d .. (h + 1) d - 1 of each E; O is [N, L, E] in the same head order; LSE is [N, heads, L].
+ * With scale = (float)(1 / sqrt((double)d)): S_ij = scale sum_k Q_ik K_jk (causal != 0: keys j <= i only), m_i = max_j S_ij, l_i = sum_j exp(S_ij - m_i),
+ * Y_ic = sum_j exp(S_ij - m_i) V_jc / l_i, LSE_i = m_i + ln l_i.  No dropout, no other mask; exp is __expf.
+ * Admission and the plan, on the host alone (no device needed; the entries call the same function).  An extent below 1, NULL out or ws_bytes < 0: T4K_ERR_ARG;
+ * d outside 4 .. 128 or d % 4 != 0, N L 3E at or above 2^31, or 4 N heads L bytes of row sums that do not fit ws_bytes: T4K_ERR_UNSUPPORTED; out is untouched then.
+ * out = { rung (1: d <= 16, 2: d <= 32, 3: d <= 64, 4: d <= 128 - the head size the kernels pad to), load path (4 = 16 bytes per lane, 1 = dwords),
+ *         query tile BQ, key tile BK, forward launches, backward launches, workgroups of the forward, workspace bytes used };
+ * aligned != 0: every pointer of the call on 16 bytes (d % 4 == 0 makes every row of every head so) */
+int t4k_attention_plan(int N, int L, int heads, int d, int causal, int aligned, long ws_bytes, int out[8]);
+/* the forward.  O and OK (where not NULL) receive the same values, each element written once: OK is the copy the backward reads once O's buffer holds dY.
+ * LSE is written once per (n, head, token).  A workgroup owns (n, head, BQ queries); K and V stream through LDS in tiles of BK keys; both products on fp32 MFMA,
+ * the online max / sum with the rescale of the running output; S and P never reach memory.  A causal call visits no key tile wholly above the diagonal.
+ * One launch; no atomics, a fixed summation order, the same bits on every call; no allocation, no synchronisation.  A NULL QKV, O or LSE: T4K_ERR_ARG.
+ * A refusal leaves a t4k_last_error text and writes nothing. */
+int t4k_attention_fwd(const float *QKV, float *O, float *OK, float *LSE, int N, int L, int heads, int d, int causal, t4k_stream_t s);
+/* its backward, the textbook one (torch autograd of the above): D_i = sum_c DY_ic OK_ic, P_ij = exp(S_ij - LSE_i) recomputed, dP_ij = sum_c DY_ic V_jc,
+ * dS_ij = P_ij (dP_ij - D_i), dV_jc = sum_i P_ij DY_ic, dQ_ik = scale sum_j dS_ij K_jk, dK_jk = scale sum_i dS_ij Q_ik.  DQKV has QKV's layout and is written
+ * once per element; it must not overlap QKV, OK or DY (an overlap of the stated extents: T4K_ERR_ARG).  Two launches: the pass that owns query tiles (D into the
+ * stream's workspace, dQ) and the pass that owns key tiles (dK, dV); no atomics, the same bits on every call; no allocation, no synchronisation. */
+int t4k_attention_bwd(const float *QKV, const float *OK, const float *DY, const float *LSE, float *DQKV,
+                      int N, int L, int heads, int d, int causal, t4k_stream_t s);
 /* k_sgd nmath.cu:419: dg=DG/Nw; beta~0: G-=lr*dg else M=b*M+(1-b)*dg, G-=lr*M; DG=0 */
 int t4k_sgd(float *G, float *DG, float *M, int Nw, float lr, float beta, long n, t4k_stream_t s);
 /* k_adam nmath.cu:438 (no bias correction, eps outside sqrt): zeroes DG */

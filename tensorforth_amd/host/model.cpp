@@ -18,6 +18,48 @@ void Model::RAND(Tensor &t, DU scale) {                 // Model::RAND model.cpp
     chk(t4k_rand(t.data, (long)t.numel, T4K_UNIFORM, -0.5f, scale * 2.0f, stream()), "rand");
 }
 
+// ---- attention, `vector{ heads causal } linear`: its own layer kind, T4K_L_ATTN, so it joins no fused group - the run, stack, head and block
+// recognisers (plan_runs, stack_at, blinear, run_backward) all name the kinds they take, and none names this one.  The layer runs t4k_attention_fwd / _bwd.
+// The entries are referenced weakly: over a C-ABI without them (the CPU oracle) the layer is admitted, shaped, printed, saved and loaded, and forward /
+// backprop refuse it - there is no host-side fallback.
+#pragma weak t4k_attention_plan
+#pragma weak t4k_attention_fwd
+#pragma weak t4k_attention_bwd
+// C = 3 heads d with a head size the kernels take: t4k_attention_plan's rule where the C-ABI has it (16-byte path, any workspace: the step's own call decides
+// those), the same rule restated where it has not
+static bool attn_admits(int N, int L, int C, int heads) {
+    if (heads < 1 || C % 3 || (C / 3) % heads) return false;
+    const int d = C / 3 / heads;
+    if (t4k_attention_plan) { int out[8]; return t4k_attention_plan(N, L, heads, d, 0, 1, 1L << 40, out) == T4K_OK; }
+    return d >= 4 && d <= 128 && d % 4 == 0 && (long)N * L * C < (1L << 31);
+}
+static int attn_fwd(Tensor &in, Tensor &out, const float *x, t4k_stream_t s) {
+    const int heads = in.iparm;
+    if (!t4k_attention_fwd) { hprintf("nn#fattention failed: nn#fattention heads=%d not supported\n", heads); return T4K_ERR_UNSUPPORTED; }
+    return chk(t4k_attention_fwd(x, out.data, in.grad[4]->data, in.mtum[4]->data, in.N(), in.H() * in.W(), heads, out.C() / heads, in.stride[0], s), "nn#fattention");
+}
+static int attn_bwd(Tensor &in, Tensor &out, const float *dy, t4k_stream_t s) {         // dX into the staging tensor, then over x: the reference's `in = dx`
+    const int heads = in.iparm;
+    if (!t4k_attention_bwd) { hprintf("nn#battention failed: nn#battention heads=%d not supported\n", heads); return T4K_ERR_UNSUPPORTED; }
+    const int rc = chk(t4k_attention_bwd(in.data, in.grad[4]->data, dy, in.mtum[4]->data, in.mtum[0]->data, in.N(), in.H() * in.W(), heads, out.C() / heads, in.stride[0], s), "nn#battention");
+    if (rc != T4K_OK) return rc;
+    return chk(t4k_copy(in.mtum[0]->data, in.data, (long)in.numel, s), "nn#battention in = dx");
+}
+// model_load: the layer has no blobs, so its line of the layer section is all the file holds of it - `heads=<h>, causal=<0|1>` replace the layer's own where
+// the channels admit them (the log-sum-exp tensor follows the head count).  false: the line is no attention line, or names heads the layer cannot have
+static bool attn_from_line(Tensor &in, const std::string &line) {
+    int heads = 0, causal = 0; char tail[16] = "";
+    if (sscanf(line.c_str(), "heads=%d, causal=%d%15s", &heads, &causal, tail) != 3 || strcmp(tail, "attentn") || (causal != 0 && causal != 1)) return false;
+    if (!attn_admits(in.N(), in.H() * in.W(), in.C(), heads)) return false;
+    if (heads != in.iparm) {
+        Store::get().free(*in.mtum[4]);
+        in.mtum[4] = &Store::get().tensor((uint64_t)in.N() * heads * in.H() * in.W());
+        in.iparm = heads;
+    }
+    in.stride[0] = (uint16_t)causal;
+    return true;
+}
+
 // ---------------------------------------------------------------- layer factory (Model::add)
 Model &Model::add(int fn, uint32_t n, DU bias, uint16_t *opt) {
     Tensor &in = at(-1);
@@ -132,6 +174,20 @@ Model &Model::add(int fn, uint32_t n, DU bias, uint16_t *opt) {
         in.iparm = me;
         in.stride[0] = k; in.stride[1] = 1; in.stride[2] = 1; in.stride[3] = 1;
         layer.push_back(&T4(in.N(), in.H() * k, in.W() * k, in.C()));
+    } break;
+    case T4K_L_ATTN: {
+        // `vector{ heads causal } linear`: multi-head attention over the H W tokens of a sample (the reference has none).  The 3E channels of a
+        // token are [ Q | K | V ], head h owning channels h d .. (h + 1) d - 1 of each E.  No parameters: grad[0..3] stay NULL and the optimizer's table skips the
+        // layer.  grad[4] is the copy of the output the backward reads (out.data holds dY by then), mtum[4] the log-sum-exp per (sample, head, token), mtum[0]
+        // the staging tensor the backward writes dX into before it is copied over x.  Per-sample and parameter-free: dp_bn_mode and the gradient exchange
+        // of a data-parallel run do not concern it.
+        const int C = in.C(), heads = opt ? opt[0] : 0, causal = (opt && opt[1]) ? 1 : 0, E = C / 3;
+        if (!attn_admits(in.N(), in.H() * in.W(), C, heads)) { hprintf("nn#iattention heads=%d? channels=%d\n", heads, C); return *this; }
+        in.grad[4] = &T4(in.N(), in.H(), in.W(), E);
+        in.mtum[4] = &VEC((uint64_t)in.N() * heads * in.H() * in.W());
+        in.mtum[0] = &T4(in.N(), in.H(), in.W(), C);
+        in.iparm = heads; in.stride[0] = (uint16_t)causal; in.xparm = 0;
+        layer.push_back(&T4(in.N(), in.H(), in.W(), E));
     } break;
     default: hprintf("Model#add layer %d not supported\n", fn); return *this;
     }
@@ -659,6 +715,7 @@ const float *Model::fstep(Tensor &in, Tensor &out, const float *x) {
     case T4K_L_USAMPLE:                                 // nearest: broadcast each cell to a kxk tile
         if (up_geo(in)) { up_geo_fwd(in, out, x, s); break; }
         chk(t4k_dpool(T4K_L_USAMPLE, out.data, x, in.N(), out.H(), out.W(), in.H(), in.W(), in.C(), in.stride[0], s), "nn#fupsample"); break;
+    case T4K_L_ATTN: attn_fwd(in, out, x, s); break;
     default: hprintf("nn#fstep layer=%d not supported\n", fn);
     }
     return out.data;
@@ -1023,6 +1080,7 @@ Model::Back Model::bstep(int i, Tensor &in, Tensor &out, const float *dy, bool l
         if (up_geo(in)) { up_geo_bwd(in, out, dy, s); break; }
         chk(t4k_pool(T4K_L_AVGPOOL, dy, in.data, in.N(), out.H(), out.W(), in.H(), in.W(), in.C(), in.stride[0], s), "nn#bupsample");
         in.map(T4K_SCALE, (DU)(in.stride[0] * in.stride[0])); break;
+    case T4K_L_ATTN: attn_bwd(in, out, dy, s); break;
     default: hprintf("nn#bstep layer=%d not supported\n", fn);
     }
     return { in.data };
@@ -1200,7 +1258,8 @@ Model &Model::adamw(DU lr, DU wd, DU b1, DU b2) { return gradient("adamw", OPTI_
 // Layout written by the reference: a `\\ tensorForth v4.0 model` line, one `<params><layer name>` line per layer, a blank
 // line, then for every conv / linear (w, b), batchnorm (w) and group-norm (w, b: `vector{ G } batchnorm`) tensor a `--- w.<layer>` marker line followed by the raw
 // fp32 values, and a closing `---`.  Loading into an already built model skips the layer section and reads the blobs in
-// layer order (the reference's own reload of the layer section is unfinished: `_parm` text is not Forth source).
+// layer order (the reference's own reload of the layer section is unfinished: `_parm` text is not Forth source).  An attention layer has
+// no blob: its `heads=<h>, causal=<c>attentn` line is read back into the model's attention layer at that place.
 int model_save(Model &m, const char *fname) {
     FILE *f = fopen(fname, "wb");
     if (!f) { hprintf("} => failed to open for output\n"); return 1; }
@@ -1229,9 +1288,14 @@ int model_load(Model &m, const char *fname) {
     if (m.layer.size() <= 1) {                           // nothing to load into.  The reference copies the file's layer section + " nn.load <file>" into the
         fclose(f); return 2;                             // input buffer (aio_model.cpp:183-204), which System::readline clears before any VM reads it (sys.cpp:101-108;
     }                                                    // `nn.load` is no word either): nothing is printed, nothing is loaded - observed on the reference's own VM
-    while (getline_(line) && line.length()) {}           // skip the layer section (model already built)
     std::vector<float> h;
     int err = 0;
+    // the layer section is skipped (model already built), but for an attention layer: it has no blobs, its line is rebuilt into the layer (attn_from_line)
+    for (int i = -1; getline_(line) && line.length(); i++) {
+        if (i < 0 || i + 1 >= (int)m.layer.size() || m.at(i).grad_fn != T4K_L_ATTN) continue;
+        if (!attn_from_line(m.at(i), line)) { hprintf(" model format error (attention layer %d: %s)\n", i, line.c_str()); err = 1; }
+    }
+    if (err) { fclose(f); return err; }
     auto rd = [&](Tensor &t) {
         while (getline_(line) && !line.length()) {}      // skip blank lines
         if (line.size() < 3 || line[0] != '-' || line[1] != '-' || line[2] != '-') { hprintf(" model format error"); err = 1; return; }   // aio_model.cpp:211 (no newline there either)

@@ -112,6 +112,7 @@ static std::string parm_s(Tensor &in, Tensor &out) {     // aio_model.cpp:103-14
         else o << "mtum=" << p;
         break;
     case T4K_L_USAMPLE: { const char *nm[] = {"nearest", "linear", "bilinear", "cubic"}; o << S << "x" << S << " " << nm[in.iparm & 3]; } break;
+    case T4K_L_ATTN: o << "heads=" << in.iparm << ", causal=" << S; break;     // `vector{ heads causal } linear`
     default: break;
     }
     return o.str();
@@ -126,6 +127,7 @@ std::string fmt_model(Model &m) {                        // aio_model.cpp:65-99
         o << '[' << std::setw(3) << i << "] " << LAYER_NAME[in.grad_fn] << ": " << fmt_objname(in, false);
         int sz = 0;
         for (int k = 0; k < 5; k++) sz += in.grad[k] ? (int)in.grad[k]->numel : 0;
+        if (in.grad_fn == T4K_L_ATTN) sz = 0;            // no parameters: grad[4] is the saved copy of the output
         o << " #p=" << sz << ' ';
         for (int k = 0; k < 2 && in.grad[k]; k++) o << fmt_objname(*in.grad[k], false) << ' ';
         if (in.grad[4]) o << fmt_objname(*in.grad[4], false) << ' ';
