@@ -53,7 +53,8 @@ enum {
     T4K_L_SIGMOID, T4K_L_SELU, T4K_L_LEAKYRL, T4K_L_ELU, T4K_L_DROPOUT, T4K_L_SOFTMAX,
     T4K_L_LOGSMAX, T4K_L_AVGPOOL, T4K_L_MAXPOOL, T4K_L_MINPOOL, T4K_L_BATCHNM,
     T4K_L_USAMPLE, T4K_L_DCONV,
-    T4K_L_ATTN                         /* beyond the reference's list (appended, no value moves): multi-head attention, `vector{ heads causal } linear` */
+    T4K_L_ATTN,                        /* beyond the reference's list (appended, no value moves): multi-head attention, `vector{ heads causal } linear` */
+    T4K_L_ADDNORM                      /* ... and add & norm, out = norm(x + skip), `vector{ back mode } selu` */
 };
 /* rand_opt: reference src/util.h:22-25 */
 enum { T4K_UNIFORM = 0, T4K_NORMAL = 1 };
@@ -634,6 +635,35 @@ int t4k_attention_fwd(const float *QKV, float *O, float *OK, float *LSE, int N, 
  * stream's workspace, dQ) and the pass that owns key tiles (dK, dV); no atomics, the same bits on every call; no allocation, no synchronisation. */
 int t4k_attention_bwd(const float *QKV, const float *OK, const float *DY, const float *LSE, float *DQKV,
                       int N, int L, int heads, int d, int causal, t4k_stream_t s);
+/* add & norm on NHWC fp32 tokens (csrc/addnorm.hip): out = norm(x + skip), either half optional.  The reference has neither a residual
+ * connection nor a per-token norm (its README lists "add block - residual map" as to do).  rows = N H W tokens of C contiguous floats; z = X + S (S NULL: z = X).
+ * mode 0: O = z.  mode 1, torch's layer_norm(z, (C,), W, B, eps): mean = sum_c z / C, var = sum_c (z - mean)^2 / C (centred on the token's own computed
+ * mean), rstd = 1 / sqrt(var + eps), xhat = (z - mean) rstd.  mode 2, RMS norm: rstd = 1 / sqrt(sum_c z^2 / C + eps), xhat = z rstd.  Both: O = xhat W[c] + B[c]
+ * (a B left at 0 is plain RMS norm).
+ * Admission and the plan, on the host alone (no device needed; the entries call the same function).  An extent below 1, a mode outside 0..2, NULL out or
+ * ws_bytes < 0: T4K_ERR_ARG; rows or rows C at or above 2^31, a mode != 0 with C above 8192 (16-byte path) or 2048 (dwords), or a workspace that does not
+ * hold one slab row of 2 C floats: T4K_ERR_UNSUPPORTED; out is untouched then.
+ * out = { rung (0: mode 0, flat; 1: a team of T lanes of a wave per token; 2: a workgroup per token), load path (4 = 16 bytes per lane: aligned != 0 and
+ *         C % 4 == 0; else 1 = dwords), tokens a workgroup holds at a time (0 on rung 0), lanes per token T (8, 16, 32, 64: the smallest that leaves a lane at
+ *         most 8 items of the load width; 256 on rung 2; 0 on rung 0), forward launches (1), dW | dB slab rows (one per workgroup of the backward: at most 1024
+ *         and at most what ws_bytes holds, whatever rows is; 0 on rung 0), fold kind (1: a thread per output walks the rows, 2: a wave per output; 0 on rung
+ *         0), backward launches with train (2; 1 on rung 0) };  aligned != 0: every pointer of the call on 16 bytes */
+int t4k_addnorm_plan(long rows, int C, int mode, int aligned, long ws_bytes, int out[8]);
+/* the forward.  S may be NULL; with mode 0, XH, RSTD, W and B may be NULL (they are ignored).  O and XH ([rows, C]) are written once per element, RSTD ([rows])
+ * once per token.  O may be X or S (the tensor itself: a thread stores only what it loaded, after all its loads of the token); any other overlap of an output
+ * with another operand that the pointers and extents show, a NULL X or O, eps <= 0: T4K_ERR_ARG.  One launch; no atomics, a fixed summation order, the same
+ * bits on every call; a token's results depend on that token alone, so any split of the rows gives the same bits.  No allocation, no synchronisation
+ * (legal under capture).  A refusal leaves a t4k_last_error text and writes nothing. */
+int t4k_addnorm_fwd(const float *X, const float *S, float *O, float *XH, float *RSTD, const float *W, const float *B,
+                    long rows, int C, int mode, float eps, t4k_stream_t s);
+/* its backward.  t = DY + DY2 (DY2: the gradient that arrives over a skip tapping this layer's output; NULL: none).  mode 0: DX = t.  Else g = W t,
+ * mode 1: DX = rstd (g - mean_c(g) - xhat mean_c(g xhat)), mode 2: DX = rstd (g - xhat mean_c(g xhat)); DW[c] += sum_rows t xhat, DB[c] += sum_rows t (SUMS)
+ * when train != 0 - otherwise, and with mode 0, DW and DB are untouched and may be NULL.  DX is written once per element and may be DY or DY2 (the tensor
+ * itself); any other overlap: T4K_ERR_ARG.  A workgroup leaves one row of 2 C partial sums in the first half of the stream's workspace, a second launch
+ * folds the rows in a fixed order: one launch, two with train.  The skip source of the forward receives the same DX: the caller hands it on as that
+ * layer's DY2. */
+int t4k_addnorm_bwd(const float *W, const float *DY, const float *DY2, const float *XH, const float *RSTD, float *DX,
+                    float *DW, float *DB, long rows, int C, int mode, int train, t4k_stream_t s);
 /* k_sgd nmath.cu:419: dg=DG/Nw; beta~0: G-=lr*dg else M=b*M+(1-b)*dg, G-=lr*M; DG=0 */
 int t4k_sgd(float *G, float *DG, float *M, int Nw, float lr, float beta, long n, t4k_stream_t s);
 /* k_adam nmath.cu:438 (no bias correction, eps outside sqrt): zeroes DG */

@@ -60,6 +60,42 @@ static bool attn_from_line(Tensor &in, const std::string &line) {
     return true;
 }
 
+// ---- add & norm, `vector{ back mode } selu`: out = norm(x + skip).  Its own layer kind, T4K_L_ADDNORM, so it joins no fused group - the run,
+// stack, head and block recognisers (plan_runs, stack_at, lin_kind, blinear, run_backward) all name the kinds they take, and none names this one.  The skip
+// source is the OUTPUT of an earlier layer of this kind, so this kind alone owns a skip's boundary in both directions: no other layer learns about skips.
+// in.iparm = back, in.stride[0] = mode; the layer that taps this layer's output is kept in in.stride[1] | in.stride[2] << 16 (0: untapped).
+// The entries are referenced weakly: over a C-ABI without them (the CPU oracle) the layer is admitted, shaped, printed, saved and loaded, and forward /
+// backprop refuse it - there is no host-side fallback.
+#pragma weak t4k_addnorm_plan
+#pragma weak t4k_addnorm_fwd
+#pragma weak t4k_addnorm_bwd
+static const float ADDNORM_EPS = 1.0e-5f;
+static int  an_tapper(const Tensor &in) { return (int)in.stride[1] | ((int)in.stride[2] << 16); }
+static void an_set_tapper(Tensor &in, int j) { in.stride[1] = (uint16_t)(j & 0xffff); in.stride[2] = (uint16_t)(j >> 16); }
+// a norm over C channels the kernels take: t4k_addnorm_plan's rule where the C-ABI has it (16-byte path - layer tensors sit on 256 bytes - and any
+// workspace: the step's own call decides that), the same rule restated where it has not
+static bool an_admits(long rows, int C, int mode) {
+    if (t4k_addnorm_plan) { int out[8]; return t4k_addnorm_plan(rows, C, mode, 1, 1L << 40, out) == T4K_OK; }
+    return rows < (1L << 31) && rows * C < (1L << 31) && (mode == 0 || C <= (C % 4 == 0 ? 8192 : 2048));
+}
+static int an_fwd(Tensor &in, Tensor &out, const float *x, const float *skip, t4k_stream_t s) {
+    const int mode = in.stride[0];
+    if (!t4k_addnorm_fwd) { hprintf("nn#faddnorm failed: nn#faddnorm mode=%d not supported\n", mode); return T4K_ERR_UNSUPPORTED; }
+    return chk(t4k_addnorm_fwd(x, skip, out.data, mode ? in.grad[4]->data : nullptr, mode ? in.mtum[4]->data : nullptr, mode ? in.grad[0]->data : nullptr,
+                               mode ? in.grad[1]->data : nullptr, (long)in.N() * in.H() * in.W(), in.C(), mode, ADDNORM_EPS, s), "nn#faddnorm");
+}
+static int an_bwd(Tensor &in, const float *dy, const float *dy2, int train, t4k_stream_t s) {      // dX = dz over x; the skip source reads the same tensor as its dy2
+    const int mode = in.stride[0];
+    if (!t4k_addnorm_bwd) { hprintf("nn#baddnorm failed: nn#baddnorm mode=%d not supported\n", mode); return T4K_ERR_UNSUPPORTED; }
+    return chk(t4k_addnorm_bwd(mode ? in.grad[0]->data : nullptr, dy, dy2, mode ? in.grad[4]->data : nullptr, mode ? in.mtum[4]->data : nullptr, in.data,
+                               mode ? in.grad[2]->data : nullptr, mode ? in.grad[3]->data : nullptr, (long)in.N() * in.H() * in.W(), in.C(), mode, train, s), "nn#baddnorm");
+}
+// model_load: the layer's line of the layer section must be its own, `back=<b>, mode=<m>addnorm` (the span of a skip is the model's structure, not a parameter)
+static bool an_line_ok(const Tensor &in, const std::string &line) {
+    int back = -1, mode = -1; char tail[16] = "";
+    return sscanf(line.c_str(), "back=%d, mode=%d%15s", &back, &mode, tail) == 3 && !strcmp(tail, "addnorm") && back == in.iparm && mode == (int)in.stride[0];
+}
+
 // ---------------------------------------------------------------- layer factory (Model::add)
 Model &Model::add(int fn, uint32_t n, DU bias, uint16_t *opt) {
     Tensor &in = at(-1);
@@ -188,6 +224,34 @@ Model &Model::add(int fn, uint32_t n, DU bias, uint16_t *opt) {
         in.mtum[0] = &T4(in.N(), in.H(), in.W(), C);
         in.iparm = heads; in.stride[0] = (uint16_t)causal; in.xparm = 0;
         layer.push_back(&T4(in.N(), in.H(), in.W(), E));
+    } break;
+    case T4K_L_ADDNORM: {
+        // `vector{ back mode } selu`: out = norm(x + skip) (the reference has none).  With this layer's input at index j the skip is the tensor
+        // at j - back, which must be the output of an earlier layer of this kind (a mark `vector{ 0 0 }`, a norm or an add) that no other add taps yet.
+        // mode 1 / 2: grad[0..3] = gamma (1), beta (0) and their gradients, as a group norm's - finalize, the gradient slab, grads_ready, the optimizers and a
+        // data-parallel exchange see them so; grad[4] = xhat, mtum[4] = rstd per token.  mode 0: nothing but the output.  Per token: dp_bn_mode does not
+        // concern it.
+        const int back = opt ? opt[0] : 0, mode = opt ? opt[1] : 0, j = (int)layer.size() - 1, C = in.C();
+        auto refuse = [&](const char *why) { hprintf("nn#iaddnorm back=%d mode=%d? %s\n", back, mode, why); };
+        if (mode > 2) { refuse("mode 0..2"); return *this; }
+        Tensor *src = nullptr;                          // the layer whose output is tapped
+        if (back >= 1) {
+            if (j - back < 1) { refuse("no layer there"); return *this; }
+            src = &at(j - back - 1);
+            if (src->grad_fn != T4K_L_ADDNORM) { char b[48]; snprintf(b, sizeof b, "layer %d is no addnorm", j - back - 1); refuse(b); return *this; }
+            if (!at(j - back).same_shape(in)) { refuse("shape"); return *this; }
+            if (an_tapper(*src)) { refuse("taken"); return *this; }
+        }
+        if (mode && !an_admits((long)in.N() * in.H() * in.W(), C, mode)) { char b[32]; snprintf(b, sizeof b, "channels=%d", C); refuse(b); return *this; }
+        if (mode) {
+            in.grad[0] = &VEC(C).map(T4K_FILL, 1.0f); in.grad[2] = &VEC(C).zeros();
+            in.grad[1] = &VEC(C).zeros();             in.grad[3] = &VEC(C).zeros();
+            in.grad[4] = &T4(in.N(), in.H(), in.W(), C);
+            in.mtum[4] = &VEC((uint64_t)in.N() * in.H() * in.W());
+        }
+        in.iparm = back; in.stride[0] = (uint16_t)mode; in.stride[1] = in.stride[2] = in.stride[3] = 0; in.xparm = 0;
+        if (src) an_set_tapper(*src, j);                // the producing layer's backward adds the gradient this layer leaves in at(j)
+        layer.push_back(&T4(in.N(), in.H(), in.W(), C));
     } break;
     default: hprintf("Model#add layer %d not supported\n", fn); return *this;
     }
@@ -716,6 +780,10 @@ const float *Model::fstep(Tensor &in, Tensor &out, const float *x) {
         if (up_geo(in)) { up_geo_fwd(in, out, x, s); break; }
         chk(t4k_dpool(T4K_L_USAMPLE, out.data, x, in.N(), out.H(), out.W(), in.H(), in.W(), in.C(), in.stride[0], s), "nn#fupsample"); break;
     case T4K_L_ATTN: attn_fwd(in, out, x, s); break;
+    case T4K_L_ADDNORM: {                               // the skip is the tensor `back` layers up: an addnorm output, which no forward launch writes after its own layer's
+        const int j = (int)(std::find(layer.begin(), layer.end(), &in) - layer.begin());
+        an_fwd(in, out, x, in.iparm ? at(j - in.iparm).data : nullptr, s); break;
+    }
     default: hprintf("nn#fstep layer=%d not supported\n", fn);
     }
     return out.data;
@@ -1081,6 +1149,18 @@ Model::Back Model::bstep(int i, Tensor &in, Tensor &out, const float *dy, bool l
         chk(t4k_pool(T4K_L_AVGPOOL, dy, in.data, in.N(), out.H(), out.W(), in.H(), in.W(), in.C(), in.stride[0], s), "nn#bupsample");
         in.map(T4K_SCALE, (DU)(in.stride[0] * in.stride[0])); break;
     case T4K_L_ATTN: attn_bwd(in, out, dy, s); break;
+    case T4K_L_ADDNORM: {
+        // dz = the backward of norm(x + skip) on t = dy + dy2, stored over x.  dy2 is the gradient that arrives over the skip tapping THIS layer's output: the
+        // tapping layer j' (further down, so its backward ran earlier in this pass) stored its dz into ITS input tensor at(j') with a real store - an_bwd's
+        // kernel, never lazy_copy - and the same dz is what the skip receives.  Nothing writes at(j') between that store and this read: a backward launch
+        // writes the INPUT tensors of the layers it covers (bstep's branches, blinear's groups, a fused run's Xb / Pb / Qb / Rb, a conv stack's X and DXS),
+        // its own scratch (grad[4], gx_, mtum[0]) and parameter gradients; at(j') is the input of layer j' alone, and to every launch between the two it is
+        // dy, which all of them only read (the one launch that writes its dy, the `out -= target` of the last layers, runs before any addnorm's backward
+        // and on at(-1) / at(-2) behind a softmax / sigmoid, never an addnorm's input).  So after backprop a tapped tensor holds the gradient that
+        // arrived from the layer behind it, not the sum; the summed gradient is in the input of the layer that produced it.
+        const int tap = an_tapper(in);
+        an_bwd(in, dy, tap ? at(tap).data : nullptr, train, s); break;
+    }
     default: hprintf("nn#bstep layer=%d not supported\n", fn);
     }
     return { in.data };
@@ -1259,7 +1339,8 @@ Model &Model::adamw(DU lr, DU wd, DU b1, DU b2) { return gradient("adamw", OPTI_
 // line, then for every conv / linear (w, b), batchnorm (w) and group-norm (w, b: `vector{ G } batchnorm`) tensor a `--- w.<layer>` marker line followed by the raw
 // fp32 values, and a closing `---`.  Loading into an already built model skips the layer section and reads the blobs in
 // layer order (the reference's own reload of the layer section is unfinished: `_parm` text is not Forth source).  An attention layer has
-// no blob: its `heads=<h>, causal=<c>attentn` line is read back into the model's attention layer at that place.
+// no blob: its `heads=<h>, causal=<c>attentn` line is read back into the model's attention layer at that place.  An add & norm layer saves
+// gamma and beta where it has them (mode != 0); its `back=<b>, mode=<m>addnorm` line must be the layer's own - a file with another is refused whole.
 int model_save(Model &m, const char *fname) {
     FILE *f = fopen(fname, "wb");
     if (!f) { hprintf("} => failed to open for output\n"); return 1; }
@@ -1275,6 +1356,7 @@ int model_save(Model &m, const char *fname) {
         Tensor &in = m.at(i); const int fn = in.grad_fn;
         if ((fn == T4K_L_CONV || fn == T4K_L_LINEAR || fn == T4K_L_DCONV) && in.grad[0] && in.grad[1]) { dump('w', LAYER_NAME[fn], *in.grad[0]); dump('b', LAYER_NAME[fn], *in.grad[1]); }   // (the reference skips dconv2d blobs, aio_model.cpp:170: a net it cannot run)
         else if (fn == T4K_L_BATCHNM && in.grad[0]) { dump('w', LAYER_NAME[fn], *in.grad[0]); if (norm_grp(in)) dump('b', LAYER_NAME[fn], *in.grad[1]); }   // batchnorm proper saves gamma alone, as the reference does
+        else if (fn == T4K_L_ADDNORM && in.grad[0]) { dump('w', LAYER_NAME[fn], *in.grad[0]); dump('b', LAYER_NAME[fn], *in.grad[1]); }
     }
     fprintf(f, "\n---\n");
     fclose(f);
@@ -1290,10 +1372,17 @@ int model_load(Model &m, const char *fname) {
     }                                                    // `nn.load` is no word either): nothing is printed, nothing is loaded - observed on the reference's own VM
     std::vector<float> h;
     int err = 0;
-    // the layer section is skipped (model already built), but for an attention layer: it has no blobs, its line is rebuilt into the layer (attn_from_line)
-    for (int i = -1; getline_(line) && line.length(); i++) {
-        if (i < 0 || i + 1 >= (int)m.layer.size() || m.at(i).grad_fn != T4K_L_ATTN) continue;
-        if (!attn_from_line(m.at(i), line)) { hprintf(" model format error (attention layer %d: %s)\n", i, line.c_str()); err = 1; }
+    // the layer section is skipped (model already built), but for an add & norm layer, whose line must be the layer's own (checked first: a refused file
+    // changes nothing), and an attention layer: it has no blobs, its line is rebuilt into the layer (attn_from_line)
+    std::vector<std::string> lines;
+    while (getline_(line) && line.length()) lines.push_back(line);
+    auto line_of = [&](int i) -> const std::string & { static const std::string none; return i + 1 < (int)lines.size() ? lines[i + 1] : none; };   // (lines[0] is the header)
+    for (int i = 0; i + 1 < (int)m.layer.size(); i++)
+        if (m.at(i).grad_fn == T4K_L_ADDNORM && !an_line_ok(m.at(i), line_of(i))) { hprintf(" model format error (addnorm layer %d: %s)\n", i, line_of(i).c_str()); err = 1; }
+    if (err) { fclose(f); return err; }
+    for (int i = 0; i + 1 < (int)m.layer.size() && i + 1 < (int)lines.size(); i++) {
+        if (m.at(i).grad_fn != T4K_L_ATTN) continue;
+        if (!attn_from_line(m.at(i), lines[i + 1])) { hprintf(" model format error (attention layer %d: %s)\n", i, lines[i + 1].c_str()); err = 1; }
     }
     if (err) { fclose(f); return err; }
     auto rd = [&](Tensor &t) {
@@ -1308,6 +1397,7 @@ int model_load(Model &m, const char *fname) {
         Tensor &in = m.at(i); const int fn = in.grad_fn;
         if ((fn == T4K_L_CONV || fn == T4K_L_LINEAR || fn == T4K_L_DCONV) && in.grad[0] && in.grad[1]) { rd(*in.grad[0]); if (!err) rd(*in.grad[1]); }
         else if (fn == T4K_L_BATCHNM && in.grad[0]) { rd(*in.grad[0]); if (!err && norm_grp(in)) rd(*in.grad[1]); }
+        else if (fn == T4K_L_ADDNORM && in.grad[0]) { rd(*in.grad[0]); if (!err) rd(*in.grad[1]); }
     }
     if (!err) {                                          // the blob list must end here: a closing `---` line and nothing else
         while (getline_(line) && !line.length()) {}

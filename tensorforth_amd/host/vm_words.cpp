@@ -466,6 +466,18 @@ void VM::nnop(int op) {
         MTOS().add(T4K_L_ATTN, 0, 0, opt);
         return;
     }
+    // beyond the reference ( N V -- N ): a vector{ back mode } on top of a model makes `selu` an add & norm layer, out = norm(x + skip): the skip is the
+    // tensor `back` layers further up (0: none), mode 0 no norm, 1 per-token layer norm, 2 per-token RMS norm; a missing mode cell means 0,
+    // further cells are ignored.  The reference prints "( N -- ) no param needed!" here
+    if (op == T4K_L_SELU && TOS1T() && TTOS().rank == 1 && SP() > 0 && is_m(SS(-1))) {
+        Tensor &t = TTOS();
+        std::vector<float> vo; t.to_host(vo, std::min<uint64_t>(t.numel, 2));
+        DU x = POP(); DROP(x);                           // the vector is dropped and freed, as the pool, batchnorm and attention branches do
+        uint16_t opt[4] = {0, 0, 0, 0};
+        for (size_t i = 0; i < vo.size(); i++) opt[i] = (uint16_t)(int)vo[i];
+        MTOS().add(T4K_L_ADDNORM, 0, 0, opt);
+        return;
+    }
     if (TOS1T()) {                                       // tensor ops (destructive)
         Tensor &t = TTOS();
         switch (op) {
