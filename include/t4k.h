@@ -54,7 +54,8 @@ enum {
     T4K_L_LOGSMAX, T4K_L_AVGPOOL, T4K_L_MAXPOOL, T4K_L_MINPOOL, T4K_L_BATCHNM,
     T4K_L_USAMPLE, T4K_L_DCONV,
     T4K_L_ATTN,                        /* beyond the reference's list (appended, no value moves): multi-head attention, `vector{ heads causal } linear` */
-    T4K_L_ADDNORM                      /* ... and add & norm, out = norm(x + skip), `vector{ back mode } selu` */
+    T4K_L_ADDNORM,                     /* ... and add & norm, out = norm(x + skip), `vector{ back mode } selu` */
+    T4K_L_EMBED                        /* ... and the embedding layer, token and learned position tables, `vector{ V E pos } upsample` */
 };
 /* rand_opt: reference src/util.h:22-25 */
 enum { T4K_UNIFORM = 0, T4K_NORMAL = 1 };
@@ -664,6 +665,36 @@ int t4k_addnorm_fwd(const float *X, const float *S, float *O, float *XH, float *
  * layer's DY2. */
 int t4k_addnorm_bwd(const float *W, const float *DY, const float *DY2, const float *XH, const float *RSTD, float *DX,
                     float *DW, float *DB, long rows, int C, int mode, int train, t4k_stream_t s);
+/* the embedding layer on NHWC fp32 tokens (csrc/embed.hip): a token-embedding lookup, a learned position table, or both.  The reference has
+ * no such layer.  T = N L tokens of E contiguous floats, t = n L + l.  Token mode (V >= 1): IDS[T] holds the ids as floats; valid(t) <=> x_t >= 0 and x_t < V
+ * in float compares (NaN, negatives, -0.5, V, 1e9, +-inf are not valid), id_t = (int)x_t, formed only where valid;  O[t, :] = (valid(t) ? TABLE[id_t, :] : 0)
+ * + (POS ? POS[l, :] : 0).  An id that is not valid is padding: a zero token vector, no gradient, no access (torch's embedding(padding_idx)).  Position mode
+ * (V = 0): O[t, :] = X[t, :] + POS[l, :].  TABLE is [V, E], POS [L, E].
+ * Admission and the plan, on the host alone (no device needed; the entries call the same function), a function of its arguments only.  An extent below 1 (V
+ * may be 0), T % L != 0, NULL out, ws_bytes < 0, pos outside 0..1, V = 0 with pos = 0: T4K_ERR_ARG; T E or V E at or above 2^31: T4K_ERR_UNSUPPORTED; out is
+ * untouched then.
+ * out = { rung (0: position mode; 1: token mode, P = 1, a unit adds onto DTABLE itself; 2: token mode, P > 1, partial rows and a fold), load path (4 = 16
+ *         bytes per lane: aligned != 0 and E % 4 == 0; else 1 = dwords), table rows of a slab R (16; 0 in position mode), token parts P (1 unless the
+ *         vocabulary alone gives fewer than 1024 wave units: then min(ceil(1024 / units), T / 64, min(ws_bytes, 2^31 - 1) / (4 V E)), at least 1, re-counted from whole
+ *         64-id loads per part), forward launches (1), backward launches with train (the rung; 1 in position mode), workgroups of the scatter launch (four
+ *         wave units each, a unit = R rows x 64 lanes of the load width x one part, plus ceil(L (E / width) / 16) for the dPOS role where pos != 0),
+ *         workspace bytes used (4 P V E where P > 1, else 0) };  aligned != 0: every pointer of the call on 16 bytes */
+int t4k_embed_plan(long T, int L, int V, int E, int pos, int aligned, long ws_bytes, int out[8]);
+/* the forward.  Exactly one of IDS (token mode: V >= 1, TABLE required) and X (position mode: V = 0, POS required, TABLE NULL) is non-NULL; POS NULL: no
+ * position term.  O [T, E] is written once per element and must not overlap another operand (T4K_ERR_ARG).  One launch; the id is read once per token; the
+ * output is streamed.  At most one fp32 add per element: the same bits as the rule restated in float32.  No allocation, no synchronisation (legal under
+ * capture).  A refusal leaves a t4k_last_error text, launches nothing and writes nothing. */
+int t4k_embed_fwd(const float *IDS, const float *X, const float *TABLE, const float *POS, float *O,
+                  long T, int L, int V, int E, t4k_stream_t s);
+/* its backward.  DTABLE[v, :] += sum over the valid t with id_t = v of DY[t, :], DPOS[l, :] += sum over n of DY[n L + l, :] (SUMS) when train != 0 -
+ * otherwise both are untouched and may be NULL; DPOS NULL with train: no position table.  Token mode (V >= 1, IDS required): no dX, DX is ignored and the
+ * ids are left as they are.  Position mode (V = 0, IDS NULL, DX required): DX = DY, read by the same load as the sum; DX may be DY itself.  Any other overlap
+ * of an output with another operand: T4K_ERR_ARG.  Ownership by table row: a wave unit walks its part of the ids in ascending token order and adds the dY
+ * rows of its slab in that order; rung 2 leaves [P, V, E] partial rows in the first half of the stream's workspace and a second launch adds them in part
+ * order.  A table element whose sum is exactly 0 is not written (a row no token names keeps its bits).  No atomics, the same bits on every call; no
+ * allocation, no synchronisation.  train == 0: token mode launches nothing, position mode copies DY to DX unless they are one tensor. */
+int t4k_embed_bwd(const float *IDS, const float *DY, float *DTABLE, float *DPOS, float *DX,
+                  long T, int L, int V, int E, int train, t4k_stream_t s);
 /* k_sgd nmath.cu:419: dg=DG/Nw; beta~0: G-=lr*dg else M=b*M+(1-b)*dg, G-=lr*M; DG=0 */
 int t4k_sgd(float *G, float *DG, float *M, int Nw, float lr, float beta, long n, t4k_stream_t s);
 /* k_adam nmath.cu:438 (no bias correction, eps outside sqrt): zeroes DG */

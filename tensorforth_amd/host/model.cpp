@@ -96,6 +96,40 @@ static bool an_line_ok(const Tensor &in, const std::string &line) {
     return sscanf(line.c_str(), "back=%d, mode=%d%15s", &back, &mode, tail) == 3 && !strcmp(tail, "addnorm") && back == in.iparm && mode == (int)in.stride[0];
 }
 
+// ---- the embedding layer, `vector{ V E pos } upsample`: a token table over the ids in the model's input, a learned position table, or both.
+// Its own layer kind, T4K_L_EMBED, so it joins no fused group - the run, stack, head and block recognisers all name the kinds they take, and none names this
+// one.  in.iparm = V (0: position mode), in.stride[0] = pos; grad[0] | grad[2] = TABLE T4(1, V, E, 1) and its gradient, grad[1] | grad[3] = POS T4(1, H, W, E)
+// and its gradient - whichever the mode lacks stays NULL, which finalize's slab, the optimizers' table and the .t4 blobs take cell by cell (grads_ready takes
+// either cell since this layer).  The entries are referenced weakly: over a C-ABI without them (the CPU oracle) the layer is admitted, shaped, printed, saved
+// and loaded, and forward / backprop refuse it - there is no host-side fallback.
+#pragma weak t4k_embed_plan
+#pragma weak t4k_embed_fwd
+#pragma weak t4k_embed_bwd
+// a shape the kernels take: t4k_embed_plan's rule where the C-ABI has it (16-byte path - layer tensors sit on 256 bytes - and any workspace: the step's own
+// call decides that), the same rule restated where it has not
+static bool em_admits(long T, int L, int V, int E, int pos) {
+    if (t4k_embed_plan) { int out[8]; return t4k_embed_plan(T, L, V, E, pos, 1, 1L << 40, out) == T4K_OK; }
+    return T < (1L << 31) && T * E < (1L << 31) && (long)V * E < (1L << 31);
+}
+static int em_fwd(Tensor &in, Tensor &out, const float *x, t4k_stream_t s) {
+    const int V = in.iparm;
+    if (!t4k_embed_fwd) { hprintf("nn#fembed failed: nn#fembed vocab=%d not supported\n", V); return T4K_ERR_UNSUPPORTED; }
+    return chk(t4k_embed_fwd(V ? x : nullptr, V ? nullptr : x, V ? in.grad[0]->data : nullptr, in.grad[1] ? in.grad[1]->data : nullptr, out.data,
+                             (long)in.N() * in.H() * in.W(), in.H() * in.W(), V, out.C(), s), "nn#fembed");
+}
+static int em_bwd(Tensor &in, Tensor &out, const float *dy, int train, t4k_stream_t s) {       // position mode: dX = dY over x; token mode: the ids stay
+    const int V = in.iparm;
+    if (!t4k_embed_bwd) { hprintf("nn#bembed failed: nn#bembed vocab=%d not supported\n", V); return T4K_ERR_UNSUPPORTED; }
+    return chk(t4k_embed_bwd(V ? in.data : nullptr, dy, in.grad[2] ? in.grad[2]->data : nullptr, in.grad[3] ? in.grad[3]->data : nullptr, V ? nullptr : in.data,
+                             (long)in.N() * in.H() * in.W(), in.H() * in.W(), V, out.C(), train, s), "nn#bembed");
+}
+// model_load: the layer's line of the layer section must be its own, `vocab=<V>, pos=<p>embed  ` (the 7-character name; the table sizes are the model's structure)
+static bool em_line_ok(const Tensor &in, const std::string &line) {
+    int V = -1, pos = -1, used = 0;
+    return sscanf(line.c_str(), "vocab=%d, pos=%d%n", &V, &pos, &used) == 2 && line.compare(used, std::string::npos, LAYER_NAME[T4K_L_EMBED]) == 0 &&
+           V == in.iparm && pos == (int)in.stride[0];
+}
+
 // ---------------------------------------------------------------- layer factory (Model::add)
 Model &Model::add(int fn, uint32_t n, DU bias, uint16_t *opt) {
     Tensor &in = at(-1);
@@ -252,6 +286,26 @@ Model &Model::add(int fn, uint32_t n, DU bias, uint16_t *opt) {
         in.iparm = back; in.stride[0] = (uint16_t)mode; in.stride[1] = in.stride[2] = in.stride[3] = 0; in.xparm = 0;
         if (src) an_set_tapper(*src, j);                // the producing layer's backward adds the gradient this layer leaves in at(j)
         layer.push_back(&T4(in.N(), in.H(), in.W(), C));
+    } break;
+    case T4K_L_EMBED: {
+        // `vector{ V E pos } upsample` (the reference has none).  Token mode, V >= 1: the model's first layer, its input T4[N,H,W,1] the ids as
+        // floats, the output T4[N,H,W,E].  Position mode, V = 0: anywhere, out = x + POS, same shape.  TABLE draws from [-1, 1), POS from [-0.02, 0.02) (the
+        // ViT / GPT-2 convention).
+        const int V = (int)n, E = opt ? opt[0] : 0, pos = opt ? opt[1] : 0, C = in.C();
+        auto refuse = [&](const char *why) { hprintf("nn#iembed vocab=%d dim=%d pos=%d? %s\n", V, E, pos, why); };
+        if (pos > 1) { refuse("pos 0..1"); return *this; }
+        if (V < 0) { refuse("vocab"); return *this; }
+        if (V == 0 && pos == 0) { refuse("no table"); return *this; }
+        if (V >= 1 && layer.size() != 1) { refuse("not the first layer"); return *this; }
+        if (V >= 1 && C != 1) { refuse("ids have 1 channel"); return *this; }
+        if (V >= 1 && E < 1) { refuse("dim"); return *this; }
+        if (V == 0 && E != 0 && E != C) { refuse("dim is the channels"); return *this; }
+        const int E0 = V ? E : C;
+        if (!em_admits((long)in.N() * in.H() * in.W(), (int)(in.H() * in.W()), V, E0, pos)) { refuse("shape"); return *this; }
+        if (V) { in.grad[0] = &T4(1, V, E0, 1); in.grad[2] = &T4(1, V, E0, 1).zeros(); RAND(*in.grad[0], 1.0f); }
+        if (pos) { in.grad[1] = &T4(1, in.H(), in.W(), E0); in.grad[3] = &T4(1, in.H(), in.W(), E0).zeros(); RAND(*in.grad[1], 0.02f); }
+        in.iparm = V; in.stride[0] = (uint16_t)pos; in.stride[1] = in.stride[2] = in.stride[3] = 0; in.xparm = 0;
+        layer.push_back(&T4(in.N(), in.H(), in.W(), E0));
     } break;
     default: hprintf("Model#add layer %d not supported\n", fn); return *this;
     }
@@ -784,6 +838,7 @@ const float *Model::fstep(Tensor &in, Tensor &out, const float *x) {
         const int j = (int)(std::find(layer.begin(), layer.end(), &in) - layer.begin());
         an_fwd(in, out, x, in.iparm ? at(j - in.iparm).data : nullptr, s); break;
     }
+    case T4K_L_EMBED: em_fwd(in, out, x, s); break;
     default: hprintf("nn#fstep layer=%d not supported\n", fn);
     }
     return out.data;
@@ -946,9 +1001,10 @@ Model &Model::backprop(Tensor &tgt) {
 int  Model::dp_overlap = (int)env_long("T4_DP_OVERLAP", 0);       // 0 off, 1 on for world > 1, 2 also for a one-rank communicator (tests)
 long Model::dp_bucket  = env_long("T4_DP_BUCKET", 16384);          // floats per early all-reduce (64 KiB)
 void Model::grads_ready(int i, Tensor &in) {
-    if (!(train && gslab && in.grad[2] && in.grad[3] && !in.grad[2]->owns)) return;
-    const long off = (long)(in.grad[2]->data - gslab->data);
-    const long end = (long)(in.grad[3]->data - gslab->data) + (long)((in.grad[3]->numel + 63) & ~(uint64_t)63);
+    Tensor *lo = in.grad[2] ? in.grad[2] : in.grad[3], *hi = in.grad[3] ? in.grad[3] : in.grad[2];    // an embedding layer has one of the two, or both
+    if (!(train && gslab && lo && !lo->owns)) return;
+    const long off = (long)(lo->data - gslab->data);
+    const long end = (long)(hi->data - gslab->data) + (long)((hi->numel + 63) & ~(uint64_t)63);
     if (grad_hook) grad_hook(i, off, end - off, grad_hook_user);
     if (!dp_overlap || dp_mixed_ || dp_pend_lo_ < 0 || t4k_comm_world() < (dp_overlap >= 2 ? 1 : 2) || concurrent() || use_graphs || capturing_) return;
     if (end != dp_pend_lo_ || off < 0 || off >= end) { dp_mixed_ = true; return; }   // not the next range down: leave the rest to `gradient`
@@ -1161,6 +1217,7 @@ Model::Back Model::bstep(int i, Tensor &in, Tensor &out, const float *dy, bool l
         const int tap = an_tapper(in);
         an_bwd(in, dy, tap ? at(tap).data : nullptr, train, s); break;
     }
+    case T4K_L_EMBED: em_bwd(in, out, dy, train, s); break;      // position mode: dX = dY over x (the reference's `in = dx`); token mode writes nothing into the ids, so a second backprop sees them
     default: hprintf("nn#bstep layer=%d not supported\n", fn);
     }
     return { in.data };
@@ -1340,7 +1397,8 @@ Model &Model::adamw(DU lr, DU wd, DU b1, DU b2) { return gradient("adamw", OPTI_
 // fp32 values, and a closing `---`.  Loading into an already built model skips the layer section and reads the blobs in
 // layer order (the reference's own reload of the layer section is unfinished: `_parm` text is not Forth source).  An attention layer has
 // no blob: its `heads=<h>, causal=<c>attentn` line is read back into the model's attention layer at that place.  An add & norm layer saves
-// gamma and beta where it has them (mode != 0); its `back=<b>, mode=<m>addnorm` line must be the layer's own - a file with another is refused whole.
+// gamma and beta where it has them (mode != 0); its `back=<b>, mode=<m>addnorm` line must be the layer's own - a file with another is refused whole.  An
+// embedding layer saves TABLE ('w') and POS ('b'), whichever it has; its `vocab=<V>, pos=<p>embed  ` line is held to the same.
 int model_save(Model &m, const char *fname) {
     FILE *f = fopen(fname, "wb");
     if (!f) { hprintf("} => failed to open for output\n"); return 1; }
@@ -1357,6 +1415,7 @@ int model_save(Model &m, const char *fname) {
         if ((fn == T4K_L_CONV || fn == T4K_L_LINEAR || fn == T4K_L_DCONV) && in.grad[0] && in.grad[1]) { dump('w', LAYER_NAME[fn], *in.grad[0]); dump('b', LAYER_NAME[fn], *in.grad[1]); }   // (the reference skips dconv2d blobs, aio_model.cpp:170: a net it cannot run)
         else if (fn == T4K_L_BATCHNM && in.grad[0]) { dump('w', LAYER_NAME[fn], *in.grad[0]); if (norm_grp(in)) dump('b', LAYER_NAME[fn], *in.grad[1]); }   // batchnorm proper saves gamma alone, as the reference does
         else if (fn == T4K_L_ADDNORM && in.grad[0]) { dump('w', LAYER_NAME[fn], *in.grad[0]); dump('b', LAYER_NAME[fn], *in.grad[1]); }
+        else if (fn == T4K_L_EMBED) { if (in.grad[0]) dump('w', LAYER_NAME[fn], *in.grad[0]); if (in.grad[1]) dump('b', LAYER_NAME[fn], *in.grad[1]); }   // TABLE | POS, whichever the mode has
     }
     fprintf(f, "\n---\n");
     fclose(f);
@@ -1379,6 +1438,8 @@ int model_load(Model &m, const char *fname) {
     auto line_of = [&](int i) -> const std::string & { static const std::string none; return i + 1 < (int)lines.size() ? lines[i + 1] : none; };   // (lines[0] is the header)
     for (int i = 0; i + 1 < (int)m.layer.size(); i++)
         if (m.at(i).grad_fn == T4K_L_ADDNORM && !an_line_ok(m.at(i), line_of(i))) { hprintf(" model format error (addnorm layer %d: %s)\n", i, line_of(i).c_str()); err = 1; }
+    for (int i = 0; i + 1 < (int)m.layer.size() && !err; i++)                                  // ... and an embedding layer's; one error line a file
+        if (m.at(i).grad_fn == T4K_L_EMBED && !em_line_ok(m.at(i), line_of(i))) { hprintf(" model format error (embed layer %d: %s)\n", i, line_of(i).c_str()); err = 1; }
     if (err) { fclose(f); return err; }
     for (int i = 0; i + 1 < (int)m.layer.size() && i + 1 < (int)lines.size(); i++) {
         if (m.at(i).grad_fn != T4K_L_ATTN) continue;
@@ -1398,6 +1459,7 @@ int model_load(Model &m, const char *fname) {
         if ((fn == T4K_L_CONV || fn == T4K_L_LINEAR || fn == T4K_L_DCONV) && in.grad[0] && in.grad[1]) { rd(*in.grad[0]); if (!err) rd(*in.grad[1]); }
         else if (fn == T4K_L_BATCHNM && in.grad[0]) { rd(*in.grad[0]); if (!err && norm_grp(in)) rd(*in.grad[1]); }
         else if (fn == T4K_L_ADDNORM && in.grad[0]) { rd(*in.grad[0]); if (!err) rd(*in.grad[1]); }
+        else if (fn == T4K_L_EMBED) { if (in.grad[0]) rd(*in.grad[0]); if (!err && in.grad[1]) rd(*in.grad[1]); }
     }
     if (!err) {                                          // the blob list must end here: a closing `---` line and nothing else
         while (getline_(line) && !line.length()) {}

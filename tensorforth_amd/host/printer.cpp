@@ -114,6 +114,7 @@ static std::string parm_s(Tensor &in, Tensor &out) {     // aio_model.cpp:103-14
     case T4K_L_USAMPLE: { const char *nm[] = {"nearest", "linear", "bilinear", "cubic"}; o << S << "x" << S << " " << nm[in.iparm & 3]; } break;
     case T4K_L_ATTN: o << "heads=" << in.iparm << ", causal=" << S; break;     // `vector{ heads causal } linear`
     case T4K_L_ADDNORM: o << "back=" << in.iparm << ", mode=" << S; break;     // `vector{ back mode } selu`
+    case T4K_L_EMBED: o << "vocab=" << in.iparm << ", pos=" << S; break;       // `vector{ V E pos } upsample`
     default: break;
     }
     return o.str();
@@ -130,8 +131,9 @@ std::string fmt_model(Model &m) {                        // aio_model.cpp:65-99
         for (int k = 0; k < 5; k++) sz += in.grad[k] ? (int)in.grad[k]->numel : 0;
         if (in.grad_fn == T4K_L_ATTN) sz = 0;            // no parameters: grad[4] is the saved copy of the output
         if (in.grad_fn == T4K_L_ADDNORM) sz = in.grad[0] ? (int)(in.grad[0]->numel + in.grad[1]->numel) : 0;   // gamma and beta of a norm (2 C); a plain add or mark has none
+        if (in.grad_fn == T4K_L_EMBED) sz = (in.grad[0] ? (int)in.grad[0]->numel : 0) + (in.grad[1] ? (int)in.grad[1]->numel : 0);   // the token table (V E) and the position table (L E), whichever the mode has
         o << " #p=" << sz << ' ';
-        for (int k = 0; k < 2 && in.grad[k]; k++) o << fmt_objname(*in.grad[k], false) << ' ';
+        for (int k = 0; k < 2 && (in.grad[k] || in.grad_fn == T4K_L_EMBED); k++) if (in.grad[k]) o << fmt_objname(*in.grad[k], false) << ' ';   // (an embedding in position mode has grad[1] alone)
         if (in.grad[4]) o << fmt_objname(*in.grad[4], false) << ' ';
         o << parm_s(in, out) << '\n';
     }

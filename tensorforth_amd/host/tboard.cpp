@@ -213,7 +213,7 @@ void tb_image(const char *tag, Tensor &t) {              // Summary::image summa
 void tb_graph(Model &m) {
     if (!tb_active()) return;
     static const char *op[] = { "Output", "Conv2D", "MatMul", "Reshape", "Relu", "Tanh", "Sigmoid", "Selu", "LeakyRelu", "Elu", "Dropout", "Softmax", "LogSoftmax",
-                                "AvgPool", "MaxPool", "MinPool", "BatchNorm", "UpSample", "UpSample", "Attention", "AddNorm" };     // summary.cpp:120-125 (+ dconv2d, which the reference's table lacks)
+                                "AvgPool", "MaxPool", "MinPool", "BatchNorm", "UpSample", "UpSample", "Attention", "AddNorm", "Embedding" };     // summary.cpp:120-125 (+ dconv2d, which the reference's table lacks)
     auto attrs = [](PB &node, Tensor &t) {
         PB dt; dt.i64(6, 1);                                                       // AttrValue.type = DT_FLOAT
         PB a1; a1.str(1, "dtype"); a1.msg(2, dt); node.msg(5, a1);

@@ -12,7 +12,7 @@ namespace t4 {
 
 const char *LAYER_NAME[] = { "output ", "conv2d ", "linear ", "flatten", "relu   ", "tanh   ", "sigmoid", "selu   ",
                              "leakyrl", "elu    ", "dropout", "softmax", "logsmax", "avgpool", "maxpool", "minpool",
-                             "batchnm", "upsampl", "dconv2d", "attentn", "addnorm" };        // (attentn, addnorm: beyond the reference's list)
+                             "batchnm", "upsampl", "dconv2d", "attentn", "addnorm", "embed  " };        // (attentn, addnorm, embed: beyond the reference's list)
 
 static bool g_ready = false;
 static float *g_scalar = nullptr;       // device scratch for reductions (replaces Tensor::_tmp)

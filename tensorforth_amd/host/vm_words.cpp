@@ -478,6 +478,19 @@ void VM::nnop(int op) {
         MTOS().add(T4K_L_ADDNORM, 0, 0, opt);
         return;
     }
+    // beyond the reference ( N V -- N ): a vector{ V E pos } on top of a model makes `upsample` an embedding layer: V >= 1 a token table of
+    // V rows of E floats over the ids in the model's input, pos = 1 a learned position table added to the H W tokens of a sample; V = 0, pos = 1 the position
+    // table alone, anywhere in the net.  Missing cells mean 0, further cells are ignored.  V goes through `n` (32 bits; opt cells hold 16).  The reference
+    // prints "( N [mtum] n -- ) for upsample required?" here
+    if (op == T4K_L_USAMPLE && TOS1T() && TTOS().rank == 1 && SP() > 0 && is_m(SS(-1))) {
+        Tensor &t = TTOS();
+        std::vector<float> vo; t.to_host(vo, std::min<uint64_t>(t.numel, 3));
+        DU x = POP(); DROP(x);                           // the vector is dropped and freed, as the pool, batchnorm, attention and addnorm branches do
+        vo.resize(3, 0.0f);
+        uint16_t opt[4] = { (uint16_t)(int)vo[1], (uint16_t)(int)vo[2], 0, 0 };
+        MTOS().add(T4K_L_EMBED, (uint32_t)(int)vo[0], 0, opt);
+        return;
+    }
     if (TOS1T()) {                                       // tensor ops (destructive)
         Tensor &t = TTOS();
         switch (op) {
