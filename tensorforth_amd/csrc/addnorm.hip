@@ -4,7 +4,7 @@
 // A TEAM owns a token at a time: T = 8 .. 64 lanes of a wave on rung 1 (a 256-thread workgroup holds 256 / T tokens), the whole workgroup on rung 2.  Lane l
 // of the team owns the column items l, l + T, l + 2T .. (at most 8 of them, each VW floats), so neighbouring lanes load neighbouring addresses, z = x + s lives
 // in registers between the sums, and a thread's gamma, beta and its dW | dB partial sums never change column.  A workgroup walks a contiguous slab of
-// tokens and leaves ONE row of 2 C partial sums; colsum.h's launchers fold the rows.  The variance is the sum of squared deviations from the token's own
+// tokens and leaves ONE row of 2 C partial sums; colsum.h's fold_dw_db folds the rows.  The variance is the sum of squared deviations from the token's own
 // computed mean, a second pass over the registers.  No atomics anywhere: every sum is a fixed tree.
 #include "t4k_common.h"
 #include "launch.h"
@@ -25,14 +25,6 @@ struct AnP {
     float eps, fC;                     // fC = (float)C
 };
 
-template <int VW> __device__ __forceinline__ void an_ld(const float *q, float (&v)[VW]) {
-    if constexpr (VW == 4) { const float4 t = *reinterpret_cast<const float4 *>(q); v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; }
-    else v[0] = *q;
-}
-template <int VW> __device__ __forceinline__ void an_st(float *q, const float (&v)[VW]) {
-    if constexpr (VW == 4) *reinterpret_cast<float4 *>(q) = make_float4(v[0], v[1], v[2], v[3]);
-    else *q = v[0];
-}
 // the sums of NV values over the team, in every lane of it.  Rung 1: xor butterflies over the team's T lanes of the wave (the partner of a lane is in its
 // own team: off < T), every lane of the wave arriving.  Rung 2: wave butterflies, then the four wave sums through LDS, added in one order
 template <int RUNG, int NV> __device__ __forceinline__ void an_sum(float (&a)[NV], int T, float *sm) {
@@ -57,24 +49,19 @@ template <int RUNG, int NV> __device__ __forceinline__ void an_sum(float (&a)[NV
 // a walking pointer stays a per-lane value: without this the compiler splits every item's address into a uniform base (a scalar pair per item and tensor,
 // hoisted out of the token loop - they spilled scalar registers on the dword path) and one lane offset
 template <typename P> __device__ __forceinline__ void an_keep(P *&q) { asm volatile("" : "+v"(q)); }
-// t = dy + dy2 and g = W t, each rounded wherever it is used: contracted into g - m1 they would be other numbers than the ones that were summed
-__device__ __forceinline__ float an_mul(float a, float b) {
-#pragma clang fp contract(off)
-    return a * b;
-}
 
 // ------------------------------------------------------------------ rung 0: mode 0, flat.  O = X + S (S NULL: O = X); the backward is the same kernel on DY, DY2
 template <int VW>
 __global__ void __launch_bounds__(AN_BLK) k_an_flat(const float *X, const float *S, float *O, long nitems) {
     for (long i = (long)blockIdx.x * AN_BLK + threadIdx.x; i < nitems; i += (long)gridDim.x * AN_BLK) {
         float x[VW], s[VW];
-        an_ld<VW>(X + i * VW, x);
+        ldv<VW>(X + i * VW, x);
         if (S) {
-            an_ld<VW>(S + i * VW, s);
+            ldv<VW>(S + i * VW, s);
 #pragma unroll
             for (int v = 0; v < VW; v++) x[v] += s[v];
         }
-        an_st<VW>(O + i * VW, x);
+        stv<VW>(O + i * VW, x);
     }
 }
 
@@ -102,9 +89,9 @@ __global__ void __launch_bounds__(AN_BLK) k_an_fwd(const float *X, const float *
 #pragma unroll
             for (int v = 0; v < VW; v++) z[k][v] = 0.f;
             if (k < n) {
-                an_ld<VW>(px, z[k]);
+                ldv<VW>(px, z[k]);
                 if (S) {
-                    float s[VW]; an_ld<VW>(ps, s);
+                    float s[VW]; ldv<VW>(ps, s);
 #pragma unroll
                     for (int v = 0; v < VW; v++) z[k][v] += s[v];
                 }
@@ -135,10 +122,10 @@ __global__ void __launch_bounds__(AN_BLK) k_an_fwd(const float *X, const float *
             an_keep(po); an_keep(ph); an_keep(pw); an_keep(pb);
             if (k < n) {
                 float gw[VW], gb[VW], xh[VW], y[VW];
-                an_ld<VW>(pw, gw); an_ld<VW>(pb, gb);
+                ldv<VW>(pw, gw); ldv<VW>(pb, gb);
 #pragma unroll
                 for (int v = 0; v < VW; v++) { xh[v] = (z[k][v] - mean) * rstd; y[v] = xh[v] * gw[v] + gb[v]; }
-                an_st<VW>(ph, xh); an_st<VW>(po, y);
+                stv<VW>(ph, xh); stv<VW>(po, y);
             }
         }
     }
@@ -173,15 +160,15 @@ __global__ void __launch_bounds__(AN_BLK) k_an_bwd(const float *__restrict__ W, 
             for (int v = 0; v < VW; v++) { g[k][v] = 0.f; xh[k][v] = 0.f; }
             if (k < n) {
                 float t[VW], gw[VW];
-                an_ld<VW>(pd, t); an_ld<VW>(ph, xh[k]); an_ld<VW>(pw, gw);
+                ldv<VW>(pd, t); ldv<VW>(ph, xh[k]); ldv<VW>(pw, gw);
                 if (DY2) {
-                    float d2[VW]; an_ld<VW>(p2, d2);
+                    float d2[VW]; ldv<VW>(p2, d2);
 #pragma unroll
                     for (int v = 0; v < VW; v++) t[v] += d2[v];
                 }
 #pragma unroll
                 for (int v = 0; v < VW; v++) {
-                    g[k][v] = an_mul(gw[v], t[v]);
+                    g[k][v] = mul_rn(gw[v], t[v]);
                     aw[k][v] += t[v] * xh[k][v]; ab[k][v] += t[v];
                 }
             }
@@ -201,7 +188,7 @@ __global__ void __launch_bounds__(AN_BLK) k_an_bwd(const float *__restrict__ W, 
                 float dx[VW];
 #pragma unroll
                 for (int v = 0; v < VW; v++) dx[v] = rstd * (g[k][v] - m1 - xh[k][v] * m2);
-                an_st<VW>(po, dx);
+                stv<VW>(po, dx);
             }
         }
     }
@@ -253,7 +240,6 @@ __global__ void __launch_bounds__(AN_BLK) k_an_bwd(const float *__restrict__ W, 
 
 // ------------------------------------------------------------------ the plan: what the launch code uses, and what t4k_addnorm_plan reports
 struct AnPlan { int rung, vw, tpw, T, tsh, nslice, fold; long fper, bper; int fgrid; };
-long an_cdiv(long a, long b) { return (a + b - 1) / b; }
 // admission (who: the entry's name for the message) in 64 bits: the extents may be anything their types hold
 int an_plan(AnPlan &g, const char *who, long rows, int C, int mode, bool aligned, long ws_bytes) {
     if (rows < 1 || C < 1) return fail(T4K_ERR_ARG, "%s: an extent below 1 (rows=%ld C=%d)", who, rows, C);
@@ -267,20 +253,20 @@ int an_plan(AnPlan &g, const char *who, long rows, int C, int mode, bool aligned
     if (mode == 0) { g.rung = 0; return T4K_OK; }
     g.rung = 0;
     for (int T = 8, sh = 3; T <= WAVE; T <<= 1, sh++)
-        if (an_cdiv(items, T) <= AN_ITEMS) { g.rung = 1; g.T = T; g.tsh = sh; g.tpw = AN_BLK / T; break; }
+        if (ceil_div(items, T) <= AN_ITEMS) { g.rung = 1; g.T = T; g.tsh = sh; g.tpw = AN_BLK / T; break; }
     if (!g.rung) {
-        if (an_cdiv(items, AN_BLK) > AN_ITEMS)
+        if (ceil_div(items, AN_BLK) > AN_ITEMS)
             return fail(T4K_ERR_UNSUPPORTED, "%s: channels=%d not supported (at most %d with every pointer on 16 bytes and C %% 4 == 0, else %d)", who, C,
                         AN_BLK * AN_ITEMS * 4, AN_BLK * AN_ITEMS);
         g.rung = 2; g.T = AN_BLK; g.tsh = 8; g.tpw = 1;
     }
-    const long groups = an_cdiv(rows, g.tpw);                              // workgroup visits the tokens need
-    g.fper = an_cdiv(groups, std::min(groups, (long)AN_WG)) * g.tpw; g.fgrid = (int)an_cdiv(rows, g.fper);
+    const long groups = ceil_div(rows, g.tpw);                             // workgroup visits the tokens need
+    g.fper = ceil_div(groups, std::min(groups, (long)AN_WG)) * g.tpw; g.fgrid = (int)ceil_div(rows, g.fper);
     // the dW | dB slab: one row of 2 C floats per workgroup of the backward, as many as the device is wide and the workspace holds - never as many as rows
     const long fit = ws_bytes / (long)sizeof(float) / (2L * C);
     if (fit < 1) return fail(T4K_ERR_UNSUPPORTED, "%s: a dW | dB slab row (%ld floats) does not fit the workspace", who, 2L * C);
-    g.bper = an_cdiv(groups, std::min(groups, std::min((long)AN_SLICES, fit))) * g.tpw; g.nslice = (int)an_cdiv(rows, g.bper);
-    g.fold = g.nslice <= 32 ? 1 : 2;                                       // as groupnorm.hip: few slices walk whole slabs, else a wave per output
+    g.bper = ceil_div(groups, std::min(groups, std::min((long)AN_SLICES, fit))) * g.tpw; g.nslice = (int)ceil_div(rows, g.bper);
+    g.fold = fold_kind(g.nslice);
     return T4K_OK;
 }
 AnP an_parms(const AnPlan &g, long rows, int C, long per, float eps) {
@@ -288,20 +274,10 @@ AnP an_parms(const AnPlan &g, long rows, int C, long per, float eps) {
     p.rows = rows; p.per = per; p.C = C; p.items = C / g.vw; p.T = g.T; p.tsh = g.tsh; p.tpw = g.tpw; p.eps = eps; p.fC = (float)C;
     return p;
 }
-bool an16(const void *a, const void *b, const void *c, const void *d, const void *e = nullptr, const void *f = nullptr, const void *h = nullptr) {
-    return aligned16(a) && aligned16(b) && aligned16(c) && aligned16(d) && aligned16(e) && aligned16(f) && aligned16(h);
-}
-// do [a, a + na) and [b, b + nb) floats share a byte?  (NULL: no.)  same_ok: the two being ONE tensor is no overlap
-bool an_clash(const float *a, long na, const float *b, long nb, bool same_ok = false) {
-    if (!a || !b) return false;
-    if (same_ok && a == b) return false;
-    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + (uintptr_t)na * sizeof(float), b0 = (uintptr_t)b, b1 = b0 + (uintptr_t)nb * sizeof(float);
-    return a0 < b1 && b0 < a1;
-}
 int an_flat(const float *X, const float *S, float *O, long n, bool aligned, hipStream_t hs) {
     const int vw = (aligned && n % 4 == 0) ? 4 : 1;
     const long nitems = n / vw;
-    const unsigned grid = (unsigned)std::min(an_cdiv(nitems, AN_BLK), (long)AN_WG);
+    const unsigned grid = (unsigned)std::min(ceil_div(nitems, AN_BLK), (long)AN_WG);
     if (vw == 4) T4K_LAUNCH((k_an_flat<4>), dim3(grid), dim3(AN_BLK), 0, hs, X, S, O, nitems);
     else         T4K_LAUNCH((k_an_flat<1>), dim3(grid), dim3(AN_BLK), 0, hs, X, S, O, nitems);
     return T4K_OK;
@@ -327,12 +303,12 @@ int t4k_addnorm_fwd(const float *X, const float *S, float *O, float *XH, float *
     if (!(eps > 0.0f)) return fail(T4K_ERR_ARG, "t4k_addnorm_fwd: eps must be above 0");
     if (mode == 0) XH = nullptr, RSTD = nullptr, W = nullptr, B = nullptr;
     AnPlan g;
-    const int rc = an_plan(g, "t4k_addnorm_fwd", rows, C, mode, an16(X, S, O, XH, W, B), (long)(st().ws_bytes / 2)); if (rc != T4K_OK) return rc;
+    const int rc = an_plan(g, "t4k_addnorm_fwd", rows, C, mode, all16(X, S, O, XH, W, B), (long)(st().ws_bytes / 2)); if (rc != T4K_OK) return rc;
     const long n = rows * C;
     // O may be X or S, the tensor itself; nothing else that is written may share a byte with another operand
-    if (an_clash(O, n, X, n, true) || an_clash(O, n, S, n, true) || an_clash(O, n, XH, n) || an_clash(O, n, RSTD, rows) || an_clash(O, n, W, C) || an_clash(O, n, B, C) ||
-        an_clash(XH, n, X, n) || an_clash(XH, n, S, n) || an_clash(XH, n, RSTD, rows) || an_clash(XH, n, W, C) || an_clash(XH, n, B, C) ||
-        an_clash(RSTD, rows, X, n) || an_clash(RSTD, rows, S, n) || an_clash(RSTD, rows, W, C) || an_clash(RSTD, rows, B, C))
+    if (clash(O, n, X, n, true) || clash(O, n, S, n, true) || clash(O, n, XH, n) || clash(O, n, RSTD, rows) || clash(O, n, W, C) || clash(O, n, B, C) ||
+        clash(XH, n, X, n) || clash(XH, n, S, n) || clash(XH, n, RSTD, rows) || clash(XH, n, W, C) || clash(XH, n, B, C) ||
+        clash(RSTD, rows, X, n) || clash(RSTD, rows, S, n) || clash(RSTD, rows, W, C) || clash(RSTD, rows, B, C))
         return fail(T4K_ERR_ARG, "t4k_addnorm_fwd: an output overlaps another operand (O may be X or S, nothing else)");
     hipStream_t hs = t4k::S(s);
     if (g.rung == 0) { an_flat(X, S, O, n, g.vw == 4, hs); T4K_LAUNCH_CHECK(); return T4K_OK; }
@@ -357,13 +333,13 @@ int t4k_addnorm_bwd(const float *W, const float *DY, const float *DY2, const flo
     if (train && (!DW || !DB)) return fail(T4K_ERR_ARG, "t4k_addnorm_bwd: DW and DB are required when train != 0");
     if (!train) DW = nullptr, DB = nullptr;
     AnPlan g;
-    const int rc = an_plan(g, "t4k_addnorm_bwd", rows, C, mode, an16(W, DY, DY2, XH, DX), (long)(st().ws_bytes / 2)); if (rc != T4K_OK) return rc;
+    const int rc = an_plan(g, "t4k_addnorm_bwd", rows, C, mode, all16(W, DY, DY2, XH, DX), (long)(st().ws_bytes / 2)); if (rc != T4K_OK) return rc;
     const long n = rows * C;
-    if (an_clash(DX, n, DY, n, true) || an_clash(DX, n, DY2, n, true) || an_clash(DX, n, XH, n) || an_clash(DX, n, RSTD, rows) || an_clash(DX, n, W, C) ||
-        an_clash(DX, n, DW, C) || an_clash(DX, n, DB, C) || an_clash(DW, C, DB, C))
+    if (clash(DX, n, DY, n, true) || clash(DX, n, DY2, n, true) || clash(DX, n, XH, n) || clash(DX, n, RSTD, rows) || clash(DX, n, W, C) ||
+        clash(DX, n, DW, C) || clash(DX, n, DB, C) || clash(DW, C, DB, C))
         return fail(T4K_ERR_ARG, "t4k_addnorm_bwd: an output overlaps another operand (DX may be DY or DY2, nothing else)");
     for (const float *g2 : { DW, DB })
-        if (an_clash(g2, C, DY, n) || an_clash(g2, C, DY2, n) || an_clash(g2, C, XH, n) || an_clash(g2, C, RSTD, rows) || an_clash(g2, C, W, C))
+        if (clash(g2, C, DY, n) || clash(g2, C, DY2, n) || clash(g2, C, XH, n) || clash(g2, C, RSTD, rows) || clash(g2, C, W, C))
             return fail(T4K_ERR_ARG, "t4k_addnorm_bwd: DW or DB overlaps another operand");
     hipStream_t hs = t4k::S(s);
     if (g.rung == 0) { an_flat(DY, DY2, DX, n, g.vw == 4, hs); T4K_LAUNCH_CHECK(); return T4K_OK; }
@@ -376,10 +352,7 @@ int t4k_addnorm_bwd(const float *W, const float *DY, const float *DY2, const flo
             });
         });
     });
-    if (train) {
-        if (g.fold == 1 && DB == DW + C) launch_fold_add(slab, DW, 2 * C, g.nslice, hs);
-        else launch_df_fold(slab, DW, DB, g.nslice, C, 2 * C, hs);
-    }
+    if (train) fold_dw_db(slab, DW, DB, C, g.nslice, g.fold, hs);
     T4K_LAUNCH_CHECK();
     return T4K_OK;
 }

@@ -333,13 +333,6 @@ AtP attn_parms(const AtPlan &a, int N, int L, int heads, int d, int causal) {
     p.scale = (float)(1.0 / std::sqrt((double)d));                         // in double, rounded once
     return p;
 }
-bool at16(const void *a, const void *b, const void *c, const void *d, const void *e = nullptr) {
-    return aligned16(a) && aligned16(b) && aligned16(c) && aligned16(d) && aligned16(e);
-}
-bool overlap(const float *a, long na, const float *b, long nb) {
-    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + (uintptr_t)na * sizeof(float), b0 = (uintptr_t)b, b1 = b0 + (uintptr_t)nb * sizeof(float);
-    return a0 < b1 && b0 < a1;
-}
 
 } // namespace
 
@@ -358,7 +351,7 @@ int t4k_attention_fwd(const float *QKV, float *O, float *OK, float *LSE, int N, 
     T4K_REQUIRE_INIT();
     if (!QKV || !O || !LSE) return fail(T4K_ERR_ARG, "t4k_attention_fwd: null tensor");
     AtPlan a;
-    const int rc = attn_plan(a, "t4k_attention_fwd", N, L, heads, d, at16(QKV, O, OK, LSE), (long)(st().ws_bytes / 2)); if (rc != T4K_OK) return rc;
+    const int rc = attn_plan(a, "t4k_attention_fwd", N, L, heads, d, all16(QKV, O, OK, LSE), (long)(st().ws_bytes / 2)); if (rc != T4K_OK) return rc;
     const AtP p = attn_parms(a, N, L, heads, d, causal);
     hipStream_t hs = t4k::S(s);
     pick<16, 32, 64, 128>(a.dp, [&](auto dp) {
@@ -375,9 +368,9 @@ int t4k_attention_bwd(const float *QKV, const float *OK, const float *DY, const 
     T4K_REQUIRE_INIT();
     if (!QKV || !OK || !DY || !LSE || !DQKV) return fail(T4K_ERR_ARG, "t4k_attention_bwd: null tensor");
     AtPlan a;
-    const int rc = attn_plan(a, "t4k_attention_bwd", N, L, heads, d, at16(QKV, OK, DY, LSE, DQKV), (long)(st().ws_bytes / 2)); if (rc != T4K_OK) return rc;
+    const int rc = attn_plan(a, "t4k_attention_bwd", N, L, heads, d, all16(QKV, OK, DY, LSE, DQKV), (long)(st().ws_bytes / 2)); if (rc != T4K_OK) return rc;
     const long ne = (long)N * L * heads * d;
-    if (overlap(DQKV, 3 * ne, QKV, 3 * ne) || overlap(DQKV, 3 * ne, OK, ne) || overlap(DQKV, 3 * ne, DY, ne))
+    if (clash(DQKV, 3 * ne, QKV, 3 * ne) || clash(DQKV, 3 * ne, OK, ne) || clash(DQKV, 3 * ne, DY, ne))
         return fail(T4K_ERR_ARG, "t4k_attention_bwd: DQKV overlaps QKV, OK or DY");
     const AtP p = attn_parms(a, N, L, heads, d, causal);
     hipStream_t hs = t4k::S(s);

@@ -15,7 +15,6 @@ constexpr long SPLIT_UNITS  = 8;                   // loads a lane keeps at leas
 constexpr long MAX_SPLIT    = 4096;
 
 inline unsigned log2_ceil(long x, unsigned cap) { unsigned k = 0; while (k < cap && (1L << k) < x) k++; return k; }
-inline long ceil_div(long a, long b) { return (a + b - 1) / b; }
 
 // ---- row family: the innermost merged group is reduced.  Group o (one output of a reduction) is r1 runs (sr1 apart) of r0 contiguous
 // floats starting at base(o) = o * sk0, or (o / k0) * sk1 + (o % k0) * sk0 when a second kept group lies outside the runs.  1 << shift lanes

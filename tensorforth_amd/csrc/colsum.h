@@ -1,5 +1,5 @@
 // colsum.h - deterministic column sums and slab folds, shared by the convolution units (dF | dB partial slabs, the bias gradient of the
-// many-channel path and of the transposed convolution) and the linear layers (their bias gradient).  The kernels live in colsum.hip; the fold
+// many-channel path and of the transposed convolution), the linear layers (their bias gradient) and the norm layers (dW | dB).  The kernels live in colsum.hip; the fold
 // BODY lives here because the dX kernels of conv.hip and conv_few.hip run it in their first workgroups (the fold rides the dX launch).
 #pragma once
 #include "t4k_common.h"
@@ -11,6 +11,12 @@ int colsum_add(const float *X, float *OUT, long rows, int E, hipStream_t hs);
 void launch_fold_add(const float *part, float *OUT, int n, int nslice, hipStream_t hs);
 // the wave-per-output fold as a launch of its own (k_conv_df_fold): outputs [0, ndf) go to DF, [ndf, ntot) to DB
 void launch_df_fold(const float *part, float *DF, float *DB, int nslice, int ndf, int ntot, hipStream_t hs);
+// which of the two folds nslice slabs: k_fold_add walks whole slabs, a thread per output, and serves up to FOLD_ADD_MAX slices (few slices x many outputs,
+// coalesced); above that the wave-per-output fold (hundreds of slices: it would run 8 of 64 lanes on few).  1 fold_add, 2 df_fold: what the plans report
+constexpr int FOLD_ADD_MAX = 32;
+inline int fold_kind(int nslice) { return nslice <= FOLD_ADD_MAX ? 1 : 2; }
+// the fold of a norm layer's dW | dB slab (nslice rows of 2 C floats) by the plan's kind: fold_add needs ONE destination, DB right behind DW
+void fold_dw_db(const float *slab, float *DW, float *DB, int C, int nslice, int kind, hipStream_t hs);
 }
 
 namespace {

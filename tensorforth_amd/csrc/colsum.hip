@@ -70,4 +70,8 @@ void launch_fold_add(const float *part, float *OUT, int n, int nslice, hipStream
 void launch_df_fold(const float *part, float *DF, float *DB, int nslice, int ndf, int ntot, hipStream_t hs) {
     T4K_LAUNCH(k_conv_df_fold, dim3((ntot + 3) / 4), dim3(256), 0, hs, part, DF, DB, nslice, ndf, ntot);
 }
+void fold_dw_db(const float *slab, float *DW, float *DB, int C, int nslice, int kind, hipStream_t hs) {
+    if (kind == 1 && DB == DW + C) launch_fold_add(slab, DW, 2 * C, nslice, hs);
+    else launch_df_fold(slab, DW, DB, nslice, C, 2 * C, hs);
+}
 }

@@ -423,9 +423,7 @@ int conv_df_stage(const float *I, const float *DO, float *DF, float *DB, int N, 
         const int nbig = launch_conv_big_df(K, S, P, hs, I, DO, part, st().ws_bytes / 8, N, H1, W1, C1, H0, W0, C0);
         if (nbig > 0) {
             const int ntot = ntaps * C0;                     // no bias row in these slabs: dB is a plain column sum of dO
-            // few slices x many outputs: one thread per output walks the slices (coalesced); the wave-per-output fold is
-            // for the opposite shape (hundreds of slices, few outputs) and would run 8 of 64 lanes here
-            if (nbig <= 32) { conv_plan_note("fold_add"); launch_fold_add(part, DF, ntot, nbig, hs); }
+            if (fold_kind(nbig) == 1) { conv_plan_note("fold_add"); launch_fold_add(part, DF, ntot, nbig, hs); }
             else            { conv_plan_note("df_fold");  launch_df_fold(part, DF, DB, nbig, ntot, ntot, hs); }
             return colsum_add(DO, DB, (long)N * H0 * W0, C0, hs);
         }

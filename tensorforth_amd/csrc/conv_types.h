@@ -97,9 +97,6 @@ struct ConvLab {
 inline const ConvLab &conv_lab() { static const ConvLab v; return v; }
 
 // ---- host-side planning shared by the units that cut dF into pixel slices
-inline bool all16(const void *a, const void *b, const void *c = nullptr, const void *d = nullptr, const void *e = nullptr) {
-    return aligned16(a) && aligned16(b) && aligned16(c) && aligned16(d) && aligned16(e);
-}
 // `want_slices` (at least one) over npix pixels: pixels per slice in whole stages, at least min_pixels, and the slices that then cover npix
 struct DfSlices { long pps, n; };
 inline DfSlices df_slices(long npix, long want_slices, int stage_pixels, int min_pixels) {
@@ -115,15 +112,15 @@ inline DfSlices df_slices(long npix, long want_slices, int stage_pixels, int min
 constexpr size_t CONV_WS_BYTES = (size_t)32 << 20, CONV_SLAB_AIM = (size_t)8 << 20;
 constexpr int CONV_DF_WG = 1024;                        // workgroups their dF launch aims at
 // slices: enough that ~CONV_DF_WG workgroups run (`tiles` per slice), whole 32-pixel stages each, no more than CONV_SLAB_AIM holds slabs of ntot floats;
-// pps_cap: what the kernel's pixels-per-slice argument holds.  k_fold_add walks whole slabs into ONE destination: it serves up to 32 slices when DB lies
-// right behind DF (a layer's gradient block); otherwise the wave-per-output fold splits the slab between the two (fold: 1 fold_add, 2 df_fold)
+// pps_cap: what the kernel's pixels-per-slice argument holds.  The fold is colsum.h's fold_kind, and k_fold_add only when DB lies right behind DF (a layer's
+// gradient block): it walks whole slabs into ONE destination
 struct SlabPlan { long pps; int nslice, fold; };
 inline SlabPlan slab_plan(long np0, long tiles, long ntot, bool db_adjacent, long pps_cap) {
     const long want = std::min((CONV_DF_WG + tiles - 1) / tiles, (long)(CONV_SLAB_AIM / sizeof(float)) / ntot);
     SlabPlan s;
     s.pps = std::min(df_slices(np0, want, 32, 0).pps, pps_cap);
     s.nslice = (int)((np0 + s.pps - 1) / s.pps);
-    s.fold = (s.nslice <= 32 && db_adjacent) ? 1 : 2;
+    s.fold = (fold_kind(s.nslice) == 1 && db_adjacent) ? 1 : 2;
     return s;
 }
 // what both admit alike (who: the entry's name for the message; groups: the group count, null for the layer without groups).  T4K_ERR_ARG: an extent below 1;

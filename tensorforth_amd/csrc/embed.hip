@@ -28,14 +28,6 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 struct EmF { long T; int L, V, E, items, tl, tsh, wb; float fV; };
 struct EmB { long T, per, units, pitems; int L, V, E, N, slabs, chunks, swg; float fV; };
 
-template <int VW> __device__ __forceinline__ void em_ld(const float *q, float (&v)[VW]) {
-    if constexpr (VW == 4) { const float4 t = *reinterpret_cast<const float4 *>(q); v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; }
-    else v[0] = *q;
-}
-template <int VW> __device__ __forceinline__ void em_st(float *q, const float (&v)[VW]) {
-    if constexpr (VW == 4) *reinterpret_cast<float4 *>(q) = make_float4(v[0], v[1], v[2], v[3]);
-    else *q = v[0];
-}
 template <int VW> __device__ __forceinline__ void em_st_nt(float *q, const float (&v)[VW]) {     // streaming store
     if constexpr (VW == 4) __builtin_nontemporal_store(v4f{v[0], v[1], v[2], v[3]}, reinterpret_cast<v4f *>(q));
     else __builtin_nontemporal_store(v[0], q);
@@ -71,9 +63,9 @@ __global__ void __launch_bounds__(EM_BLK) k_em_fwd(const float *__restrict__ SRC
                 float v[VW], q[VW];
 #pragma unroll
                 for (int e = 0; e < VW; e++) v[e] = 0.0f;
-                if (!TOK || idj >= 0) em_ld<VW>(row + it * VW, v);
+                if (!TOK || idj >= 0) ldv<VW>(row + it * VW, v);
                 if (POS) {
-                    em_ld<VW>(pr + it * VW, q);
+                    ldv<VW>(pr + it * VW, q);
 #pragma unroll
                     for (int e = 0; e < VW; e++) v[e] += q[e];
                 }
@@ -135,7 +127,7 @@ __global__ void __launch_bounds__(EM_BLK) k_em_bwd(const float *__restrict__ IDS
                     for (int q = 0; q < EM_MB; q++) {
 #pragma unroll
                         for (int e = 0; e < VW; e++) v[q][e] = 0.0f;
-                        if (j[q] >= 0 && active) em_ld<VW>(dyc + (base + j[q]) * p.E, v[q]);
+                        if (j[q] >= 0 && active) ldv<VW>(dyc + (base + j[q]) * p.E, v[q]);
                     }
 #pragma unroll
                     for (int q = 0; q < EM_MB; q++) {
@@ -156,7 +148,7 @@ __global__ void __launch_bounds__(EM_BLK) k_em_bwd(const float *__restrict__ IDS
                 float a[VW];
 #pragma unroll
                 for (int e = 0; e < VW; e++) a[e] = acc[r * CH + e];
-                em_st<VW>(PART + ((long)part * p.V + v0 + r) * p.E + c, a);
+                stv<VW>(PART + ((long)part * p.V + v0 + r) * p.E + c, a);
             }
             return;
         }
@@ -165,14 +157,14 @@ __global__ void __launch_bounds__(EM_BLK) k_em_bwd(const float *__restrict__ IDS
         for (int r = 0; r < EM_R; r++) {
 #pragma unroll
             for (int e = 0; e < VW; e++) d[r][e] = 0.0f;
-            if (hit >> r & 1) em_ld<VW>(DTABLE + (long)(v0 + r) * p.E + c, d[r]);      // (a named row is below V)
+            if (hit >> r & 1) ldv<VW>(DTABLE + (long)(v0 + r) * p.E + c, d[r]);      // (a named row is below V)
         }
 #pragma unroll
         for (int r = 0; r < EM_R; r++) {
             bool any = false;
 #pragma unroll
             for (int e = 0; e < VW; e++) { const float a = acc[r * CH + e]; if (a != 0.0f) { d[r][e] += a; any = true; } }     // a sum of exactly 0 leaves the element's bits
-            if (any && (hit >> r & 1)) em_st<VW>(DTABLE + (long)(v0 + r) * p.E + c, d[r]);
+            if (any && (hit >> r & 1)) stv<VW>(DTABLE + (long)(v0 + r) * p.E + c, d[r]);
         }
         return;
     }
@@ -189,8 +181,8 @@ __global__ void __launch_bounds__(EM_BLK) k_em_bwd(const float *__restrict__ IDS
 #pragma unroll 4
             for (int n = n0; n < n1; n++) {
                 float v[VW];
-                em_ld<VW>(DY + n * LE + item * VW, v);
-                if (DX) em_st<VW>(DX + n * LE + item * VW, v);
+                ldv<VW>(DY + n * LE + item * VW, v);
+                if (DX) stv<VW>(DX + n * LE + item * VW, v);
 #pragma unroll
                 for (int e = 0; e < VW; e++) s[e] += v[e];
             }
@@ -219,11 +211,11 @@ template <int VW>
 __global__ void __launch_bounds__(EM_BLK) k_em_fold(const float *__restrict__ PART, float *__restrict__ DTABLE, long nitems, long VE, int P) {
     for (long i = (long)blockIdx.x * EM_BLK + threadIdx.x; i < nitems; i += (long)gridDim.x * EM_BLK) {
         float a[VW];
-        em_ld<VW>(PART + i * VW, a);
+        ldv<VW>(PART + i * VW, a);
 #pragma unroll 8
         for (int q = 1; q < P; q++) {
             float b[VW];
-            em_ld<VW>(PART + q * VE + i * VW, b);
+            ldv<VW>(PART + q * VE + i * VW, b);
 #pragma unroll
             for (int e = 0; e < VW; e++) a[e] += b[e];
         }
@@ -235,7 +227,6 @@ __global__ void __launch_bounds__(EM_BLK) k_em_fold(const float *__restrict__ PA
 
 // ------------------------------------------------------------------ the plan: what the launch code uses, and what t4k_embed_plan reports
 struct EmPlan { int rung, vw, R, P, fl, bl, swg, tl, tsh, wb, fgrid, slabs, chunks, pwg; long per, units, ws; };
-long em_cdiv(long a, long b) { return (a + b - 1) / b; }
 // admission (who: the entry's name for the message) in 64 bits: the extents may be anything their types hold.  g is written on T4K_OK alone
 int em_plan(EmPlan &o, const char *who, long T, int L, int V, int E, int pos, bool aligned, long ws_bytes) {
     if (T < 1 || L < 1 || E < 1 || V < 0) return fail(T4K_ERR_ARG, "%s: an extent below 1 (T=%ld L=%d V=%d E=%d)", who, T, L, V, E);
@@ -253,38 +244,28 @@ int em_plan(EmPlan &o, const char *who, long T, int L, int V, int E, int pos, bo
     g.tl = 1; g.tsh = 0;
     while (g.tl < 64 && g.tl < items) { g.tl <<= 1; g.tsh++; }
     g.wb = 64;
-    while (g.wb > 64 / g.tl && em_cdiv(T, 4L * g.wb) < 1024) g.wb >>= 1;
-    g.fgrid = (int)std::min(em_cdiv(T, 4L * g.wb), (long)EM_WG);
+    while (g.wb > 64 / g.tl && ceil_div(T, 4L * g.wb) < 1024) g.wb >>= 1;
+    g.fgrid = (int)std::min(ceil_div(T, 4L * g.wb), (long)EM_WG);
     g.fl = 1;
-    g.pwg = pos ? (int)em_cdiv((long)L * items, EM_PI) : 0;                 // workgroups of the dPOS | DX role
+    g.pwg = pos ? (int)ceil_div((long)L * items, EM_PI) : 0;                // workgroups of the dPOS | DX role
     if (V == 0) {                                                           // position mode
         g.rung = 0; g.R = 0; g.P = 1; g.bl = 1; g.swg = g.pwg; g.slabs = g.chunks = 0; g.per = 0; g.units = 0; g.ws = 0;
         o = g; return T4K_OK;
     }
     g.R = EM_R;
-    g.slabs = (int)em_cdiv(V, EM_R); g.chunks = (int)em_cdiv(items, 64);
+    g.slabs = (int)ceil_div(V, EM_R); g.chunks = (int)ceil_div(items, 64);
     const long base = (long)g.slabs * g.chunks;                             // units the vocabulary gives by itself
     const long bytes = (long)V * E * (long)sizeof(float);                   // one part's rows in the workspace
-    long P = std::min(std::min(em_cdiv(EM_UNITS, base), std::max(1L, T / EM_PART)), std::min(ws_bytes, 0x7fffffffL) / bytes);   // (the bytes used are reported in an int)
+    long P = std::min(std::min(ceil_div(EM_UNITS, base), std::max(1L, T / EM_PART)), std::min(ws_bytes, 0x7fffffffL) / bytes);   // (the bytes used are reported in an int)
     if (P < 1) P = 1;
-    g.per = em_cdiv(em_cdiv(T, 64), P) * 64;                                // tokens of a part: whole id loads
-    g.P = (int)em_cdiv(T, g.per);
+    g.per = ceil_div(ceil_div(T, 64), P) * 64;                              // tokens of a part: whole id loads
+    g.P = (int)ceil_div(T, g.per);
     g.rung = g.P > 1 ? 2 : 1;
     g.units = base * g.P;
-    g.swg = (int)(em_cdiv(g.units, 4) + g.pwg);
+    g.swg = (int)(ceil_div(g.units, 4) + g.pwg);
     g.bl = g.rung;
     g.ws = g.P > 1 ? g.P * bytes : 0;
     o = g; return T4K_OK;
-}
-// do [a, a + na) and [b, b + nb) floats share a byte?  (NULL: no.)  same_ok: the two being ONE tensor is no overlap
-bool em_clash(const float *a, long na, const float *b, long nb, bool same_ok = false) {
-    if (!a || !b) return false;
-    if (same_ok && a == b) return false;
-    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + (uintptr_t)na * sizeof(float), b0 = (uintptr_t)b, b1 = b0 + (uintptr_t)nb * sizeof(float);
-    return a0 < b1 && b0 < a1;
-}
-bool em16(const void *a, const void *b, const void *c, const void *d, const void *e) {
-    return aligned16(a) && aligned16(b) && aligned16(c) && aligned16(d) && aligned16(e);
 }
 
 } // namespace
@@ -306,9 +287,9 @@ int t4k_embed_fwd(const float *IDS, const float *X, const float *TABLE, const fl
     if (IDS && (V < 1 || !TABLE)) return fail(T4K_ERR_ARG, "t4k_embed_fwd: token mode needs V >= 1 and TABLE");
     if (X && (V != 0 || !POS || TABLE)) return fail(T4K_ERR_ARG, "t4k_embed_fwd: position mode needs V = 0, POS and no TABLE");
     EmPlan g;
-    const int rc = em_plan(g, "t4k_embed_fwd", T, L, V, E, POS ? 1 : 0, em16(IDS, X, TABLE, POS, O), (long)(st().ws_bytes / 2)); if (rc != T4K_OK) return rc;
+    const int rc = em_plan(g, "t4k_embed_fwd", T, L, V, E, POS ? 1 : 0, all16(IDS, X, TABLE, POS, O), (long)(st().ws_bytes / 2)); if (rc != T4K_OK) return rc;
     const long n = T * E;
-    if (em_clash(O, n, IDS, T) || em_clash(O, n, X, n) || em_clash(O, n, TABLE, (long)V * E) || em_clash(O, n, POS, (long)L * E))
+    if (clash(O, n, IDS, T) || clash(O, n, X, n) || clash(O, n, TABLE, (long)V * E) || clash(O, n, POS, (long)L * E))
         return fail(T4K_ERR_ARG, "t4k_embed_fwd: the output overlaps another operand");
     hipStream_t hs = t4k::S(s);
     EmF p;
@@ -336,17 +317,17 @@ int t4k_embed_bwd(const float *IDS, const float *DY, float *DTABLE, float *DPOS,
     if (train && V == 0 && !DPOS) return fail(T4K_ERR_ARG, "t4k_embed_bwd: DPOS is required when train != 0");
     if (V == 0) DTABLE = nullptr;
     EmPlan g;
-    const int rc = em_plan(g, "t4k_embed_bwd", T, L, V, E, (V == 0 || DPOS) ? 1 : 0, em16(IDS, DY, DTABLE, DPOS, DX), (long)(st().ws_bytes / 2)); if (rc != T4K_OK) return rc;
+    const int rc = em_plan(g, "t4k_embed_bwd", T, L, V, E, (V == 0 || DPOS) ? 1 : 0, all16(IDS, DY, DTABLE, DPOS, DX), (long)(st().ws_bytes / 2)); if (rc != T4K_OK) return rc;
     const long n = T * E, ve = (long)V * E, le = (long)L * E;
-    if (em_clash(DX, n, DY, n, true) || em_clash(DX, n, DPOS, le) || em_clash(DTABLE, ve, DPOS, le) ||
-        em_clash(DTABLE, ve, DY, n) || em_clash(DTABLE, ve, IDS, T) || em_clash(DPOS, le, DY, n) || em_clash(DPOS, le, IDS, T))
+    if (clash(DX, n, DY, n, true) || clash(DX, n, DPOS, le) || clash(DTABLE, ve, DPOS, le) ||
+        clash(DTABLE, ve, DY, n) || clash(DTABLE, ve, IDS, T) || clash(DPOS, le, DY, n) || clash(DPOS, le, IDS, T))
         return fail(T4K_ERR_ARG, "t4k_embed_bwd: an output overlaps another operand (DX may be DY, nothing else)");
     if (DX == DY) DX = nullptr;                                              // in place: nothing to copy
     if (!DTABLE && !DPOS && !DX) return T4K_OK;                              // train == 0 and no dX to move: nothing to do
     hipStream_t hs = t4k::S(s);
     EmB p;
     p.T = T; p.per = g.per; p.units = g.units; p.pitems = le / g.vw; p.L = L; p.V = V; p.E = E; p.N = (int)(T / L);
-    p.slabs = g.slabs; p.chunks = g.chunks; p.swg = DTABLE ? (int)em_cdiv(g.units, 4) : 0; p.fV = (float)V;
+    p.slabs = g.slabs; p.chunks = g.chunks; p.swg = DTABLE ? (int)ceil_div(g.units, 4) : 0; p.fV = (float)V;
     const int pwg = (DPOS || DX) ? g.pwg : 0;
     float *part = (DTABLE && g.P > 1) ? ws_for(s) : nullptr;
     const dim3 grid((unsigned)(p.swg + pwg)), blk(EM_BLK);
@@ -358,7 +339,7 @@ int t4k_embed_bwd(const float *IDS, const float *DY, float *DTABLE, float *DPOS,
         else                 T4K_LAUNCH((k_em_bwd<VW, 3>), grid, blk, 0, hs, IDS, DY, DTABLE, part, DPOS, DX, p);
         if (part) {
             const long nitems = ve / VW;
-            T4K_LAUNCH((k_em_fold<VW>), dim3((unsigned)std::min(em_cdiv(nitems, EM_BLK), (long)EM_WG)), blk, 0, hs, part, DTABLE, nitems, ve, g.P);
+            T4K_LAUNCH((k_em_fold<VW>), dim3((unsigned)std::min(ceil_div(nitems, EM_BLK), (long)EM_WG)), blk, 0, hs, part, DTABLE, nitems, ve, g.P);
         }
     });
     T4K_LAUNCH_CHECK();

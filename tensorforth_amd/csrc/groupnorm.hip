@@ -32,15 +32,6 @@ struct GnP {
     FastDiv dCgV, dG, dP;
 };
 
-template <int VW> __device__ __forceinline__ void gn_ld(const float *q, float (&v)[VW]) {
-    if constexpr (VW == 4) { const float4 t = *reinterpret_cast<const float4 *>(q); v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; }
-    else v[0] = *q;
-}
-template <int VW> __device__ __forceinline__ void gn_st(float *q, const float (&v)[VW]) {
-    if constexpr (VW == 4) *reinterpret_cast<float4 *>(q) = make_float4(v[0], v[1], v[2], v[3]);
-    else *q = v[0];
-}
-
 // the sum of two values over the team, in every thread: a fixed xor tree inside a wave, the 16 wave sums added in wave order
 template <int T> __device__ __forceinline__ void team_sum2(float &a, float &b, float *sm) {
     a = wave_sum_all(a); b = wave_sum_all(b);
@@ -83,12 +74,6 @@ __device__ __forceinline__ void team_colsum(float (&acc)[NV], const GnP &p, int 
         __syncthreads();
     }
 }
-// t = W dy, rounded wherever it is used: contracted into t - s1 it would be another number than the t that was summed, and a group of one element would
-// not get dx = 0
-__device__ __forceinline__ float gn_t(float w, float dy) {
-#pragma clang fp contract(off)
-    return w * dy;
-}
 // a slab row's cells of one column item: dW at [c], dB at [C + c]
 template <int VW> __device__ __forceinline__ void slab_put(float *row, int C, int c, const float (&acc)[2 * VW]) {
 #pragma unroll
@@ -127,7 +112,7 @@ __global__ void __launch_bounds__(T == 64 ? 256 : T) k_gn_fwd_res(const float *I
             const int row = j + k * p.RT;
 #pragma unroll
             for (int v = 0; v < VW; v++) x[k][v] = 0.f;
-            if (act && row < p.HW) { gn_ld<VW>(pi, x[k]); have |= 1u << k; }
+            if (act && row < p.HW) { ldv<VW>(pi, x[k]); have |= 1u << k; }
 #pragma unroll
             for (int v = 0; v < VW; v++) s += x[k][v];
         }
@@ -146,7 +131,7 @@ __global__ void __launch_bounds__(T == 64 ? 256 : T) k_gn_fwd_res(const float *I
         if (t == 0) { STAT[gid] = mean; STAT[p.NG + gid] = rstd; }
         if (act) {
             float gw[VW], gb[VW];
-            gn_ld<VW>(W + g * p.Cg + col * VW, gw); gn_ld<VW>(B + g * p.Cg + col * VW, gb);
+            ldv<VW>(W + g * p.Cg + col * VW, gw); ldv<VW>(B + g * p.Cg + col * VW, gb);
             float *po = O + first, *px = XH + first;
 #pragma unroll
             for (int k = 0; k < GN_R; k++, po += step, px += step) {
@@ -154,7 +139,7 @@ __global__ void __launch_bounds__(T == 64 ? 256 : T) k_gn_fwd_res(const float *I
                     float xh[VW], y[VW];
 #pragma unroll
                     for (int v = 0; v < VW; v++) { xh[v] = (x[k][v] - mean) * rstd; y[v] = xh[v] * gw[v] + gb[v]; }
-                    gn_st<VW>(px, xh); gn_st<VW>(po, y);
+                    stv<VW>(px, xh); stv<VW>(po, y);
                 }
             }
         }
@@ -176,7 +161,7 @@ __global__ void __launch_bounds__(T == 64 ? 256 : T) k_gn_bwd_res(const float *_
         float dy[GN_R][VW], xh[GN_R][VW], gw[VW], acc[2 * VW];
 #pragma unroll
         for (int v = 0; v < VW; v++) { gw[v] = 0.f; acc[v] = 0.f; acc[VW + v] = 0.f; }
-        if (act) gn_ld<VW>(W + g * p.Cg + col * VW, gw);
+        if (act) ldv<VW>(W + g * p.Cg + col * VW, gw);
         float a1 = 0.f, a2 = 0.f;
         const long first = base + (long)j * p.C, step = (long)p.RT * p.C;
         const float *pd = DY + first, *px = XH + first;
@@ -186,10 +171,10 @@ __global__ void __launch_bounds__(T == 64 ? 256 : T) k_gn_bwd_res(const float *_
             const int row = j + k * p.RT;
 #pragma unroll
             for (int v = 0; v < VW; v++) { dy[k][v] = 0.f; xh[k][v] = 0.f; }
-            if (act && row < p.HW) { gn_ld<VW>(pd, dy[k]); gn_ld<VW>(px, xh[k]); have |= 1u << k; }
+            if (act && row < p.HW) { ldv<VW>(pd, dy[k]); ldv<VW>(px, xh[k]); have |= 1u << k; }
 #pragma unroll
             for (int v = 0; v < VW; v++) {
-                const float tt = gn_t(gw[v], dy[k][v]);
+                const float tt = mul_rn(gw[v], dy[k][v]);
                 a1 += tt; a2 += tt * xh[k][v];
                 acc[v] += dy[k][v] * xh[k][v]; acc[VW + v] += dy[k][v];
             }
@@ -204,8 +189,8 @@ __global__ void __launch_bounds__(T == 64 ? 256 : T) k_gn_bwd_res(const float *_
                 if ((have >> k) & 1u) {
                     float dx[VW];
 #pragma unroll
-                    for (int v = 0; v < VW; v++) dx[v] = rstd * (gn_t(gw[v], dy[k][v]) - s1 - xh[k][v] * s2);
-                    gn_st<VW>(po, dx);
+                    for (int v = 0; v < VW; v++) dx[v] = rstd * (mul_rn(gw[v], dy[k][v]) - s1 - xh[k][v] * s2);
+                    stv<VW>(po, dx);
                 }
             }
         }
@@ -235,7 +220,7 @@ __device__ __forceinline__ void gn_items(const GnP &p, const GnT &m, int rb, int
 template <int VW>
 __device__ __forceinline__ float gn_sum_rows(const float *I, const GnP &p, const GnT &m, int rb, int re) {
     float s = 0.f;
-    gn_items<VW>(p, m, rb, re, [&](long o, int) { float x[VW]; gn_ld<VW>(I + o, x);
+    gn_items<VW>(p, m, rb, re, [&](long o, int) { float x[VW]; ldv<VW>(I + o, x);
 #pragma unroll
         for (int v = 0; v < VW; v++) s += x[v]; });
     return s;
@@ -243,7 +228,7 @@ __device__ __forceinline__ float gn_sum_rows(const float *I, const GnP &p, const
 template <int VW>
 __device__ __forceinline__ float gn_sq_rows(const float *I, const GnP &p, const GnT &m, int rb, int re, float mean) {
     float q = 0.f;
-    gn_items<VW>(p, m, rb, re, [&](long o, int) { float x[VW]; gn_ld<VW>(I + o, x);
+    gn_items<VW>(p, m, rb, re, [&](long o, int) { float x[VW]; ldv<VW>(I + o, x);
 #pragma unroll
         for (int v = 0; v < VW; v++) { const float d = x[v] - mean; q += d * d; } });
     return q;
@@ -256,15 +241,15 @@ __device__ __forceinline__ void gn_apply_rows(const float *I, float *O, float *X
         const int col = m.col0 + cc * GN_T;
         if (!m.act || col >= p.CgV) continue;
         float gw[VW], gb[VW];
-        gn_ld<VW>(W + col * VW, gw); gn_ld<VW>(B + col * VW, gb);
+        ldv<VW>(W + col * VW, gw); ldv<VW>(B + col * VW, gb);
 #pragma unroll 4
         for (int row = rb + m.j; row < re; row += p.RT) {
             const long o = (long)row * p.C + col * VW;
             float x[VW], xh[VW], y[VW];
-            gn_ld<VW>(I + o, x);
+            ldv<VW>(I + o, x);
 #pragma unroll
             for (int v = 0; v < VW; v++) { xh[v] = (x[v] - mean) * rstd; y[v] = xh[v] * gw[v] + gb[v]; }
-            gn_st<VW>(XH + o, xh); gn_st<VW>(O + o, y);
+            stv<VW>(XH + o, xh); stv<VW>(O + o, y);
         }
     }
 }
@@ -280,15 +265,15 @@ __device__ __forceinline__ void gn_bwd_sum_rows(const float *W, const float *DY,
 #pragma unroll
         for (int v = 0; v < VW; v++) { acc[v] = 0.f; acc[VW + v] = 0.f; gw[v] = 0.f; }
         if (ok) {
-            gn_ld<VW>(W + col * VW, gw);
+            ldv<VW>(W + col * VW, gw);
 #pragma unroll 4
             for (int row = rb + m.j; row < re; row += p.RT) {
                 const long o = (long)row * p.C + col * VW;
                 float dy[VW], xh[VW];
-                gn_ld<VW>(DY + o, dy); gn_ld<VW>(XH + o, xh);
+                ldv<VW>(DY + o, dy); ldv<VW>(XH + o, xh);
 #pragma unroll
                 for (int v = 0; v < VW; v++) {
-                    const float tt = gn_t(gw[v], dy[v]);
+                    const float tt = mul_rn(gw[v], dy[v]);
                     a1 += tt; a2 += tt * xh[v];
                     acc[v] += dy[v] * xh[v]; acc[VW + v] += dy[v];
                 }
@@ -307,15 +292,15 @@ __device__ __forceinline__ void gn_dx_rows(const float *W, const float *DY, cons
         const int col = m.col0 + cc * GN_T;
         if (!m.act || col >= p.CgV) continue;
         float gw[VW];
-        gn_ld<VW>(W + col * VW, gw);
+        ldv<VW>(W + col * VW, gw);
 #pragma unroll 4
         for (int row = rb + m.j; row < re; row += p.RT) {
             const long o = (long)row * p.C + col * VW;
             float dy[VW], xh[VW], dx[VW];
-            gn_ld<VW>(DY + o, dy); gn_ld<VW>(XH + o, xh);
+            ldv<VW>(DY + o, dy); ldv<VW>(XH + o, xh);
 #pragma unroll
-            for (int v = 0; v < VW; v++) dx[v] = rstd * (gn_t(gw[v], dy[v]) - s1 - xh[v] * s2);
-            gn_st<VW>(DX + o, dx);
+            for (int v = 0; v < VW; v++) dx[v] = rstd * (mul_rn(gw[v], dy[v]) - s1 - xh[v] * s2);
+            stv<VW>(DX + o, dx);
         }
     }
 }
@@ -457,7 +442,7 @@ int gn_plan(GnPlan &g, const char *who, int N, int HW, int C, int G, bool aligne
     const long avail = ws_bytes / (long)sizeof(float);
     if (g.part_floats > avail || (long)g.nslice > (avail - g.part_floats) / (2L * C))
         return fail(T4K_ERR_UNSUPPORTED, "%s: the dW | dB slab (%d x %ld floats) does not fit the workspace", who, g.nslice, 2L * C);
-    g.fold = g.nslice <= 32 ? 1 : 2;                                       // as conv_geo.hip: few slices x many outputs walk whole slabs, else a wave per output
+    g.fold = fold_kind(g.nslice);
     return T4K_OK;
 }
 GnP gn_parms(const GnPlan &g, int N, int HW, int C, int G, float eps) {
@@ -472,9 +457,6 @@ GnP gn_parms(const GnPlan &g, int N, int HW, int C, int G, float eps) {
     p.eps = eps; p.fE = (float)((long)HW * p.Cg);
     p.dCgV = fast_div(p.CgV); p.dG = fast_div(G); p.dP = fast_div(g.P);
     return p;
-}
-bool gn16(const void *a, const void *b, const void *c, const void *d, const void *e = nullptr, const void *f = nullptr) {
-    return aligned16(a) && aligned16(b) && aligned16(c) && aligned16(d) && aligned16(e) && aligned16(f);
 }
 
 } // namespace
@@ -495,7 +477,7 @@ int t4k_groupnorm_fwd(const float *I, float *O, float *XH, const float *W, const
     if (!I || !O || !XH || !W || !B || !STAT) return fail(T4K_ERR_ARG, "t4k_groupnorm_fwd: null tensor");
     if (!(eps > 0.0f)) return fail(T4K_ERR_ARG, "t4k_groupnorm_fwd: eps must be above 0");
     GnPlan g;
-    const int rc = gn_plan(g, "t4k_groupnorm_fwd", N, HW, C, G, gn16(I, O, XH, W, B), (long)(st().ws_bytes / 2)); if (rc != T4K_OK) return rc;
+    const int rc = gn_plan(g, "t4k_groupnorm_fwd", N, HW, C, G, all16(I, O, XH, W, B), (long)(st().ws_bytes / 2)); if (rc != T4K_OK) return rc;
     const GnP p = gn_parms(g, N, HW, C, G, eps);
     hipStream_t hs = t4k::S(s);
     float *ws = ws_for(s);
@@ -519,7 +501,7 @@ int t4k_groupnorm_bwd(const float *W, const float *DY, const float *XH, float *S
     if (!W || !DY || !XH || !STAT || !DX) return fail(T4K_ERR_ARG, "t4k_groupnorm_bwd: null tensor");
     if (train && (!DW || !DB)) return fail(T4K_ERR_ARG, "t4k_groupnorm_bwd: DW and DB are required when train != 0");
     GnPlan g;
-    const int rc = gn_plan(g, "t4k_groupnorm_bwd", N, HW, C, G, gn16(W, DY, XH, DX), (long)(st().ws_bytes / 2)); if (rc != T4K_OK) return rc;
+    const int rc = gn_plan(g, "t4k_groupnorm_bwd", N, HW, C, G, all16(W, DY, XH, DX), (long)(st().ws_bytes / 2)); if (rc != T4K_OK) return rc;
     const GnP p = gn_parms(g, N, HW, C, G, 0.0f);
     hipStream_t hs = t4k::S(s);
     float *ws = ws_for(s), *slab = train ? ws + g.part_floats : nullptr;
@@ -533,10 +515,7 @@ int t4k_groupnorm_bwd(const float *W, const float *DY, const float *XH, float *S
             T4K_LAUNCH((k_gn_bwd_split<VW>), dim3((unsigned)(p.NG * p.P)), dim3(GN_T), 0, hs, W, DY, XH, STAT, DX, (const float *)ws, p);
         }
     });
-    if (train) {
-        if (g.fold == 1 && DB == DW + C) launch_fold_add(slab, DW, 2 * C, g.nslice, hs);
-        else launch_df_fold(slab, DW, DB, g.nslice, C, 2 * C, hs);
-    }
+    if (train) fold_dw_db(slab, DW, DB, C, g.nslice, g.fold, hs);
     T4K_LAUNCH_CHECK();
     return T4K_OK;
 }

@@ -153,8 +153,34 @@ inline int grid_for(long n, int per_thread = 1) {
     return (int)g;
 }
 inline bool aligned16(const void *p) { return (((uintptr_t)p) & 15) == 0; }
+// every pointer on 16 bytes (NULL, an operand that is absent, counts as aligned): what a unit asks before it takes its float4 path
+template <typename... P> inline bool all16(P... p) { return (aligned16(p) && ...); }
+// do [a, a + na) and [b, b + nb) floats share a byte?  (NULL: no.)  same_ok: the two being ONE tensor is no overlap
+inline bool clash(const float *a, long na, const float *b, long nb, bool same_ok = false) {
+    if (!a || !b) return false;
+    if (same_ok && a == b) return false;
+    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + (uintptr_t)na * sizeof(float), b0 = (uintptr_t)b, b1 = b0 + (uintptr_t)nb * sizeof(float);
+    return a0 < b1 && b0 < a1;
+}
+inline long ceil_div(long a, long b) { return (a + b - 1) / b; }
 
 // ---- device helpers ----
+// VW floats at q, one 16-byte access when VW is 4 (q on 16 bytes: the host's all16) and one dword when it is 1
+template <int VW> __device__ __forceinline__ void ldv(const float *q, float (&v)[VW]) {
+    if constexpr (VW == 4) { const float4 t = *reinterpret_cast<const float4 *>(q); v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; }
+    else v[0] = *q;
+}
+template <int VW> __device__ __forceinline__ void stv(float *q, const float (&v)[VW]) {
+    if constexpr (VW == 4) *reinterpret_cast<float4 *>(q) = make_float4(v[0], v[1], v[2], v[3]);
+    else *q = v[0];
+}
+// a b, rounded wherever it is used: the value that is summed and the value used later must be the same number (the norms' backward: g = W dy goes into
+// the group's or token's mean and then into g - mean).  Contracted into that subtraction it would be another number than the one that was summed, and a
+// group of one element would not get dx = 0
+__device__ __forceinline__ float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);

@@ -224,3 +224,9 @@ def test_rejections(t4k):
         assert np.isnan(dv.get(h, (dv.n,))).all()
     guards_intact(dO, dOK, dL, dG)
     assert fwd() == OK and bwd() == OK
+    # the ranges are half-open: DQKV starting on the float behind QKV's last shares no byte with it and is admitted
+    dQG = Dev(np.concatenate([QKV.ravel(), nan(3 * N * L * E)]))
+    assert bwd([dQG.p, dYK.p, dDY.p, dLS.p, at(dQG, 3 * N * L * E)]) == OK, h.lib.t4k_last_error()
+    both = dQG.get(h, (2, 3 * N * L * E))
+    assert np.array_equal(both[0], QKV.ravel()) and not np.isnan(both[1]).any()
+    guards_intact(dQG)
