@@ -55,7 +55,8 @@ enum {
     T4K_L_USAMPLE, T4K_L_DCONV,
     T4K_L_ATTN,                        /* beyond the reference's list (appended, no value moves): multi-head attention, `vector{ heads causal } linear` */
     T4K_L_ADDNORM,                     /* ... and add & norm, out = norm(x + skip), `vector{ back mode } selu` */
-    T4K_L_EMBED                        /* ... and the embedding layer, token and learned position tables, `vector{ V E pos } upsample` */
+    T4K_L_EMBED,                       /* ... and the embedding layer, token and learned position tables, `vector{ V E pos } upsample` */
+    T4K_L_TOKSMAX                      /* ... and the per-token softmax / cross-entropy head over the channels, `1 softmax` */
 };
 /* rand_opt: reference src/util.h:22-25 */
 enum { T4K_UNIFORM = 0, T4K_NORMAL = 1 };
@@ -695,6 +696,42 @@ int t4k_embed_fwd(const float *IDS, const float *X, const float *TABLE, const fl
  * allocation, no synchronisation.  train == 0: token mode launches nothing, position mode copies DY to DX unless they are one tensor. */
 int t4k_embed_bwd(const float *IDS, const float *DY, float *DTABLE, float *DPOS, float *DX,
                   long T, int L, int V, int E, int train, t4k_stream_t s);
+/* the per-token softmax and cross-entropy head on NHWC fp32 tokens (csrc/token_ce.hip).  The reference has no such layer: its softmax
+ * normalises a whole sample.  X is [T, V]: T = N H W tokens, rows of V contiguous logits.
+ *   m_t = max_c x[t,c]   s_t = sum_c exp(x[t,c] - m_t)   lse_t = m_t + ln s_t   P[t,c] = exp(x[t,c] - m_t) / s_t   amax_t = the smallest c with x[t,c] == m_t
+ *   STAT[t] = (lse_t, (float)amax_t), [T, 2].
+ * Targets are ids as floats, IDS[T]: valid(t) <=> id_t >= 0 and id_t < V in float compares (NaN, negatives, -0.5, V, 1e9, +-inf are not valid), k_t =
+ * (int)id_t, formed only where valid - the id rule of t4k_embed_fwd.  A token that is not valid is padding: no loss term, no hit, a zero gradient row
+ * (torch's ignore_index).  Arithmetic as t4k_softmax: max shift, __expf, fp32 sums in fixed trees, one fp32 division per element; -inf logits are admitted
+ * where a row keeps a finite element (they store exactly +0), other non-finite logits are unspecified.
+ * Admission and the plan, on the host alone (no device needed; the entries call the same function), a function of its arguments only.  T < 1, V < 2, NULL
+ * out or ws_bytes < 0: T4K_ERR_ARG; V above 2^24 (float ids and the float arg-max are exact below it), T V at or above 2^31: T4K_ERR_UNSUPPORTED; out is
+ * untouched then.  width = 4 (16 bytes a lane) where aligned != 0 and V % 4 == 0, else 1 (dwords); items = V / width.
+ * out = { rung of the forward and the Jacobian backward (0: items <= 512, a team of lanes of a wave owns a token, the row in registers; 1: items <= 2048,
+ *         the workgroup is the team, its waves meet in LDS; 2: beyond, two passes over the row in the one launch), load path (4 | 1), lanes of a team (rung 0:
+ *         the power of two that leaves a lane at most 4 items, at most 64; else 256), tokens a wave has in flight on rung 0 (64 / team; 1 on the others: a
+ *         token a workgroup), passes over a row (1; 2 on rung 2), rescales R of a term of the sum on rung 2 (ceil(items / 2048) + 1, one a chunk of a lane's
+ *         walk and one from the lane to the workgroup; 0 on the register rungs), launches of t4k_token_ce_score (2 where T > 256 and the partial records fit
+ *         ws_bytes, else 1; every other entry is one launch), workspace bytes used (16 a score workgroup, min(ceil(T / 256), 256) of them, where it launches
+ *         twice, else 0) };  aligned != 0: every [T, V] pointer of the call on 16 bytes */
+int t4k_token_ce_plan(long T, int V, int aligned, long ws_bytes, int out[8]);
+/* the forward: P [T, V] and STAT [T, 2] from X.  One launch, X read once from memory (rung 2 reads a row a second time, from the cache); STAT is stored once
+ * per token.  The arg-max is the FIRST maximum on every rung.  No output may overlap another operand (T4K_ERR_ARG).  Common to the four launch entries: a
+ * NULL pointer is T4K_ERR_ARG; no floating-point atomics, fixed trees, the same bits on every call; no allocation, no synchronisation, no read-back (legal
+ * under capture); a refusal leaves a t4k_last_error text, launches nothing and writes nothing. */
+int t4k_token_softmax_fwd(const float *X, float *P, float *STAT, long T, int V, t4k_stream_t s);
+/* the Jacobian product, for a layer that is not the net's last: p = exp(x[t,c] - lse_t) with lse from STAT, g_t = sum_c DY[t,c] p[t,c], DX[t,c] =
+ * p (DY[t,c] - g_t).  One launch, the forward's rungs.  DX may be X itself (a lane stores the items it loaded); any other overlap: T4K_ERR_ARG. */
+int t4k_token_softmax_bwd(const float *X, const float *STAT, const float *DY, float *DX, long T, int V, t4k_stream_t s);
+/* the cross-entropy gradient of a last layer against id targets, a SUM (unscaled, as out - target is for every other head): DX[t,c] = valid(t) ? P[t,c] -
+ * (c == k_t ? 1 : 0) : 0.  One launch, 8 bytes an element: an id is read once per token, a padding row is stored as zeros without its P being read.  DX
+ * must not overlap P or IDS (T4K_ERR_ARG). */
+int t4k_token_ce_bwd(const float *P, const float *IDS, float *DX, long T, int V, t4k_stream_t s);
+/* loss and hits of a batch in one call: nll_t = valid(t) ? -ln(max(P[t,k_t], FLT_MIN)) : 0;  REC, three 32-bit words at a device-visible address (it may be
+ * pinned host memory: the kernel's store is the read-back) = { float sum_t nll_t, int #{t : valid(t) and amax_t == k_t}, int #{t : valid(t)} }, amax from
+ * STAT.  A fixed two-level sum: per workgroup, then one workgroup over the partial records in the first half of the stream's workspace (the plan's launch
+ * count). */
+int t4k_token_ce_score(const float *P, const float *STAT, const float *IDS, void *REC, long T, int V, t4k_stream_t s);
 /* k_sgd nmath.cu:419: dg=DG/Nw; beta~0: G-=lr*dg else M=b*M+(1-b)*dg, G-=lr*M; DG=0 */
 int t4k_sgd(float *G, float *DG, float *M, int Nw, float lr, float beta, long n, t4k_stream_t s);
 /* k_adam nmath.cu:438 (no bias correction, eps outside sqrt): zeroes DG */

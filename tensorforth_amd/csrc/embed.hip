@@ -32,12 +32,6 @@ template <int VW> __device__ __forceinline__ void em_st_nt(float *q, const float
     if constexpr (VW == 4) __builtin_nontemporal_store(v4f{v[0], v[1], v[2], v[3]}, reinterpret_cast<v4f *>(q));
     else __builtin_nontemporal_store(v[0], q);
 }
-// the id of a token: -1 for padding (NaN, negatives, -0.5, V and above: every compare is a float compare, the id is formed only where they hold)
-__device__ __forceinline__ int em_id(float x, float fV, int V) {
-    if (!(x >= 0.0f && x < fV)) return -1;
-    const int id = (int)x;
-    return id < V ? id : -1;
-}
 
 // ------------------------------------------------------------------ forward: one launch.  SRC = the ids (TOK) or x
 template <int VW, bool TOK>
@@ -49,7 +43,7 @@ __global__ void __launch_bounds__(EM_BLK) k_em_fwd(const float *__restrict__ SRC
         const long t0 = b * p.wb, tm = t0 + lane;
         int id = -1, l = 0;
         if (lane < p.wb && tm < p.T) {                                          // one lane reads a token's id and works out its position, once
-            if constexpr (TOK) id = em_id(SRC[tm], p.fV, p.V);
+            if constexpr (TOK) id = token_id(SRC[tm], p.fV, p.V);
             if (POS) l = (int)(tm % p.L);
         }
         for (int k = 0; k < p.wb; k += G) {                                     // (uniform; k + sub < wb <= 64)
@@ -106,7 +100,7 @@ __global__ void __launch_bounds__(EM_BLK) k_em_bwd(const float *__restrict__ IDS
                 const long tm = b4 + u * 64 + lane;
                 r4[u] = -1;
                 if (tm < t1) {
-                    const int id = em_id(IDS[tm], p.fV, p.V);
+                    const int id = token_id(IDS[tm], p.fV, p.V);
                     if (id >= v0 && id < v0 + EM_R) r4[u] = id - v0;
                 }
             }

@@ -174,6 +174,13 @@ template <int VW> __device__ __forceinline__ void stv(float *q, const float (&v)
     if constexpr (VW == 4) *reinterpret_cast<float4 *>(q) = make_float4(v[0], v[1], v[2], v[3]);
     else *q = v[0];
 }
+// the id a float names among V rows or classes (embed.hip, token_ce.hip): -1 for padding (NaN, negatives, -0.5, V and above: every compare is a float
+// compare, the id is formed only where they hold)
+__device__ __forceinline__ int token_id(float x, float fV, int V) {
+    if (!(x >= 0.0f && x < fV)) return -1;
+    const int id = (int)x;
+    return id < V ? id : -1;
+}
 // a b, rounded wherever it is used: the value that is summed and the value used later must be the same number (the norms' backward: g = W dy goes into
 // the group's or token's mean and then into g - mean).  Contracted into that subtraction it would be another number than the one that was summed, and a
 // group of one element would not get dx = 0

@@ -130,6 +130,47 @@ static bool em_line_ok(const Tensor &in, const std::string &line) {
            V == in.iparm && pos == (int)in.stride[0];
 }
 
+// ---- the per-token softmax / cross-entropy head, `1 softmax`: a softmax over the C channels of every (n, h, w) token.  Its own layer kind,
+// T4K_L_TOKSMAX, so it joins no fused group and rides in no linear backward - the run, stack, head and block recognisers all name the kinds they take, and
+// none names this one.  No parameters; grad[4] = STAT T4(N, H, W, 2), (lse, arg-max) per token - the slot where an activation keeps its mask.  As the net's
+// last layer it takes id targets, one float per token (Model::tok_ids): backprop is one t4k_token_ce_bwd, `loss.ce` / `nn.hit` one t4k_token_ce_score.
+// Anywhere else its backward is the Jacobian product.  The entries are referenced weakly: over a C-ABI without them (the CPU oracle) the layer is admitted,
+// shaped, printed, saved and loaded, and forward / backprop / the id-target words refuse it - there is no host-side fallback.
+#pragma weak t4k_token_ce_plan
+#pragma weak t4k_token_softmax_fwd
+#pragma weak t4k_token_softmax_bwd
+#pragma weak t4k_token_ce_bwd
+#pragma weak t4k_token_ce_score
+static bool ts_admits(long T, int V) {
+    if (t4k_token_ce_plan) { int out[8]; return t4k_token_ce_plan(T, V, 1, 1L << 40, out) == T4K_OK; }
+    return V <= (1 << 24) && T < (1L << 31) && T * V < (1L << 31);
+}
+static long ts_tokens(Tensor &in) { return (long)in.N() * in.H() * in.W(); }
+static int ts_fwd(Tensor &in, Tensor &out, const float *x, t4k_stream_t s) {
+    if (!t4k_token_softmax_fwd) { hprintf("nn#ftoksmax failed: nn#ftoksmax axes=%d not supported\n", in.iparm); return T4K_ERR_UNSUPPORTED; }
+    return chk(t4k_token_softmax_fwd(x, out.data, in.grad[4]->data, ts_tokens(in), in.C(), s), "nn#ftoksmax");
+}
+static int ts_bwd(Tensor &in, const float *dy, t4k_stream_t s) {                  // not the last layer: the Jacobian product, dX over x (the reference's `in = dx`)
+    if (!t4k_token_softmax_bwd) { hprintf("nn#btoksmax failed: nn#btoksmax axes=%d not supported\n", in.iparm); return T4K_ERR_UNSUPPORTED; }
+    return chk(t4k_token_softmax_bwd(in.data, in.grad[4]->data, dy, in.data, ts_tokens(in), in.C(), s), "nn#btoksmax");
+}
+static int ts_ce_bwd(Tensor &in, Tensor &out, const float *ids, t4k_stream_t s) { // the last layer against id targets: P - onehot over x, padding rows zero
+    if (!t4k_token_ce_bwd) { hprintf("nn#btoksmax failed: nn#btoksmax axes=%d not supported\n", in.iparm); return T4K_ERR_UNSUPPORTED; }
+    return chk(t4k_token_ce_bwd(out.data, ids, in.data, ts_tokens(in), in.C(), s), "nn#btoksmax");
+}
+// model_load: the layer's line of the layer section must be its own, `axes=1toksmax`
+static bool ts_line_ok(const Tensor &in, const std::string &line) { return line == "axes=" + std::to_string(in.iparm) + LAYER_NAME[T4K_L_TOKSMAX]; }
+// an id target: the model's last layer is the token head and the tensor holds one float per token (C >= 2: never the output's numel)
+bool Model::tok_ids(Tensor &tgt) {
+    return layer.size() > 1 && at(-2).grad_fn == T4K_L_TOKSMAX && tgt.numel == (uint64_t)ts_tokens(at(-1)) && tgt.numel != at(-1).numel;
+}
+int Model::tok_score(Tensor &ids) {
+    Tensor &out = at(-1);
+    if (!t4k_token_ce_score) { hprintf("nn#ftoksmax failed: nn#ftoksmax score not supported\n"); return T4K_ERR_UNSUPPORTED; }
+    if (!hit_pin) { void *p = nullptr; if (chk(t4k_host_alloc(&p, 64), "nn#hit") != T4K_OK) return T4K_ERR_NOMEM; hit_pin = (int *)p; }   // (64 bytes: word 0 is t4k_hit's, words 4..6 the record)
+    return chk(t4k_token_ce_score(out.data, at(-2).grad[4]->data, ids.data, hit_pin + 4, ts_tokens(out), out.C(), stream()), "nn#toksmax score");
+}
+
 // ---------------------------------------------------------------- layer factory (Model::add)
 Model &Model::add(int fn, uint32_t n, DU bias, uint16_t *opt) {
     Tensor &in = at(-1);
@@ -306,6 +347,15 @@ Model &Model::add(int fn, uint32_t n, DU bias, uint16_t *opt) {
         if (pos) { in.grad[1] = &T4(1, in.H(), in.W(), E0); in.grad[3] = &T4(1, in.H(), in.W(), E0).zeros(); RAND(*in.grad[1], 0.02f); }
         in.iparm = V; in.stride[0] = (uint16_t)pos; in.stride[1] = in.stride[2] = in.stride[3] = 0; in.xparm = 0;
         layer.push_back(&T4(in.N(), in.H(), in.W(), E0));
+    } break;
+    case T4K_L_TOKSMAX: {
+        // `1 softmax` on a model (the reference has none): a softmax over the channels of every token; the output has the input's shape
+        auto refuse = [&](const char *why) { hprintf("nn#itoksmax axes=1? %s\n", why); };
+        if (in.C() < 2) { refuse("channels"); return *this; }        // nothing to normalise, and an id target could not be told from a dense one
+        if (!ts_admits(ts_tokens(in), in.C())) { refuse("shape"); return *this; }
+        in.grad[4] = &T4(in.N(), in.H(), in.W(), 2);
+        in.iparm = 1; in.xparm = 0;
+        layer.push_back(&T4(in.N(), in.H(), in.W(), in.C()));
     } break;
     default: hprintf("Model#add layer %d not supported\n", fn); return *this;
     }
@@ -839,6 +889,7 @@ const float *Model::fstep(Tensor &in, Tensor &out, const float *x) {
         an_fwd(in, out, x, in.iparm ? at(j - in.iparm).data : nullptr, s); break;
     }
     case T4K_L_EMBED: em_fwd(in, out, x, s); break;
+    case T4K_L_TOKSMAX: ts_fwd(in, out, x, s); break;
     default: hprintf("nn#fstep layer=%d not supported\n", fn);
     }
     return out.data;
@@ -854,7 +905,7 @@ Tensor &Model::onehot(Tensor &t) {
     Tensor &out = at(-1);
     const uint32_t N = out.N(), E = (uint32_t)out.HWC();
     if (hot) { hprintf("WARN: Model.onehot exists, replaced\n"); Store::get().free(*hot); }
-    else if (t.N() != N || (uint32_t)t.HWC() != E) { hprintf("Model.onehot dimension is not [%d,1,%d,1]\n", N, E); return t; }
+    else if ((t.N() != N || (uint32_t)t.HWC() != E) && !tok_ids(t)) { hprintf("Model.onehot dimension is not [%d,1,%d,1]\n", N, E); return t; }
     hot = &t; hit_ = hit(true);
     return *hot;
 }
@@ -873,6 +924,7 @@ void Model::onehot_hit(Dataset &d) {                    // Model::onehot(Dataset
     if (!hot) hot = &T4(out.N(), 1, E, 1);
     if ((uint32_t)d.batch_sz < out.N()) hot->zeros();     // short last batch: the rows past it stay zero and count nothing
     if (!hit_pin) { void *p; chk(t4k_host_alloc(&p, 64), "nn#hit"); hit_pin = (int *)p; }
+    tok_pending_ = false;
     chk(t4k_onehot_hit(d.label, hot->data, out.data, d.batch_sz, (int)E, hit_pin, stream()), "nn#onehot+hit");
     hit_pending_ = true;
 }
@@ -908,6 +960,8 @@ void Model::traced_onehot_hit(Dataset &d) {             // the same two steps wi
 }
 void Model::hit_lazy() {                                 // count on the GPU now, read it back only if somebody asks (`nn.hit`)
     if (!hot) { hit_ = 0; hit_pending_ = false; return; }
+    if (tok_ids(*hot)) { hit_pending_ = tok_pending_ = tok_score(*hot) == T4K_OK; return; }   // id targets: the token head's record, loss and hits in one launch
+    tok_pending_ = false;
     Tensor &out = at(-1);
     if (!hit_pin) { void *p; chk(t4k_host_alloc(&p, 64), "nn#hit"); hit_pin = (int *)p; }   // device-visible host word: the kernel's store IS the read-back
     chk(t4k_hit(out.data, hot->data, out.N(), (int)out.HWC(), hit_pin, stream()), "nn#hit");
@@ -941,7 +995,7 @@ int Model::hit(bool recalc) {                           // loss.cpp:75-107
     }
     if (hit_pending_) {
         t4k_sync(stream());                                // kernel completion makes its store to the pinned word visible (no copy command)
-        const int c = *(volatile int *)hit_pin;
+        const int c = *(volatile int *)(hit_pin + (tok_pending_ ? 5 : 0));
         hit_ = (int)dp_sum((DU)c); hit_pending_ = false;
     }
     return hit_;
@@ -949,6 +1003,15 @@ int Model::hit(bool recalc) {                           // loss.cpp:75-107
 DU Model::loss(Loss op) { return hot ? loss(op, *hot) : 0.0f; }
 DU Model::loss(Loss op, Tensor &tgt) {                  // loss.cpp:119-136: non-destructive (works on a copy)
     Tensor &out = at(-1);
+    if (op == LOSS_CE && tok_ids(tgt)) {                 // a token head against id targets: sum of the valid tokens' nll / N, hits in the same record
+        if (tok_score(tgt) != T4K_OK) return 0;
+        t4k_sync(stream());
+        const DU z = SCALAR(*(volatile float *)(hit_pin + 4) / (DU)out.N());   // SCALAR: a value whose mantissa LSB is set is an object handle to the VM
+        if (&tgt == hot) hit_pending_ = tok_pending_ = true;   // `nn.hit` reads the same record: no second launch
+        NLOG("  Model#loss: CE=%6.3f\n", z);
+        const int world = t4k_comm_world();
+        return (world < 2 || !train) ? z : SCALAR(dp_sum(z) / (DU)world);
+    }
     if (out.numel != tgt.numel) {
         hprintf("nn::loss model output shape[%d,%d,%d,%d] != tgt[%d,%d,%d,%d]\n", out.N(), out.H(), out.W(), out.C(), tgt.N(), tgt.H(), tgt.W(), tgt.C());
         return 0;
@@ -976,14 +1039,15 @@ Model &Model::backprop() {
 }
 Model &Model::backprop(Tensor &tgt) {
     Tensor &out = at(-1);
-    if (out.numel != tgt.numel) {                       // _bprep backprop.cu:75-109
+    const bool ids = tok_ids(tgt);                      // a token head takes one id per token
+    if (out.numel != tgt.numel && !ids) {               // _bprep backprop.cu:75-109
         hprintf("Model#bprep: Onehot wrong shape[%d,%d,%d,%d] != [%d,%d,%d,%d], numel=%ld,%ld ", tgt.N(), tgt.H(), tgt.W(), tgt.C(),
                out.N(), out.H(), out.W(), out.C(), (long)tgt.numel, (long)out.numel);
         return *this;
     }
     finalize();
     const double tb0 = trace_ms();
-    if (!replay(g_bwd_, tgt.data, (int)train, nullptr)) {
+    if (!replay(g_bwd_, tgt.data, (int)train | (ids ? 2 : 0), nullptr)) {
         const bool cap = capturing_;
         run_backward(tgt);
         end_capture(g_bwd_, cap);
@@ -1062,7 +1126,17 @@ void Model::run_backward(Tensor &tgt) {
     const float *dy0 = nullptr;                         // ... and where they left the gradient (default: the output tensor)
     const float *tg = nullptr;                          // `out -= target` still pending: the last linear layer's backward launch performs it
     NLOG("Model::bprep input(onehot) numel=%ld OK {\n", (long)tgt.numel);     // _bprep backprop.cu:84-106 (under trace nothing is fused: the loss derivative is a launch of its own)
+    tok_tgt_ = tok_ids(tgt) ? tgt.data : nullptr;
     switch (at(-2).grad_fn) {
+    case T4K_L_TOKSMAX:                                 // the token head rides in no linear backward
+        if (tok_tgt_) {                                 // id targets: P - onehot over the layer's input, one launch; the output keeps P (under trace bstep runs it, so the layer has its line)
+            if (!(trace && *trace) && layer.size() > 2) { ts_ce_bwd(at(-2), out, tok_tgt_, s); skip = 1; dy0 = at(-2).data; }
+            break;
+        }
+        if (fused && layer.size() > 2) {                // a dense target: out -= target and the pass-through, as behind a softmax
+            chk(t4k_tt_op2(T4K_SUB, out.data, tgt.data, out.data, at(-2).data, (long)out.numel, s), "bprep"); skip = 1; break;
+        }
+        chk(t4k_tt_op(T4K_SUB, out.data, tgt.data, out.data, (long)out.numel, s), "bprep"); break;
     case T4K_L_SIGMOID: case T4K_L_SOFTMAX: case T4K_L_LOGSMAX:
         if (fused && layer.size() > 3 && at(-3).grad_fn == T4K_L_LINEAR) { tg = tgt.data; skip = 1; break; }   // rides in the linear backward launch
         if (fused && layer.size() > 2) {                // out -= target, and the pass-through `in = out` of the last layer, in one launch
@@ -1217,6 +1291,10 @@ Model::Back Model::bstep(int i, Tensor &in, Tensor &out, const float *dy, bool l
         const int tap = an_tapper(in);
         an_bwd(in, dy, tap ? at(tap).data : nullptr, train, s); break;
     }
+    case T4K_L_TOKSMAX:
+        if (last && tok_tgt_) { ts_ce_bwd(in, out, tok_tgt_, s); break; }     // (traced, or a one-layer net: run_backward's prep left it here)
+        if (last) { lazy_copy(dy, in); return { dy }; }                      // a dense target: out - target passes through, as behind a softmax
+        ts_bwd(in, dy, s); break;                                            // inside a net: the Jacobian product, not the reference's pass-through
     case T4K_L_EMBED: em_bwd(in, out, dy, train, s); break;      // position mode: dX = dY over x (the reference's `in = dx`); token mode writes nothing into the ids, so a second backprop sees them
     default: hprintf("nn#bstep layer=%d not supported\n", fn);
     }
@@ -1440,6 +1518,8 @@ int model_load(Model &m, const char *fname) {
         if (m.at(i).grad_fn == T4K_L_ADDNORM && !an_line_ok(m.at(i), line_of(i))) { hprintf(" model format error (addnorm layer %d: %s)\n", i, line_of(i).c_str()); err = 1; }
     for (int i = 0; i + 1 < (int)m.layer.size() && !err; i++)                                  // ... and an embedding layer's; one error line a file
         if (m.at(i).grad_fn == T4K_L_EMBED && !em_line_ok(m.at(i), line_of(i))) { hprintf(" model format error (embed layer %d: %s)\n", i, line_of(i).c_str()); err = 1; }
+    for (int i = 0; i + 1 < (int)m.layer.size() && !err; i++)                                  // ... and a token head's
+        if (m.at(i).grad_fn == T4K_L_TOKSMAX && !ts_line_ok(m.at(i), line_of(i))) { hprintf(" model format error (toksmax layer %d: %s)\n", i, line_of(i).c_str()); err = 1; }
     if (err) { fclose(f); return err; }
     for (int i = 0; i + 1 < (int)m.layer.size() && i + 1 < (int)lines.size(); i++) {
         if (m.at(i).grad_fn != T4K_L_ATTN) continue;

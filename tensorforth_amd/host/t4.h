@@ -276,6 +276,10 @@ struct Model : Obj {
     void hit_lazy();
     void traced_onehot_hit(Dataset &d);                           // forward(dataset): enqueue the count, defer the read-back
     bool hit_pending_ = false;
+    bool tok_ids(Tensor &tgt);                 // a token head's id target: one float per token
+    int  tok_score(Tensor &ids);               // loss, hits and valid count of the batch into hit_pin[4..6], one call
+    bool tok_pending_ = false;                 // ... the pending hit count is that record's, not t4k_hit's word
+    const float *tok_tgt_ = nullptr;           // the id target of the backward in progress (NULL: a dense one)
     DU   loss(Loss op);
     DU   loss(Loss op, Tensor &tgt);
     Model &sgd(DU lr, DU b = 0.9f);

@@ -491,6 +491,11 @@ void VM::nnop(int op) {
         MTOS().add(T4K_L_EMBED, (uint32_t)(int)vo[0], 0, opt);
         return;
     }
+    // beyond the reference ( N m -- N ): a scalar axis mask on top of a model makes `softmax` a layer of its tensor twin's meaning (`T m softmax` above): m = 1,
+    // the C axis, is a softmax over the channels of every (n, h, w) token - the per-token head whose id targets make a language-model loss;
+    // the reference prints "( N -- ) no param needed!" here and leaves the scalar, which every other m still gets (mask 7 is what plain `softmax` means, the
+    // other masks are not built, and that text is pinned for them)
+    if (op == T4K_L_SOFTMAX && M1V() && tos_ == 1.0f) { POP(); MTOS().add(T4K_L_TOKSMAX); return; }
     if (TOS1T()) {                                       // tensor ops (destructive)
         Tensor &t = TTOS();
         switch (op) {
@@ -625,7 +630,7 @@ void VM::init_nn() {
             Model &m = is_m(tos_) ? MTOS() : MNOS();
             switch (m.at(-2).grad_fn) {
             case T4K_L_TANH: case T4K_L_SIGMOID: loss(LOSS_BCE); break;
-            case T4K_L_SOFTMAX: loss(LOSS_CE); break;
+            case T4K_L_SOFTMAX: case T4K_L_TOKSMAX: loss(LOSS_CE); break;
             case T4K_L_LOGSMAX: loss(LOSS_NLL); break;
             default: loss(LOSS_MSE);
             }
