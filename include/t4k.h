@@ -356,7 +356,15 @@ int t4k_logdet(const float *LU, int K, float *logdet_dev, int *sign_dev, t4k_str
  * the per-matrix entries: largest |a|, lowest row on a tie, |pivot| < 1e-6 = singular -> status_dev[b] = z + 1 (else 0).  A singular
  * entry does not stop the others; what it leaves in its outputs is unspecified, except det_dev[b] = 0.
  * Unlike the per-matrix entries, X and Pm are pure OUTPUTS: the kernel writes the identity itself.
- * K <= 0, batch < 0 or a NULL pointer: T4K_ERR_ARG; K > 1024: T4K_ERR_UNSUPPORTED. */
+ * K <= 0, batch < 0 or a NULL pointer: T4K_ERR_ARG; K > 1024: T4K_ERR_UNSUPPORTED.
+ * Four regimes by K: wave (K <= 32), workgroup (A, and X, in LDS: K <= 140, plu / det K <= 200), global (inverse, lu_inverse
+ * up to 192) and blocked (from there to 1024: right-looking PLU in panels of 32 columns, the trailing update and, for inverse and lu_inverse,
+ * the substitution X = U^-1 L^-1 P on fp32 MFMA; inverse leaves the packed L\U in A there). */
+/* The plan the four factorising entries launch from, and nothing else: pure host arithmetic, no device needed.  entry: 0 inverse, 1 plu,
+ * 2 lu_inverse, 3 det; aligned: every matrix pointer on a 16-byte boundary.  out = { regime (0 wave, 1 workgroup, 2 global, 3 blocked),
+ * threads per group, NB (32 in the blocked regime, else 0), LDS bytes, launches (1), workgroups, load path (4: 16-byte pieces, 1: dwords), 0 }.
+ * Refuses what the entries refuse with their codes (and an entry outside 0..3, or a NULL out, with T4K_ERR_ARG) and leaves out untouched then. */
+int t4k_linalg_batched_plan(int entry, int K, int batch, int aligned, int out[8]);
 /* Tensor::inverse tensor.cu:344-369 (k_find_pivot/k_swap_rows/k_diag/k_elim :742-836); no reference definition for the batch.
  * X[b] = inverse(A[b]) by Gauss-Jordan.  A is scratch: K <= 140 leaves it untouched, above that it holds the eliminated rows (column z
  * of it is not maintained) - treat it as undefined after the call. */

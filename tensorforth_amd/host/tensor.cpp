@@ -520,19 +520,34 @@ void Tensor::window(Tensor &S, const int soff[4], Tensor &D, const int doff[4], 
         chk(t4k_copy(S.data + so, D.data + dn, run, stream()), "copy");
     }
 }
+// The batched entries are referenced weakly (the CPU oracle's C-ABI has none).  A rank-2 matrix whose K the blocked regime of
+// csrc/linalg_batched.hip serves (t4k_linalg_batched_plan says which: DESIGN.md 3.8) goes through the batched entry as a batch of one;
+// the status word, the texts and the results' meaning are those of the per-matrix calls, which stay the path for every other K.
+#pragma weak t4k_inverse_batched
+#pragma weak t4k_plu_batched
+#pragma weak t4k_lu_inverse_batched
+#pragma weak t4k_lu_extract_batched
+#pragma weak t4k_det_batched
+#pragma weak t4k_linalg_batched_plan
+static bool blocked_regime(int entry, int K) {           // entry: 0 inverse, 1 plu, 2 lu_inverse
+    int out[8];
+    return t4k_linalg_batched_plan && t4k_linalg_batched_plan(entry, K, 1, 1, out) == T4K_OK && out[0] == 3;
+}
 static int read_status() { int s = 0; t4k_memcpy_d2h(&s, g_iscalar, sizeof(int), stream()); t4k_sync(stream()); return s; }
 Tensor &Tensor::inverse(Tensor &A, Tensor &I) {          // tensor.cu:344-369
     if (A.H() != A.W() || I.H() != I.W()) { hprintf(" A: square matrix required (%d x %d)\n", A.H(), A.W()); return A; }
     const int K = A.W();
     hprintf("  tensor#inverse [%d,%d]\n", K, K);
-    chk(t4k_inverse(A.data, I.data, K, g_iscalar, stream()), "inverse");
+    if (t4k_inverse_batched && blocked_regime(0, K)) chk(t4k_inverse_batched(A.data, I.data, K, 1, g_iscalar, stream()), "inverse_batched");
+    else chk(t4k_inverse(A.data, I.data, K, g_iscalar, stream()), "inverse");
     int st = read_status();
     if (st) { hprintf("  tensor#inverse: singular matrix at column %d\n", st - 1); return A; }
     return I;
 }
 Tensor &Tensor::plu(Tensor &A, Tensor &I, int *piv_dev) {
     if (A.H() != A.W()) { hprintf(" A: square matrix required (%d x %d)\n", A.H(), A.W()); return A; }
-    chk(t4k_plu(A.data, (&A == &I) ? nullptr : I.data, piv_dev, A.W(), g_iscalar, stream()), "plu");
+    if (t4k_plu_batched && blocked_regime(1, A.W())) chk(t4k_plu_batched(A.data, (&A == &I) ? nullptr : I.data, piv_dev, A.W(), 1, g_iscalar, stream()), "plu_batched");
+    else chk(t4k_plu(A.data, (&A == &I) ? nullptr : I.data, piv_dev, A.W(), g_iscalar, stream()), "plu");
     int st = read_status();
     if (st) { hprintf("  tensor#plu: singular at column %d\n", st - 1); return A; }
     return I;
@@ -542,7 +557,8 @@ Tensor &Tensor::lu_inverse(Tensor &A, Tensor &I) {
     const int K = A.W();
     hprintf("  tensor#lu_inverse [%d,%d]\n", K, K);
     Tensor &piv = Store::get().tensor(K);
-    chk(t4k_lu_inverse(A.data, I.data, (int *)piv.data, K, g_iscalar, stream()), "lu_inverse");
+    if (t4k_lu_inverse_batched && blocked_regime(2, K)) chk(t4k_lu_inverse_batched(A.data, I.data, (int *)piv.data, K, 1, g_iscalar, stream()), "lu_inverse_batched");
+    else chk(t4k_lu_inverse(A.data, I.data, (int *)piv.data, K, g_iscalar, stream()), "lu_inverse");
     int st = read_status();
     if (st) hprintf("  tensor#plu: singular at column %d\n", st - 1);
     Store::get().free(piv);
@@ -570,13 +586,8 @@ DU Tensor::det() {                                      // tensor.cu:431-456
 // The linear-algebra words over a batch T4[N,K,K,1] (beyond the reference, whose words take one rank-2 matrix: tenvm.cpp:134-216):
 // entry n is treated as the rank-2 word treats its matrix.  One t4k_*_batched launch and ONE read-back of an int[N] status array per
 // call; a singular entry prints the rank-2 word's line with " entry n" appended and does not stop the others.  The five symbols are
-// referenced weakly: over a C-ABI without them (the CPU oracle) the same methods loop over the entries with the per-matrix calls,
+// referenced weakly (the pragmas stand in front of the rank-2 words above): over a C-ABI without them (the CPU oracle) the same methods loop over the entries with the per-matrix calls,
 // the host filling the identity those expect.
-#pragma weak t4k_inverse_batched
-#pragma weak t4k_plu_batched
-#pragma weak t4k_lu_inverse_batched
-#pragma weak t4k_lu_extract_batched
-#pragma weak t4k_det_batched
 static void batch_status(const int *st_dev, int N, bool gauss_jordan, std::vector<int> *keep = nullptr) {
     std::vector<int> st(N);
     t4k_memcpy_d2h(st.data(), st_dev, sizeof(int) * N, stream()); t4k_sync(stream());

@@ -1,6 +1,7 @@
 """Batched linear algebra: each t4k_*_batched entry (one launch per call) against the loop of the per-matrix entry on the same device.
 
     python tools/linalg_batched_probe.py [--reps R] [--once] [--json out.json]
+    python tools/linalg_batched_probe.py --against PARENT/libt4hip.so [--reps R] [--json profiles/linalg_blocked_probe.json]
 
 Cases: 128 x 4^2, 128 x 16^2, 1024 x 16^2, 128 x 64^2, 32 x 128^2, 8 x 512^2 (fp32, diagonally dominant entries).  Per case and entry three wall
 times per call on the library's default stream, bracketed by t4k_sync and divided by the repetitions:
@@ -10,7 +11,13 @@ times per call on the library's default stream, bracketed by t4k_sync and divide
 The factorisations work in place, so every repetition of every path first restores the inputs with one device copy of the whole batch (and, for
 the per-matrix inverse / lu_inverse, one more of the identity those entries expect); det's loop is t4k_plu + t4k_logdet per matrix and, with
 read-back, the three read-backs Tensor::det makes.  --once: one call of each path per case and nothing else (the run to put under
-`rocprofv3 --kernel-trace --stats -- python tools/linalg_batched_probe.py --once`: dispatch counts per call)."""
+`rocprofv3 --kernel-trace --stats -- python tools/linalg_batched_probe.py --once`: dispatch counts per call).
+
+--against LIB: the blocked regime against another build of the library, e.g. the parent commit's (build it in a second checkout
+and pass its libt4hip.so): `plu`, `inverse`, `lu_inverse` and `det` on 32 x 256^2, 8 x 512^2, 2 x 768^2, 1 x 1024^2 and 8 x K^2 for K = 224 ... 512
+in steps of 32, random matrices.  Both libraries live in this process; inside every repeat this build's call and the other's ALTERNATE, each
+timed alone (inputs restored and the device idle before the clock starts, call + t4k_sync inside it).  A row reports min / median / max of
+both and whether this build's max is at or below the other's min - the rule that sets KB."""
 import argparse
 import ctypes
 import json
@@ -21,8 +28,45 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+AGAINST = [(32, 256), (8, 512), (2, 768), (1, 1024)] + [(8, K) for K in range(224, 513, 32)]
 CASES = [(128, 4), (128, 16), (1024, 16), (128, 64), (32, 128), (8, 512)]      # batch, K
 ENTRIES = ("inverse", "plu", "lu_inverse", "lu_extract", "det")
+
+
+def against(args):
+    import numpy as np
+    import torch
+    from tensorforth_amd.lib import T4K
+    new, old = T4K(os.path.join(ROOT, "tensorforth_amd", "libt4hip.so")), T4K(os.path.abspath(args.against))
+    for h in (new, old):
+        h.init(0); h.call("t4k_set_default_stream", None)
+    V = ctypes.c_void_p
+    rows = []
+    for batch, K in AGAINST:
+        rng = np.random.default_rng(K + batch)
+        A0 = torch.from_numpy(rng.standard_normal((batch, K, K)).astype(np.float32)).cuda()
+        A, X = torch.empty_like(A0), torch.empty_like(A0)
+        piv = torch.zeros(batch * K, dtype=torch.int32, device="cuda"); st = torch.zeros(batch, dtype=torch.int32, device="cuda"); det = torch.zeros(batch, device="cuda")
+        pa, px, pp, ps, pd = (V(t.data_ptr()) for t in (A, X, piv, st, det))
+        for e in ("plu", "inverse", "lu_inverse", "det"):
+            def run(h):
+                A.copy_(A0); torch.cuda.synchronize(); t0 = time.perf_counter()
+                if e == "plu": h.call("t4k_plu_batched", pa, None, pp, K, batch, ps, None)
+                elif e == "inverse": h.call("t4k_inverse_batched", pa, px, K, batch, ps, None)
+                elif e == "lu_inverse": h.call("t4k_lu_inverse_batched", pa, px, pp, K, batch, ps, None)
+                else: h.call("t4k_det_batched", pa, pp, K, batch, pd, ps, None)
+                h.call("t4k_sync", None)
+                return (time.perf_counter() - t0) * 1e6
+            run(new); run(old)                                          # warm: code objects loaded, LDS attributes set
+            tn, to = [], []
+            for _ in range(max(3, args.reps // 4)):
+                tn.append(run(new)); to.append(run(old))
+            mmm = lambda t: [round(min(t)), round(float(np.median(t))), round(max(t))]
+            rows.append({"case": "%d x %d^2" % (batch, K), "entry": e, "blocked_us": mmm(tn), "parent_us": mmm(to), "blocked_max_le_parent_min": max(tn) <= min(to)})
+            print(json.dumps(rows[-1]), flush=True)
+    if args.json:
+        with open(args.json, "w") as f:
+            f.write("[\n" + ",\n".join(" " + json.dumps(r) for r in rows) + "\n]\n")
 
 
 def main():
@@ -30,7 +74,10 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--once", action="store_true")
     ap.add_argument("--json")
+    ap.add_argument("--against", help="another build's libt4hip.so: the blocked rows, alternated against it")
     args = ap.parse_args()
+    if args.against:
+        return against(args)
     import numpy as np
     import torch
     from tensorforth_amd.lib import load
