@@ -56,7 +56,8 @@ enum {
     T4K_L_ATTN,                        /* beyond the reference's list (appended, no value moves): multi-head attention, `vector{ heads causal } linear` */
     T4K_L_ADDNORM,                     /* ... and add & norm, out = norm(x + skip), `vector{ back mode } selu` */
     T4K_L_EMBED,                       /* ... and the embedding layer, token and learned position tables, `vector{ V E pos } upsample` */
-    T4K_L_TOKSMAX                      /* ... and the per-token softmax / cross-entropy head over the channels, `1 softmax` */
+    T4K_L_TOKSMAX,                     /* ... and the per-token softmax / cross-entropy head over the channels, `1 softmax` */
+    T4K_L_GATEACT                      /* ... and the smooth and gated feed-forward activations, `vector{ kind gate } elu` */
 };
 /* rand_opt: reference src/util.h:22-25 */
 enum { T4K_UNIFORM = 0, T4K_NORMAL = 1 };
@@ -740,6 +741,29 @@ int t4k_token_ce_bwd(const float *P, const float *IDS, float *DX, long T, int V,
  * STAT.  A fixed two-level sum: per workgroup, then one workgroup over the partial records in the first half of the stream's workspace (the plan's launch
  * count). */
 int t4k_token_ce_score(const float *P, const float *STAT, const float *IDS, void *REC, long T, int V, t4k_stream_t s);
+/* the smooth and gated feed-forward activations on NHWC fp32 tokens (csrc/gateact.hip).  The reference has no such layer (its to-do list
+ * asks for "Swish, Mish").  X is [T, C]: T = N H W tokens.  kind picks f:
+ *   0  a (1 + erf(a / sqrt 2)) / 2                                      torch gelu(approximate="none")
+ *   1  a (1 + tanh(sqrt(2 / pi) (a + 0.044715 a^3))) / 2                torch gelu(approximate="tanh"), GPT-2
+ *   2  a sigmoid(a)                                                      torch silu
+ *   3  a tanh(softplus(a))                                               torch mish
+ * gate 0: Y [T, C] = f(X);  dX = dY f'(X).  gate 1 (C even, Hc = C / 2, a token's channels are [ A(Hc) | B(Hc) ]): Y [T, Hc] = f(A) B;  dA = dY B f'(A),
+ * dB = dY f(A), stored where A and B were - SwiGLU with kind 2, GeGLU with kind 0 or 1.  f and f' are finite for every finite float.  Nothing is stored
+ * between the passes: the backward forms f' from X.
+ * Admission and the plan, on the host alone (no device needed; the entries call the same function), a function of its arguments only.  T < 1, C < 1, kind
+ * outside 0..3, gate outside 0..1, an odd C with gate 1, NULL out: T4K_ERR_ARG; T C at or above 2^31: T4K_ERR_UNSUPPORTED; out is untouched then.
+ * load path = 4 (16 bytes a lane) where aligned != 0 and (gate 0: T C % 4 == 0, the tensor is one flat span; gate 1: Hc % 4 == 0, B's rows stay on 16
+ * bytes), else 1 (dwords); items = T Hc / path (Hc = C with gate 0).
+ * out = { rung (2 gate + (path == 1)), load path (4 | 1), items a lane has in flight (4), workgroups of the forward (ceil(items / 1024)), workgroups of the
+ *         backward (the same), launches of the forward (1), launches of the backward (1), 0 };  aligned != 0: every pointer of the call on 16 bytes */
+int t4k_gateact_plan(long T, int C, int kind, int gate, int aligned, int out[8]);
+/* Y from X, one launch, every byte moved once.  Y must not overlap X (T4K_ERR_ARG).  Common to the two launch entries: a NULL pointer is T4K_ERR_ARG; no
+ * LDS, no atomics, the same bits on every call; no allocation, no synchronisation, no read-back (legal under capture); a refusal leaves a t4k_last_error
+ * text, launches nothing and writes nothing. */
+int t4k_gateact_fwd(const float *X, float *Y, long T, int C, int kind, int gate, t4k_stream_t s);
+/* DX [T, C] from X [T, C] and DY [T, Hc], one launch.  DX may be X itself (a lane stores to the addresses it loaded); any other overlap among the three:
+ * T4K_ERR_ARG. */
+int t4k_gateact_bwd(const float *X, const float *DY, float *DX, long T, int C, int kind, int gate, t4k_stream_t s);
 /* k_sgd nmath.cu:419: dg=DG/Nw; beta~0: G-=lr*dg else M=b*M+(1-b)*dg, G-=lr*M; DG=0 */
 int t4k_sgd(float *G, float *DG, float *M, int Nw, float lr, float beta, long n, t4k_stream_t s);
 /* k_adam nmath.cu:438 (no bias correction, eps outside sqrt): zeroes DG */

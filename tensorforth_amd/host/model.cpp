@@ -171,6 +171,38 @@ int Model::tok_score(Tensor &ids) {
     return chk(t4k_token_ce_score(out.data, at(-2).grad[4]->data, ids.data, hit_pin + 4, ts_tokens(out), out.C(), stream()), "nn#toksmax score");
 }
 
+// ---- the smooth and gated feed-forward activations, `vector{ kind gate } elu`: GELU, tanh-GELU, SiLU, Mish, and f(A) B over a token's
+// [ A | B ] channels.  Its own layer kind, T4K_L_GATEACT, so it joins no fused group - the run, stack, head and block recognisers all name the kinds they
+// take, and none names this one (is_mact does not: there is no mask).  in.iparm = kind, in.stride[0] = gate.  No parameters and no stored state:
+// grad[0..4] stay NULL, and the backward forms f' from x, which the layer's input tensor still holds - every forward launch writes its layer's OUTPUT,
+// and the backward of the layers behind this one write their own inputs.  Per element and parameter-free: dp_bn_mode and the gradient exchange of a
+// data-parallel run do not concern it.  The entries are referenced weakly: over a C-ABI without them (the CPU oracle) the layer is admitted, shaped,
+// printed, saved and loaded, and forward / backprop refuse it - there is no host-side fallback.
+#pragma weak t4k_gateact_plan
+#pragma weak t4k_gateact_fwd
+#pragma weak t4k_gateact_bwd
+static bool ga_admits(long T, int C, int kind, int gate) {
+    if (t4k_gateact_plan) { int out[8]; return t4k_gateact_plan(T, C, kind, gate, 1, out) == T4K_OK; }
+    return kind >= 0 && kind <= 3 && gate >= 0 && gate <= 1 && !(gate && C % 2) && T < (1L << 31) && T * C < (1L << 31);
+}
+static int ga_fwd(Tensor &in, Tensor &out, const float *x, t4k_stream_t s) {
+    if (!t4k_gateact_fwd) { hprintf("nn#fgateact failed: nn#fgateact kind=%d not supported\n", in.iparm); return T4K_ERR_UNSUPPORTED; }
+    return chk(t4k_gateact_fwd(x, out.data, (long)in.N() * in.H() * in.W(), in.C(), in.iparm, in.stride[0], s), "nn#fgateact");
+}
+static int ga_bwd(Tensor &in, const float *dy, t4k_stream_t s) {                  // dX over x (the reference's `in = dx`): no staging copy
+    if (!t4k_gateact_bwd) { hprintf("nn#bgateact failed: nn#bgateact kind=%d not supported\n", in.iparm); return T4K_ERR_UNSUPPORTED; }
+    return chk(t4k_gateact_bwd(in.data, dy, in.data, (long)in.N() * in.H() * in.W(), in.C(), in.iparm, in.stride[0], s), "nn#bgateact");
+}
+// model_load: the layer has no blobs, so its `kind=<k>, gate=<g>gateact` line is all the file holds of it.  The gate is the model's structure (it halves
+// the channels) and must be the layer's own; the kind replaces the layer's.  false: the line is no gateact line, or one this layer cannot take
+static bool ga_from_line(Tensor &in, const std::string &line, bool apply) {
+    int kind = -1, gate = -1; char tail[16] = "";
+    if (sscanf(line.c_str(), "kind=%d, gate=%d%15s", &kind, &gate, tail) != 3 || strcmp(tail, "gateact")) return false;
+    if (kind < 0 || kind > 3 || gate != (int)in.stride[0]) return false;
+    if (apply) in.iparm = kind;
+    return true;
+}
+
 // ---------------------------------------------------------------- layer factory (Model::add)
 Model &Model::add(int fn, uint32_t n, DU bias, uint16_t *opt) {
     Tensor &in = at(-1);
@@ -356,6 +388,13 @@ Model &Model::add(int fn, uint32_t n, DU bias, uint16_t *opt) {
         in.grad[4] = &T4(in.N(), in.H(), in.W(), 2);
         in.iparm = 1; in.xparm = 0;
         layer.push_back(&T4(in.N(), in.H(), in.W(), in.C()));
+    } break;
+    case T4K_L_GATEACT: {
+        // `vector{ kind gate } elu` (the reference has none): gate 0 keeps the shape, gate 1 halves the channels.  Nothing is allocated but the output
+        const int kind = opt ? (int16_t)opt[0] : 0, gate = opt ? (int16_t)opt[1] : 0, C = in.C();
+        if (!ga_admits((long)in.N() * in.H() * in.W(), C, kind, gate)) { hprintf("nn#igateact kind=%d gate=%d? channels=%d\n", kind, gate, C); return *this; }
+        in.iparm = kind; in.stride[0] = (uint16_t)gate; in.stride[1] = in.stride[2] = in.stride[3] = 0; in.xparm = 0;
+        layer.push_back(&T4(in.N(), in.H(), in.W(), gate ? C / 2 : C));
     } break;
     default: hprintf("Model#add layer %d not supported\n", fn); return *this;
     }
@@ -890,6 +929,7 @@ const float *Model::fstep(Tensor &in, Tensor &out, const float *x) {
     }
     case T4K_L_EMBED: em_fwd(in, out, x, s); break;
     case T4K_L_TOKSMAX: ts_fwd(in, out, x, s); break;
+    case T4K_L_GATEACT: ga_fwd(in, out, x, s); break;
     default: hprintf("nn#fstep layer=%d not supported\n", fn);
     }
     return out.data;
@@ -1295,6 +1335,7 @@ Model::Back Model::bstep(int i, Tensor &in, Tensor &out, const float *dy, bool l
         if (last && tok_tgt_) { ts_ce_bwd(in, out, tok_tgt_, s); break; }     // (traced, or a one-layer net: run_backward's prep left it here)
         if (last) { lazy_copy(dy, in); return { dy }; }                      // a dense target: out - target passes through, as behind a softmax
         ts_bwd(in, dy, s); break;                                            // inside a net: the Jacobian product, not the reference's pass-through
+    case T4K_L_GATEACT: ga_bwd(in, dy, s); break;
     case T4K_L_EMBED: em_bwd(in, out, dy, train, s); break;      // position mode: dX = dY over x (the reference's `in = dx`); token mode writes nothing into the ids, so a second backprop sees them
     default: hprintf("nn#bstep layer=%d not supported\n", fn);
     }
@@ -1476,7 +1517,8 @@ Model &Model::adamw(DU lr, DU wd, DU b1, DU b2) { return gradient("adamw", OPTI_
 // layer order (the reference's own reload of the layer section is unfinished: `_parm` text is not Forth source).  An attention layer has
 // no blob: its `heads=<h>, causal=<c>attentn` line is read back into the model's attention layer at that place.  An add & norm layer saves
 // gamma and beta where it has them (mode != 0); its `back=<b>, mode=<m>addnorm` line must be the layer's own - a file with another is refused whole.  An
-// embedding layer saves TABLE ('w') and POS ('b'), whichever it has; its `vocab=<V>, pos=<p>embed  ` line is held to the same.
+// embedding layer saves TABLE ('w') and POS ('b'), whichever it has; its `vocab=<V>, pos=<p>embed  ` line is held to the same.  An
+// activation of DESIGN.md 3.24 has no blob: its `kind=<k>, gate=<g>gateact` line must carry the layer's gate, and its kind is read back into the layer.
 int model_save(Model &m, const char *fname) {
     FILE *f = fopen(fname, "wb");
     if (!f) { hprintf("} => failed to open for output\n"); return 1; }
@@ -1520,12 +1562,15 @@ int model_load(Model &m, const char *fname) {
         if (m.at(i).grad_fn == T4K_L_EMBED && !em_line_ok(m.at(i), line_of(i))) { hprintf(" model format error (embed layer %d: %s)\n", i, line_of(i).c_str()); err = 1; }
     for (int i = 0; i + 1 < (int)m.layer.size() && !err; i++)                                  // ... and a token head's
         if (m.at(i).grad_fn == T4K_L_TOKSMAX && !ts_line_ok(m.at(i), line_of(i))) { hprintf(" model format error (toksmax layer %d: %s)\n", i, line_of(i).c_str()); err = 1; }
+    for (int i = 0; i + 1 < (int)m.layer.size() && !err; i++)                                  // ... and an activation's of DESIGN.md 3.24 (checked here, taken below)
+        if (m.at(i).grad_fn == T4K_L_GATEACT && !ga_from_line(m.at(i), line_of(i), false)) { hprintf(" model format error (gateact layer %d: %s)\n", i, line_of(i).c_str()); err = 1; }
     if (err) { fclose(f); return err; }
     for (int i = 0; i + 1 < (int)m.layer.size() && i + 1 < (int)lines.size(); i++) {
         if (m.at(i).grad_fn != T4K_L_ATTN) continue;
         if (!attn_from_line(m.at(i), lines[i + 1])) { hprintf(" model format error (attention layer %d: %s)\n", i, lines[i + 1].c_str()); err = 1; }
     }
     if (err) { fclose(f); return err; }
+    for (int i = 0; i + 1 < (int)m.layer.size(); i++) if (m.at(i).grad_fn == T4K_L_GATEACT) ga_from_line(m.at(i), line_of(i), true);
     auto rd = [&](Tensor &t) {
         while (getline_(line) && !line.length()) {}      // skip blank lines
         if (line.size() < 3 || line[0] != '-' || line[1] != '-' || line[2] != '-') { hprintf(" model format error"); err = 1; return; }   // aio_model.cpp:211 (no newline there either)

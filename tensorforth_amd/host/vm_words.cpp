@@ -491,6 +491,18 @@ void VM::nnop(int op) {
         MTOS().add(T4K_L_EMBED, (uint32_t)(int)vo[0], 0, opt);
         return;
     }
+    // beyond the reference ( N V -- N ): a vector{ kind gate } on top of a model makes `elu` a smooth feed-forward activation: kind 0 GELU, 1
+    // tanh-GELU, 2 SiLU, 3 Mish; gate 1 takes a token's channels as [ A | B ] and gives f(A) B on half of them (SwiGLU, GeGLU).  A missing gate cell means 0,
+    // further cells are ignored.  The reference prints "( N n -- ) one param required!" here
+    if (op == T4K_L_ELU && TOS1T() && TTOS().rank == 1 && SP() > 0 && is_m(SS(-1))) {
+        Tensor &t = TTOS();
+        std::vector<float> vo; t.to_host(vo, std::min<uint64_t>(t.numel, 2));
+        DU x = POP(); DROP(x);                           // the vector is dropped and freed, as the pool, batchnorm, attention, addnorm and embedding branches do
+        uint16_t opt[4] = {0, 0, 0, 0};
+        for (size_t i = 0; i < vo.size(); i++) opt[i] = (uint16_t)(int)vo[i];
+        MTOS().add(T4K_L_GATEACT, 0, 0, opt);
+        return;
+    }
     // beyond the reference ( N m -- N ): a scalar axis mask on top of a model makes `softmax` a layer of its tensor twin's meaning (`T m softmax` above): m = 1,
     // the C axis, is a softmax over the channels of every (n, h, w) token - the per-token head whose id targets make a language-model loss;
     // the reference prints "( N -- ) no param needed!" here and leaves the scalar, which every other m still gets (mask 7 is what plain `softmax` means, the
