@@ -496,6 +496,38 @@ int t4k_conv2d_geo_bwd(const float *I, const float *DO, float *DX, float *DX2, c
  *         launches of a whole backward (3) }. */
 int t4k_conv2d_geo_plan(int N, int H1, int W1, int C1, int C0, int K, int S, int P, int D,
                         int aligned, int out[8]);
+/* Patch embedding (csrc/patch.hip): conv2d with stride == kernel size and no padding, what "TODO: stride, dilation" nmath.tcu:12 and the
+ * 1x1..7x7 test of Model::_iconv model.cpp:124-137 leave out - the first layer of a ViT, DeiT or MLP-Mixer (K 14, 16, 32) and ConvNeXt's 4 / 4 / 0 stem.
+ * H0 = H1 / K, W0 = W1 / K (floor; W0 from W1): rows from H0 K and columns from W0 K of the image are not read.
+ *   O[n,ph,pw,c0] = B[c0] + sum_{c1,ky,kx} F[((c1*K+ky)*K+kx)*C0+c0] * I[n,ph*K+ky,pw*K+kx,c1]     (O is written once, not accumulated)
+ * = torch.nn.functional.conv2d(x, w, b, stride=K) with w[c0][c1][ky][kx] = F[c1,ky,kx,c0].
+ * Admitted: 2 <= K <= 32, every extent >= 1, H1 >= K and W1 >= K, N H1 W1 C1 and N H0 W0 C0 below 2^31, one dF | dB slab ((K K C1 + 1) C0 floats) within
+ * half the stream workspace.  An extent below 1 or a NULL tensor: T4K_ERR_ARG; anything else outside the set: T4K_ERR_UNSUPPORTED; either leaves a
+ * t4k_last_error text and writes nothing.  ICOPY (may be NULL) receives I by a copy command.  One kernel launch; no allocation, no synchronisation
+ * (legal under capture); t4k_conv_last_plan: "patch<64|128,v4|v1,f4|f1>" (channel tile, 16-byte or dword gather of I, 16-byte or dword loads of F). */
+int t4k_patch_fwd(const float *I, float *ICOPY, float *O, const float *F, const float *B,
+                  int N, int H1, int W1, int C1, int C0, int K, t4k_stream_t s);
+/* its backward (k_dconv2d nmath.tcu:211-338 finished for nmath.tcu:12; model.cpp:124-137): DF[c1,ky,kx,c0] += sum_{n,ph,pw} I[n,ph*K+ky,pw*K+kx,c1] * dO[n,ph,pw,c0]
+ * and DB[c0] += sum dO (both only if train; DF and DB go together); DX[n,y,x,c1] = sum_c0 F[c1,y%K,x%K,c0] * dO[n,y/K,x/K,c0] for y < H0 K and x < W0 K, 0
+ * elsewhere - every element of DX stored exactly once, by ONE launch - and the optional second copy DX2, which may be I itself (dF | dB read I first).
+ * DX == NULL: dF | dB only; DF == DB == NULL: dX only.  At most three launches (slabs, their fold, dX), one for dX alone; fixed summation order, no
+ * atomics; the slabs live in the stream workspace half t4k_conv2d_geo_bwd uses and are folded by the same two kernels.
+ * t4k_conv_last_plan: "patch_dfxN<i4|i1,d4|d1>" (N token slices; 16-byte or dword gather of I, loads of dO), "fold_add" or "df_fold", "patch_dx<64|128,v4|v1>". */
+int t4k_patch_bwd(const float *I, const float *DO, float *DX, float *DX2, const float *F,
+                  float *DF, float *DB,
+                  int N, int H1, int W1, int C1, int C0, int K, int train, t4k_stream_t s);
+/* The plan the two entries above take (nmath.tcu:12; model.cpp:124-137); pure host arithmetic: launches nothing, needs no device; the launch code calls the
+ * same function.  Admission and return codes as above (out == NULL: T4K_ERR_ARG); a refusal leaves out untouched.
+ * aligned: bit 0 I, bit 1 F, bit 2 dO on 16 bytes; bit 3 set: DB does NOT lie right behind DF (DB != DF + C1 K K C0).
+ * out = { forward channel tile (64 | 128; the token tile is 128),
+ *         forward load path (bit 0: 16-byte gather of I - (K C1) % 4 == 0, (W1 C1) % 4 == 0 and I aligned; bit 1: 16-byte loads of F - C0 % 4 == 0 and F aligned),
+ *         dX column tile over (ky, kx, c1) (64 | 128), dX load path (1: 16-byte loads of dO and F - C0 % 4 == 0, both aligned),
+ *         dF load path (bit 0: 16-byte gather of I, as the forward's; bit 1: 16-byte loads of dO - C0 % 4 == 0 and dO aligned),
+ *         dF slices (token slices of whole 32-token stages aiming at 1024 workgroups over the 64 x 64 tiles of (K K C1 + 1) x C0, shrunk until the slabs
+ *                    fit 8 MiB of workspace - down to one, which may take the 32 MiB),
+ *         the fold behind them (1: k_fold_add - up to 32 slices and DB right behind DF; 2: k_conv_df_fold),
+ *         launches of a whole backward (3) }. */
+int t4k_patch_plan(int N, int H1, int W1, int C1, int C0, int K, int aligned, int out[8]);
 /* Grouped and depthwise conv2d with RUN-TIME geometry (csrc/conv_group.hip): the entries above with the channels cut into G groups.  The reference has
  * NO groups - Model::_iconv model.cpp:121-180 allocates the dense T4(C1, K, K, C0) and k_conv2d ("TODO: stride, dilation" nmath.tcu:12) walks every input
  * channel - so there is no quirk to keep: this finishes those two for torch's conv2d(groups=G).  With Cg1 = C1 / G and Cg0 = C0 / G, output channel c0

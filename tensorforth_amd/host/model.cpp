@@ -214,11 +214,16 @@ Model &Model::add(int fn, uint32_t n, DU bias, uint16_t *opt) {
         const bool txn = fn == T4K_L_DCONV;
         const uint32_t N1 = in.N(), H1 = in.H(), W1 = in.W(), C1 = in.C(), C0 = n;
         const uint16_t K = opt[0], S = opt[1];
-        const uint16_t P = (K > 1 && opt[2]) ? opt[2] : (K - 1) / 2;
+        uint16_t P = (K > 1 && opt[2]) ? opt[2] : (K - 1) / 2;
         uint16_t H0, W0, D = 0;
         uint32_t G = 1;
         if (txn) { const uint16_t P0 = (H1 + P * 2 - K) % S; H0 = (H1 - 1) * S - P * 2 + K + P0; W0 = (W1 - 1) * S - P * 2 + K + P0; }
-        else {
+        else if (K >= 8 && K <= 32 && S == K && !opt[2] && opt[3] <= 1 && opt[4] <= 1) {
+            // the patch form: K 8..32 with the stride equal to it - here the P cell's 0 is NO padding, (K - 1) / 2 under stride K has no use;
+            // a floor grid, W0 from W1 (quirk :137 is not extended to a geometry the reference never computes)
+            if (H1 < K || W1 < K) { hprintf("nn#iconv %s stride=%d padding=%d dilation=%d?\n", LAYER_NAME[fn], S, 0, 1); return *this; }
+            P = 0; D = 1; H0 = H1 / K; W0 = W1 / K;
+        } else {
             // conv2d takes any K 1..7 with stride, padding and dilation (the reference: "TODO: dilation" model.cpp:125): a D cell of 0 means 1
             if (K < 1 || K > 7) { hprintf("nn#iconv %s f=[%d,%d]? 1x1 to 7x7 supported only.\n", LAYER_NAME[fn], K, K); return *this; }
             D = opt[3] ? opt[3] : 1;
@@ -430,8 +435,17 @@ static void geo_refusal(const char *who, int K, int S, int P, int D, int G) {   
     if (D > 1) hprintf("%s failed: %s kernel_size=%d stride=%d padding=%d dilation=%d%s not supported\n", who, who, K, S, P, D, grp);
     else       hprintf("%s failed: %s kernel_size=%d stride=%d padding=%d%s not supported\n", who, who, K, S, P, grp);
 }
+// A patch layer (K 8..32, S == K, P == 0) is a run-time-geometry convolution to every recogniser - conv_geo() is true of it, none of the four
+// geometries having K > 7 - and runs t4k_patch_fwd / _bwd, referenced weakly as the entries above
+#pragma weak t4k_patch_fwd
+#pragma weak t4k_patch_bwd
+static bool conv_patch(const Tensor &in) { return in.grad[0]->H() > 7; }
 static int geo_fwd(Tensor &in, Tensor &out, const float *x, float *cp, t4k_stream_t s) {
     const int K = in.grad[0]->H(), S = in.stride[0], P = in.stride[2], G = conv_G(in);
+    if (conv_patch(in)) {
+        if (!t4k_patch_fwd) { geo_refusal("nn#fconv", K, S, P, 1, 1); return T4K_ERR_UNSUPPORTED; }
+        return chk(t4k_patch_fwd(x, cp, out.data, in.grad[0]->data, in.grad[1]->data, out.N(), in.H(), in.W(), in.C(), out.C(), K, s), "nn#fconv");
+    }
     if (G > 1) {
         if (!t4k_conv2d_grp_fwd) { geo_refusal("nn#fconv", K, S, P, conv_D(in), G); return T4K_ERR_UNSUPPORTED; }
         return chk(t4k_conv2d_grp_fwd(x, cp, out.data, in.grad[0]->data, in.grad[1]->data, out.N(), in.H(), in.W(), in.C(), out.H(), out.W(), out.C(),
@@ -443,6 +457,11 @@ static int geo_fwd(Tensor &in, Tensor &out, const float *x, float *cp, t4k_strea
 }
 static int geo_bwd(Tensor &in, Tensor &out, const float *dy, float *dx, float *dx2, const float *w, bool grads, int train, t4k_stream_t s) {
     const int K = in.grad[0]->H(), S = in.stride[0], P = in.stride[2], G = conv_G(in);
+    if (conv_patch(in)) {
+        if (!t4k_patch_bwd) { geo_refusal("nn#bconv", K, S, P, 1, 1); return T4K_ERR_UNSUPPORTED; }
+        return chk(t4k_patch_bwd(in.data, dy, dx, dx2, w, grads ? in.grad[2]->data : nullptr, grads ? in.grad[3]->data : nullptr,
+                                 in.N(), in.H(), in.W(), in.C(), out.C(), K, train, s), "nn#bconv");
+    }
     if (G > 1) {
         if (!t4k_conv2d_grp_bwd) { geo_refusal("nn#bconv", K, S, P, conv_D(in), G); return T4K_ERR_UNSUPPORTED; }
         return chk(t4k_conv2d_grp_bwd(in.data, dy, dx, dx2, w, grads ? in.grad[2]->data : nullptr, grads ? in.grad[3]->data : nullptr,
