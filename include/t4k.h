@@ -57,7 +57,8 @@ enum {
     T4K_L_ADDNORM,                     /* ... and add & norm, out = norm(x + skip), `vector{ back mode } selu` */
     T4K_L_EMBED,                       /* ... and the embedding layer, token and learned position tables, `vector{ V E pos } upsample` */
     T4K_L_TOKSMAX,                     /* ... and the per-token softmax / cross-entropy head over the channels, `1 softmax` */
-    T4K_L_GATEACT                      /* ... and the smooth and gated feed-forward activations, `vector{ kind gate } elu` */
+    T4K_L_GATEACT,                     /* ... and the smooth and gated feed-forward activations, `vector{ kind gate } elu` */
+    T4K_L_RETN                         /* ... and multi-scale retention, `vector{ heads 1 1 } linear` */
 };
 /* rand_opt: reference src/util.h:22-25 */
 enum { T4K_UNIFORM = 0, T4K_NORMAL = 1 };
@@ -796,6 +797,29 @@ int t4k_gateact_fwd(const float *X, float *Y, long T, int C, int kind, int gate,
 /* DX [T, C] from X [T, C] and DY [T, Hc], one launch.  DX may be X itself (a lane stores to the addresses it loaded); any other overlap among the three:
  * T4K_ERR_ARG. */
 int t4k_gateact_bwd(const float *X, const float *DY, float *DX, long T, int C, int kind, int gate, t4k_stream_t s);
+/* multi-scale retention on NHWC fp32 tokens, chunkwise (csrc/retention.hip): RetNet's retention without xPos, group norm and gate.  The
+ * reference has no such layer (its README lists "Retentive" for v4.2).  QKV is [N, L, 3E] and O is [N, L, E] exactly as t4k_attention_fwd takes them.  Per
+ * (n, head h), with g = 1 - 2^(-5-h) and scale = (float)(1 / sqrt((double)d)):  Y_i = scale sum_{j <= i} g^(i-j) (Q_i . K_j) V_j.  Every power of g is
+ * exp2f(l dist), l = (float)log2(g) formed in double, dist an integer distance of tokens.  The tokens are cut into chunks of B; ST is [N, heads, chunks, d, d]:
+ * ST_c = sum_{j < cB} g^(cB-1-j) K_j^T V_j, the state in front of chunk c, which the backward reads again.  A call of one chunk neither writes nor reads ST.
+ * Admission and the plan, on the host alone (no device needed; the entries call the same function).  An extent below 1, heads above 32 (g rounds to 1 in
+ * float beyond), NULL out or ws_bytes < 0: T4K_ERR_ARG; d outside 4 .. 128 or d % 4 != 0, N L 3E at or above 2^31, or 4 N heads (chunks - 1) d d bytes of
+ * reverse states that do not fit ws_bytes: T4K_ERR_UNSUPPORTED; out is untouched then.
+ * out = { rung (1: d <= 16, 2: d <= 32, 3: d <= 64, 4: d <= 128 - the head size the kernels pad to), load path (4 = 16 bytes per lane, 1 = dwords),
+ *         chunk B (64; 32 on rung 4), chunks, forward launches, backward launches (1 with one chunk, else 3), workgroups of the chunk launch,
+ *         workspace bytes used (2^31 - 1 where they are more) };  aligned != 0: every pointer of the call on 16 bytes */
+int t4k_retention_plan(int N, int L, int heads, int d, int aligned, long ws_bytes, int out[8]);
+/* the forward.  Three launches: the chunk-local products U_c = sum_r g^(B-1-r) K_r^T V_r into ST (a workgroup per (n, head, chunk)), the scan
+ * ST_(c+1) = g^B ST_c + U_c in place (a thread per element, serial over the chunks), and the chunk launch: a workgroup owns (n, head, chunk), a wave 16
+ * queries; the masked and decayed scores stay in registers, ST_c comes through LDS as one more operand.  All products on fp32 MFMA.  O is written once per
+ * element.  No atomics, a fixed summation order, the same bits on every call; no allocation, no synchronisation.  A NULL QKV, O or ST: T4K_ERR_ARG.
+ * A refusal leaves a t4k_last_error text and writes nothing. */
+int t4k_retention_fwd(const float *QKV, float *O, float *ST, int N, int L, int heads, int d, t4k_stream_t s);
+/* its backward (autograd of the above), chunkwise with the reverse states R_c = sum_{i >= (c+1)B} g^(i-(c+1)B+1) Q_i^T DY_i in the stream's workspace:
+ * dQ_i = scale sum_{j <= i} g^(i-j) (DY_i . V_j) K_j,  dK_j = scale sum_{i >= j} g^(i-j) (DY_i . V_j) Q_i,  dV_j = scale sum_{i >= j} g^(i-j) (Q_i . K_j) DY_i.
+ * ST is what the forward left.  DQKV has QKV's layout and is written once per element; it must not overlap QKV, DY or ST (an overlap of the stated
+ * extents: T4K_ERR_ARG).  Three launches: chunk-local reverse products, the reverse scan, and one launch per chunk that gives dQ, dK and dV. */
+int t4k_retention_bwd(const float *QKV, const float *DY, const float *ST, float *DQKV, int N, int L, int heads, int d, t4k_stream_t s);
 /* k_sgd nmath.cu:419: dg=DG/Nw; beta~0: G-=lr*dg else M=b*M+(1-b)*dg, G-=lr*M; DG=0 */
 int t4k_sgd(float *G, float *DG, float *M, int Nw, float lr, float beta, long n, t4k_stream_t s);
 /* k_adam nmath.cu:438 (no bias correction, eps outside sqrt): zeroes DG */

@@ -60,6 +60,47 @@ static bool attn_from_line(Tensor &in, const std::string &line) {
     return true;
 }
 
+// ---- retention, `vector{ heads 1 1 } linear`: the attention layer's token layout and shapes with RetNet's decayed causal sum in place of
+// the softmax.  Its own layer kind, T4K_L_RETN, so it joins no fused group either.  The layer runs t4k_retention_fwd / _bwd; mtum[4] holds the chunk states
+// the forward leaves for the backward (what the log-sum-exp is to attention), mtum[0] the staging tensor for dX.  The entries are referenced weakly, as above.
+#pragma weak t4k_retention_plan
+#pragma weak t4k_retention_fwd
+#pragma weak t4k_retention_bwd
+// the floats of the state tensor, N heads chunks d d; 0: C, heads or the extents are not admitted (t4k_retention_plan's rule, restated where the C-ABI lacks it)
+static uint64_t retn_states(int N, int L, int C, int heads) {
+    if (heads < 1 || heads > 32 || C % 3 || (C / 3) % heads) return 0;
+    const int d = C / 3 / heads;
+    int out[8] = { 0, 0, d > 64 ? 32 : 64, 0, 0, 0, 0, 0 };
+    if (t4k_retention_plan) { if (t4k_retention_plan(N, L, heads, d, 1, 1L << 40, out) != T4K_OK) return 0; }
+    else if (d < 4 || d > 128 || d % 4 != 0 || (long)N * L * C >= (1L << 31)) return 0;
+    return (uint64_t)N * heads * ((L + out[2] - 1) / out[2]) * d * d;
+}
+static int retn_fwd(Tensor &in, Tensor &out, const float *x, t4k_stream_t s) {
+    const int heads = in.iparm;
+    if (!t4k_retention_fwd) { hprintf("nn#fretention failed: nn#fretention heads=%d not supported\n", heads); return T4K_ERR_UNSUPPORTED; }
+    return chk(t4k_retention_fwd(x, out.data, in.mtum[4]->data, in.N(), in.H() * in.W(), heads, out.C() / heads, s), "nn#fretention");
+}
+static int retn_bwd(Tensor &in, Tensor &out, const float *dy, t4k_stream_t s) {         // dX into the staging tensor, then over x: the reference's `in = dx`
+    const int heads = in.iparm;
+    if (!t4k_retention_bwd) { hprintf("nn#bretention failed: nn#bretention heads=%d not supported\n", heads); return T4K_ERR_UNSUPPORTED; }
+    const int rc = chk(t4k_retention_bwd(in.data, dy, in.mtum[4]->data, in.mtum[0]->data, in.N(), in.H() * in.W(), heads, out.C() / heads, s), "nn#bretention");
+    if (rc != T4K_OK) return rc;
+    return chk(t4k_copy(in.mtum[0]->data, in.data, (long)in.numel, s), "nn#bretention in = dx");
+}
+// model_load: `heads=<h>, decay=1retentn` replaces the layer's head count where the channels admit it (the state tensor follows it)
+static bool retn_from_line(Tensor &in, const std::string &line) {
+    int heads = 0, decay = 0; char tail[16] = "";
+    if (sscanf(line.c_str(), "heads=%d, decay=%d%15s", &heads, &decay, tail) != 3 || strcmp(tail, "retentn") || decay != 1) return false;
+    const uint64_t ns = retn_states(in.N(), in.H() * in.W(), in.C(), heads);
+    if (!ns) return false;
+    if (heads != in.iparm) {
+        Store::get().free(*in.mtum[4]);
+        in.mtum[4] = &Store::get().tensor(ns);
+        in.iparm = heads;
+    }
+    return true;
+}
+
 // ---- add & norm, `vector{ back mode } selu`: out = norm(x + skip).  Its own layer kind, T4K_L_ADDNORM, so it joins no fused group - the run,
 // stack, head and block recognisers (plan_runs, stack_at, lin_kind, blinear, run_backward) all name the kinds they take, and none names this one.  The skip
 // source is the OUTPUT of an earlier layer of this kind, so this kind alone owns a skip's boundary in both directions: no other layer learns about skips.
@@ -400,6 +441,18 @@ Model &Model::add(int fn, uint32_t n, DU bias, uint16_t *opt) {
         if (!ga_admits((long)in.N() * in.H() * in.W(), C, kind, gate)) { hprintf("nn#igateact kind=%d gate=%d? channels=%d\n", kind, gate, C); return *this; }
         in.iparm = kind; in.stride[0] = (uint16_t)gate; in.stride[1] = in.stride[2] = in.stride[3] = 0; in.xparm = 0;
         layer.push_back(&T4(in.N(), in.H(), in.W(), gate ? C / 2 : C));
+    } break;
+    case T4K_L_RETN: {
+        // `vector{ heads 1 1 } linear`: multi-scale retention over the H W tokens of a sample (the reference has none), the attention layer's
+        // channels and shapes.  The decay is causal by its rule: a third cell with causal == 0 is refused.  No parameters: grad[0..4] stay NULL and the
+        // optimizer's table skips the layer.  mtum[4] holds the chunk states, mtum[0] the staging tensor the backward writes dX into
+        const int C = in.C(), heads = opt ? opt[0] : 0;
+        const uint64_t ns = (opt && opt[1]) ? retn_states(in.N(), in.H() * in.W(), C, heads) : 0;
+        if (!ns) { hprintf("nn#iretention heads=%d? channels=%d\n", heads, C); return *this; }
+        in.mtum[4] = &VEC(ns);
+        in.mtum[0] = &T4(in.N(), in.H(), in.W(), C);
+        in.iparm = heads; in.stride[0] = 1; in.xparm = 0;
+        layer.push_back(&T4(in.N(), in.H(), in.W(), C / 3));
     } break;
     default: hprintf("Model#add layer %d not supported\n", fn); return *this;
     }
@@ -949,6 +1002,7 @@ const float *Model::fstep(Tensor &in, Tensor &out, const float *x) {
     case T4K_L_EMBED: em_fwd(in, out, x, s); break;
     case T4K_L_TOKSMAX: ts_fwd(in, out, x, s); break;
     case T4K_L_GATEACT: ga_fwd(in, out, x, s); break;
+    case T4K_L_RETN: retn_fwd(in, out, x, s); break;
     default: hprintf("nn#fstep layer=%d not supported\n", fn);
     }
     return out.data;
@@ -1355,6 +1409,7 @@ Model::Back Model::bstep(int i, Tensor &in, Tensor &out, const float *dy, bool l
         if (last) { lazy_copy(dy, in); return { dy }; }                      // a dense target: out - target passes through, as behind a softmax
         ts_bwd(in, dy, s); break;                                            // inside a net: the Jacobian product, not the reference's pass-through
     case T4K_L_GATEACT: ga_bwd(in, dy, s); break;
+    case T4K_L_RETN: retn_bwd(in, out, dy, s); break;
     case T4K_L_EMBED: em_bwd(in, out, dy, train, s); break;      // position mode: dX = dY over x (the reference's `in = dx`); token mode writes nothing into the ids, so a second backprop sees them
     default: hprintf("nn#bstep layer=%d not supported\n", fn);
     }
@@ -1537,7 +1592,8 @@ Model &Model::adamw(DU lr, DU wd, DU b1, DU b2) { return gradient("adamw", OPTI_
 // no blob: its `heads=<h>, causal=<c>attentn` line is read back into the model's attention layer at that place.  An add & norm layer saves
 // gamma and beta where it has them (mode != 0); its `back=<b>, mode=<m>addnorm` line must be the layer's own - a file with another is refused whole.  An
 // embedding layer saves TABLE ('w') and POS ('b'), whichever it has; its `vocab=<V>, pos=<p>embed  ` line is held to the same.  An
-// activation of DESIGN.md 3.24 has no blob: its `kind=<k>, gate=<g>gateact` line must carry the layer's gate, and its kind is read back into the layer.
+// activation of DESIGN.md 3.24 has no blob: its `kind=<k>, gate=<g>gateact` line must carry the layer's gate, and its kind is read back into the layer.  A
+// retention layer is read back as an attention layer is, from its `heads=<h>, decay=1retentn` line.
 int model_save(Model &m, const char *fname) {
     FILE *f = fopen(fname, "wb");
     if (!f) { hprintf("} => failed to open for output\n"); return 1; }
@@ -1585,6 +1641,7 @@ int model_load(Model &m, const char *fname) {
         if (m.at(i).grad_fn == T4K_L_GATEACT && !ga_from_line(m.at(i), line_of(i), false)) { hprintf(" model format error (gateact layer %d: %s)\n", i, line_of(i).c_str()); err = 1; }
     if (err) { fclose(f); return err; }
     for (int i = 0; i + 1 < (int)m.layer.size() && i + 1 < (int)lines.size(); i++) {
+        if (m.at(i).grad_fn == T4K_L_RETN && !retn_from_line(m.at(i), lines[i + 1])) { hprintf(" model format error (retention layer %d: %s)\n", i, lines[i + 1].c_str()); err = 1; }
         if (m.at(i).grad_fn != T4K_L_ATTN) continue;
         if (!attn_from_line(m.at(i), lines[i + 1])) { hprintf(" model format error (attention layer %d: %s)\n", i, lines[i + 1].c_str()); err = 1; }
     }

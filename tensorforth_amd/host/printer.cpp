@@ -117,6 +117,7 @@ static std::string parm_s(Tensor &in, Tensor &out) {     // aio_model.cpp:103-14
     case T4K_L_EMBED: o << "vocab=" << in.iparm << ", pos=" << S; break;       // `vector{ V E pos } upsample`
     case T4K_L_TOKSMAX: o << "axes=" << in.iparm; break;                       // `1 softmax`
     case T4K_L_GATEACT: o << "kind=" << in.iparm << ", gate=" << S; break;     // `vector{ kind gate } elu`
+    case T4K_L_RETN: o << "heads=" << in.iparm << ", decay=" << S; break;      // `vector{ heads 1 1 } linear`
     default: break;
     }
     return o.str();

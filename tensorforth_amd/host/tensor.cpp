@@ -12,7 +12,7 @@ namespace t4 {
 
 const char *LAYER_NAME[] = { "output ", "conv2d ", "linear ", "flatten", "relu   ", "tanh   ", "sigmoid", "selu   ",
                              "leakyrl", "elu    ", "dropout", "softmax", "logsmax", "avgpool", "maxpool", "minpool",
-                             "batchnm", "upsampl", "dconv2d", "attentn", "addnorm", "embed  ", "toksmax", "gateact" };        // (attentn, addnorm, embed, toksmax, gateact: beyond the reference's list)
+                             "batchnm", "upsampl", "dconv2d", "attentn", "addnorm", "embed  ", "toksmax", "gateact", "retentn" };        // (attentn .. retentn: beyond the reference's list)
 
 static bool g_ready = false;
 static float *g_scalar = nullptr;       // device scratch for reductions (replaces Tensor::_tmp)

@@ -455,15 +455,16 @@ void VM::nnop(int op) {
         return;
     }
     // beyond the reference ( N V -- N ): a vector{ heads causal } on top of a model makes `linear` a multi-head attention layer over the H W tokens of a
-    // sample, the 3E channels of a token being [ Q | K | V ]; a missing causal cell means 0, further cells are ignored.  The reference
-    // prints "( N [bias] n -- ) for linear required!" here
+    // sample, the 3E channels of a token being [ Q | K | V ]; a missing causal cell means 0.  A third cell, decay, that is 1 makes it the
+    // retention layer on the same channels; any other value there is ignored, as it and further cells always were.  The reference prints
+    // "( N [bias] n -- ) for linear required!" here
     if (op == T4K_L_LINEAR && TOS1T() && TTOS().rank == 1 && SP() > 0 && is_m(SS(-1))) {
         Tensor &t = TTOS();
-        std::vector<float> vo; t.to_host(vo, std::min<uint64_t>(t.numel, 2));
+        std::vector<float> vo; t.to_host(vo, std::min<uint64_t>(t.numel, 3));
         DU x = POP(); DROP(x);                           // the vector is dropped and freed, as the pool and batchnorm branches do
         uint16_t opt[4] = {0, 0, 0, 0};
         for (size_t i = 0; i < vo.size(); i++) opt[i] = (uint16_t)(int)vo[i];
-        MTOS().add(T4K_L_ATTN, 0, 0, opt);
+        MTOS().add(opt[2] == 1 ? T4K_L_RETN : T4K_L_ATTN, 0, 0, opt);
         return;
     }
     // beyond the reference ( N V -- N ): a vector{ back mode } on top of a model makes `selu` an add & norm layer, out = norm(x + skip): the skip is the
